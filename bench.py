@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- EM iterations/sec of the Vireo VB hot path on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K=200] [--warmup W=50] [--config c3|mid|c2] [--no-cpu] [--no-c4]
-                  [--comm rccl|tcp]
+  python bench.py [--gpus N] [--steps K=200] [--warmup W=50] [--config c3|mid|c2] [--dump-outputs DIR]
+                  [--full [--no-cpu] [--no-c4] [--no-side-legs] [--only-headline]] [--comm rccl|tcp]
 
 A step is ONE full coordinate-ascent iteration (theta update, GT update, ID update, ELBO:
 vireoSNP/utils/vireo_model.py:257-264) over the synthetic AD/DP of SURVEY.md 8(d), inputs
@@ -10,8 +10,21 @@ and state already resident in HBM.  Default workload = BASELINE.json configs[2]
 (N=100k variants x M=50k cells, K=16, ~2 % nnz), the configuration the metric is quoted on.
 The W warm-up iterations are the protocol's start (delay_fit_theta=3: the first three without the
 theta update, so every kernel of the timed iterations has been launched once), the K timed ones
-all run with it.  The GPU legs this run executes anyway (c2, c5's GPU half, the c4 restart
-search, and last -- directly before the warm-up, nothing but Python call overhead in between --
+all run with it.
+
+A plain run (no --full) does what the headline needs and nothing else: inputs, problem build,
+this rank's whole-protocol fit on a second model continued until the chip has worked ~0.5 s (its
+clocks; the timed model's state is untouched), the W warm-up and K timed iterations, the line.
+Its `roofline`, `ms_per_step_repeats` and every leg below are null; `comm` is backend and world.
+--dump-outputs DIR writes what the timed iterations computed, rank 0's model after the last of
+them: elbo (the K timed ELBOs), ID_prob, GT_prob, beta_mu, beta_sum as DIR/<name>.npy, float64,
+64 MB at most (a seeded row sample of the larger ones beyond that; c3 fits whole).  The inputs are
+fixed by --config (seed 0) and the model's start by np.random.seed(1): two builds compare output
+for output.
+
+--full runs everything else as well, as described from here on.  The GPU legs it executes (c2,
+c5's GPU half, the c4 restart search, and last -- directly before the warm-up, nothing but Python
+call overhead in between --
 every rank's own whole-protocol fit of its restart, at N = 1 also the perturbed copy of the
 parity check) come BEFORE the timed region and are listed in `preceded_by`: the chip used to
 idle through ~20 s of host-side input generation right before a 16-ms timed window (driver flags
@@ -27,7 +40,7 @@ exchanges).  `--comm tcp` (host sockets, ranks sharing one device: a plumbing re
 box) must be asked for on THIS command line: a VIREO_COMM=tcp merely inherited from the environment
 is refused for N > 1, and a line it produces carries "scaling": "plumbing-only", never "weak".
 
-Besides the headline value the line carries
+Besides the headline value the line of a --full run carries
   roofline      the dominant sparse pass against the HBM roofline (HIP events on the library's
                 stream; PMC traffic from profiles/traffic_<config>.json when it was collected
                 on the same kernel sources),
@@ -68,6 +81,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0            # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md
 PROTOCOL = dict(min_iter=5, max_iter=20, delay_fit_theta=3)
+CLOCK_RAMP_S = 0.5               # continuous work before a plain run's warm-up (the clocks' ramp)
+DUMP_BYTES = 64 * 10**6          # --dump-outputs: at most this much in all
 
 
 def algorithmic_bytes(N, M, K, T, nnz):
@@ -86,6 +101,52 @@ def kernel_source_hash():
     for f in ("vrx_kernels.h", "vrx_engine.hip", "vrx_common.h"):
         h.update(open(os.path.join(ROOT, "vireo_amd", "csrc", f), "rb").read())
     return h.hexdigest()[:16]
+
+
+def donor_workload(N, M, K, density, seed=0):
+    """synth.donor_workload(N, M, K, density, seed) bit for bit -- the same draws in the same order --
+    sorted in a fraction of the time: its stable argsort of the (column, row) keys is most of a plain
+    run's start-up at c3 (~20 s for 1e8 keys).  Here (ad, dp) ride in the low bits of the keys and ONE
+    unstable sort orders them; entries with equal keys are summed, so their order never mattered.
+    (tests/test_host_cpu.py holds the two generators equal.)"""
+    from vireo_amd import synth
+    rng = np.random.default_rng(seed)
+    nnz_t = int(N * M * density)
+    r = rng.integers(0, N, nnz_t)
+    c = rng.integers(0, M, nnz_t)
+    dp = 1 + rng.poisson(1.0, nnz_t)
+    GT = rng.integers(0, 3, (N, K))
+    z = rng.integers(0, K, M)
+    theta = np.array([0.01, 0.5, 0.99])[GT[r, z[c]]]
+    ad = rng.binomial(dp, theta)
+    del theta
+    fb = max(int(dp.max()).bit_length(), 1)              # bits of one count field (ad <= dp)
+    if int(N * M - 1).bit_length() + 2 * fb > 63:
+        return synth.donor_workload(N, M, K, density, seed=seed)
+    packed = c * np.int64(N) + r
+    del r, c
+    packed <<= 2 * fb
+    packed |= ad << fb
+    del ad
+    packed |= dp
+    del dp
+    packed.sort()
+    key = packed >> (2 * fb)
+    first = np.empty(nnz_t, dtype=bool)
+    first[0] = True
+    np.not_equal(key[1:], key[:-1], out=first[1:])
+    starts = np.flatnonzero(first)
+    del first
+    key = key[starts]
+    mask = np.int64((1 << fb) - 1)
+    dp = np.add.reduceat(packed & mask, starts).astype(np.int32)
+    ad = np.add.reduceat((packed >> fb) & mask, starts).astype(np.int32)
+    del packed, starts
+    col = key // N
+    rowidx = (key - col * N).astype(np.int32)
+    colptr = np.zeros(M + 1, dtype=np.int64)
+    np.cumsum(np.bincount(col, minlength=M), out=colptr[1:])
+    return dict(shape=(N, M), colptr=colptr, rowidx=rowidx, ad=ad, dp=dp, GT=GT, z=z)
 
 
 def stream_choice():
@@ -513,6 +574,27 @@ def comm_leg(comm, device, dm, host):
     return rec
 
 
+def dump_outputs(path, arrays, limit=DUMP_BYTES):
+    """--dump-outputs: every array as <path>/<name>.npy (float64).  Over `limit` bytes in all, the
+    larger arrays keep a fixed, seeded sample of their rows (sorted; <name>_rows.npy says which)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    head = 256                                            # (bytes of a .npy header, at most)
+    big = [k for k, a in arrays.items() if a.ndim > 0 and a.nbytes > limit // 16]
+    if sum(a.nbytes + head for a in arrays.values()) <= limit:
+        big = []
+    small = sum(a.nbytes for k, a in arrays.items() if k not in big) + head * (len(arrays) + len(big))
+    # kept rows cost their bytes + 8 for their index: the fraction that keeps the whole within `limit`
+    frac = (limit - small) / max(sum(a.nbytes + 8 * a.shape[0] for k, a in arrays.items() if k in big), 1)
+    for name, a in arrays.items():
+        if name in big:
+            keep = max(1, int(a.shape[0] * frac))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def side_leg(name, fn, *a, **k):
     """a side leg must never cost the run its headline: an exception becomes {"error": ...}"""
     try:
@@ -539,8 +621,13 @@ def main():
     ap.add_argument("--comm", choices=("rccl", "tcp"), default=None,
                     help="tcp: host sockets instead of RCCL, for ranks that share ONE device "
                          "(a plumbing rehearsal; the line is marked plumbing-only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline as well: the legs above, the repeats, the roofline "
+                         "events, the communicator's timings (without it: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed iterations computed (rank 0's last step) as DIR/<name>.npy")
     args = ap.parse_args()
-    if args.only_headline:
+    if args.only_headline or not args.full:
         args.no_cpu = args.no_c4 = args.no_side_legs = True
     # The communicator of a multi-GPU line is chosen on THIS command line.  VIREO_COMM=tcp left
     # behind in an environment would otherwise turn the driver's `bench.py --gpus 8` into a
@@ -596,7 +683,7 @@ def main():
     N, M, K, dens = synth.CONFIGS[args.config]
     T = 3
     t_gen = time.perf_counter()
-    w = synth.donor_workload(N, M, K, dens, seed=0)
+    w = donor_workload(N, M, K, dens, seed=0)
     t_gen = time.perf_counter() - t_gen
     nnz = int(w["rowidx"].size)
     # The headline runs on BALANCED SLABS (vrx_problem_create2, VRX_PROBLEM_BALANCED: which contracted rows
@@ -688,9 +775,9 @@ def main():
         pert.ID_prob = pert.ID_prob * (1.0 + 1e-13 * np.random.default_rng(7).standard_normal(pert.ID_prob.shape))
         pert_dm, _ = pert._device_model(counts, None)
         del pert
-    tg = time.perf_counter()
+    t_fit = time.perf_counter()
     gfull, git, _ = proto_dm.fit(*fit_args)
-    tg = time.perf_counter() - tg
+    tg = time.perf_counter() - t_fit
     n_pre = 1
     if pert_dm is not None:
         pfull, pit, _ = pert_dm.fit(*fit_args)
@@ -699,6 +786,17 @@ def main():
     preceded_by.append("whole-protocol fit of this rank's restart on the GPU (%d x %d iterations%s)"
                        % (n_pre, git + 1, "; the parity check downloads their results after the timed region"
                           if pert_dm is not None else ""))
+    if not args.full:
+        # A plain run has no legs before its timed region, and the chip has idled through the input
+        # generation: its clocks need ~0.4 s of continuous work (DESIGN_HISTORY.md section 6), or the
+        # timed steps run ~10 % slow.  The protocol fit's model iterates on until then; the timed
+        # model's state is untouched, `warmup` stays what the flag says.
+        n_ramp = 0
+        while time.perf_counter() - t_fit < CLOCK_RAMP_S:
+            proto_dm.run_iters(50, theta_from_iter=0)
+            n_ramp += 50
+        preceded_by.append("clock ramp: %d more iterations of the protocol fit's model (%.1f s of work with the fit)"
+                           % (n_ramp, CLOCK_RAMP_S))
 
     if args.warmup > 0:
         dm.run_iters(args.warmup, theta_from_iter=PROTOCOL["delay_fit_theta"])
@@ -712,32 +810,38 @@ def main():
     wall_max = float(np.max(walls))
     last_elbos = comm.allgather(np.array([trace[-1]]))            # the restart-shard exchange
     proto_elbos = comm.allgather(np.array([gfull[git - 1]]))      # ELBO[:it][-1] of every rank's protocol fit
+    if args.dump_outputs and rank == 0:
+        ID, GT, mu, sm = dm.get_state(want_GT=True)
+        dump_outputs(args.dump_outputs, dict(elbo=trace, ID_prob=ID, GT_prob=GT, beta_mu=mu, beta_sum=sm))
+        del ID, GT
     # spread of the number above: the same K iterations four more times (not part of `value`)
     repeats = [wall / args.steps * 1e3]
-    for _ in range(4):
-        t0 = time.perf_counter()
-        dm.run_iters(args.steps, theta_from_iter=0)
-        repeats.append((time.perf_counter() - t0) / args.steps * 1e3)
+    comm_rec = dict(backend=comm.backend, world=world)
+    if args.full:
+        for _ in range(4):
+            t0 = time.perf_counter()
+            dm.run_iters(args.steps, theta_from_iter=0)
+            repeats.append((time.perf_counter() - t0) / args.steps * 1e3)
 
-    # roofline leg: the same K iterations again with every pass bracketed by HIP events on
-    # the library's stream
-    # (three times; the line reports the run with the median pass time and lists all three: the
-    #  boxes of the pool show a sporadic slow stretch -- one run of K iterations 15-30 % over its
-    #  neighbours, `ms_per_step_repeats` catches them too -- and one such stretch under this leg
-    #  used to BE the roofline figure)
-    prof_runs = []
-    for _ in range(3):
-        dm.profile(True)
-        dm.run_iters(args.steps, theta_from_iter=0)
-        prof_runs.append(dm.profile_read())
-    dm.profile(False)
-    prof_runs.sort(key=lambda r: r[0][_lib.KERN_VARIANT_PASS] + r[0][_lib.KERN_CELL_PASS])
-    ms, n = prof_runs[1]
-    kinfo = dm.info()
-    # (collective: every rank.  At N > 1 an exception in it is NOT swallowed like a side leg's: a rank
-    #  that stayed alive after a failed collective would leave the others waiting for it -- it exits,
-    #  the launcher stops the rest, the reason is on stderr)
-    comm_rec = comm_leg(comm, local, dm, host) if world > 1 else side_leg("comm", comm_leg, comm, local, dm, host)
+        # roofline leg: the same K iterations again with every pass bracketed by HIP events on
+        # the library's stream
+        # (three times; the line reports the run with the median pass time and lists all three: the
+        #  boxes of the pool show a sporadic slow stretch -- one run of K iterations 15-30 % over its
+        #  neighbours, `ms_per_step_repeats` catches them too -- and one such stretch under this leg
+        #  used to BE the roofline figure)
+        prof_runs = []
+        for _ in range(3):
+            dm.profile(True)
+            dm.run_iters(args.steps, theta_from_iter=0)
+            prof_runs.append(dm.profile_read())
+        dm.profile(False)
+        prof_runs.sort(key=lambda r: r[0][_lib.KERN_VARIANT_PASS] + r[0][_lib.KERN_CELL_PASS])
+        ms, n = prof_runs[1]
+        kinfo = dm.info()
+        # (collective: every rank.  At N > 1 an exception in it is NOT swallowed like a side leg's: a rank
+        #  that stayed alive after a failed collective would leave the others waiting for it -- it exits,
+        #  the launcher stops the rest, the reason is on stderr)
+        comm_rec = comm_leg(comm, local, dm, host) if world > 1 else side_leg("comm", comm_leg, comm, local, dm, host)
     dm.close()
     if parity_gpu is None:
         proto_dm.close()
@@ -852,38 +956,62 @@ def main():
     del w
 
     if rank == 0:
-        B = algorithmic_bytes(N, M, K, T, nnz)
-        avg_v = ms[_lib.KERN_VARIANT_PASS] / max(n[_lib.KERN_VARIANT_PASS], 1)
-        avg_c = ms[_lib.KERN_CELL_PASS] / max(n[_lib.KERN_CELL_PASS], 1)
-        avg_d = ms[_lib.KERN_DENSE] / max(args.steps, 1)
-        dom = "cell" if avg_c >= avg_v else "variant"
-        avg = max(avg_c, avg_v)
-        ach = B[dom] / (avg * 1e-3) / 1e9
         info = _lib.device_info(local)
-        # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this
-        # process; the figure comes from the committed rocprofv3 --pmc run of this same command
-        # (profiles/traffic_<config>.json, scratch/collect_traffic.py) and is quoted only when
-        # that run used the kernel sources this process was built from.
-        traffic, traffic_src = None, None
-        kname = ("vrx_spmm_lds<%d>" % (dom == "cell")) if kinfo["lds_" + dom] else None
-        tpath = os.path.join(ROOT, "profiles", "traffic_%s.json" % args.config)
-        if kname and os.path.exists(tpath):
-            doc = json.load(open(tpath))
-            rec = doc.get("kernels", {}).get(kname)
-            same_stream = args.config != "c3" or doc.get("stream") == stream_choice()
-            if rec and doc.get("kernel_source_hash") == kernel_source_hash() and same_stream:
-                traffic = rec["traffic_bytes"]
-                traffic_src = ("profiles/traffic_%s.json (rocprofv3 --pmc FETCH_SIZE x2 + "
-                               "WRITE_SIZE, kernel sources %s%s)"
-                               % (args.config, kernel_source_hash(),
-                                  ", " + doc["stream"] if doc.get("stream") else ""))
-            elif rec and not same_stream:
-                traffic_src = ("profiles/traffic_%s.json was collected on the other stream build (%s): "
-                               "not quoted" % (args.config, doc.get("stream")))
-            elif rec:
-                traffic_src = ("profiles/traffic_%s.json was collected on other kernel sources "
-                               "(%s, now %s): not quoted" % (args.config, doc.get("kernel_source_hash"),
-                                                             kernel_source_hash()))
+        roofline = None
+        if args.full:
+            B = algorithmic_bytes(N, M, K, T, nnz)
+            avg_v = ms[_lib.KERN_VARIANT_PASS] / max(n[_lib.KERN_VARIANT_PASS], 1)
+            avg_c = ms[_lib.KERN_CELL_PASS] / max(n[_lib.KERN_CELL_PASS], 1)
+            avg_d = ms[_lib.KERN_DENSE] / max(args.steps, 1)
+            dom = "cell" if avg_c >= avg_v else "variant"
+            avg = max(avg_c, avg_v)
+            ach = B[dom] / (avg * 1e-3) / 1e9
+            # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this
+            # process; the figure comes from the committed rocprofv3 --pmc run of this same command
+            # (profiles/traffic_<config>.json, scratch/collect_traffic.py) and is quoted only when
+            # that run used the kernel sources this process was built from.
+            traffic, traffic_src = None, None
+            kname = ("vrx_spmm_lds<%d>" % (dom == "cell")) if kinfo["lds_" + dom] else None
+            tpath = os.path.join(ROOT, "profiles", "traffic_%s.json" % args.config)
+            if kname and os.path.exists(tpath):
+                doc = json.load(open(tpath))
+                rec = doc.get("kernels", {}).get(kname)
+                same_stream = args.config != "c3" or doc.get("stream") == stream_choice()
+                if rec and doc.get("kernel_source_hash") == kernel_source_hash() and same_stream:
+                    traffic = rec["traffic_bytes"]
+                    traffic_src = ("profiles/traffic_%s.json (rocprofv3 --pmc FETCH_SIZE x2 + "
+                                   "WRITE_SIZE, kernel sources %s%s)"
+                                   % (args.config, kernel_source_hash(),
+                                      ", " + doc["stream"] if doc.get("stream") else ""))
+                elif rec and not same_stream:
+                    traffic_src = ("profiles/traffic_%s.json was collected on the other stream build (%s): "
+                                   "not quoted" % (args.config, doc.get("stream")))
+                elif rec:
+                    traffic_src = ("profiles/traffic_%s.json was collected on other kernel sources "
+                                   "(%s, now %s): not quoted" % (args.config, doc.get("kernel_source_hash"),
+                                                                 kernel_source_hash()))
+            roofline = {"bound": "hbm",
+                        "kernel": "%s (%s pass)" % (
+                            "vrx_spmm_lds<MODE %d, FORM %d>" % (dom == "cell", kinfo["cell_form"] if dom == "cell" else kinfo["var_form"])
+                            if kinfo["lds_" + dom]
+                            else "vrx_spmm<..,%d,fmt%d>" % (dom == "cell", kinfo["fmt_" + dom]), dom),
+                        "kernel_info": kinfo,
+                        "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": ach / HBM_PEAK_GBS, "traffic": traffic,
+                        "traffic_source": traffic_src,
+                        "algorithmic_bytes_per_launch": B[dom],
+                        "avg_launch_ms": avg,
+                        "per_iteration_ms": {"variant_pass": avg_v, "cell_pass": avg_c,
+                                             "dense_kernels": avg_d},
+                        "event_runs_ms": [{"variant_pass": r[0][_lib.KERN_VARIANT_PASS] / max(r[1][_lib.KERN_VARIANT_PASS], 1),
+                                           "cell_pass": r[0][_lib.KERN_CELL_PASS] / max(r[1][_lib.KERN_CELL_PASS], 1),
+                                           "dense_kernels": r[0][_lib.KERN_DENSE] / max(args.steps, 1)}
+                                          for r in prof_runs],
+                        "event_runs_note": "the K iterations three times with HIP events around every pass; "
+                                           "`avg_launch_ms` / `per_iteration_ms` are the run with the median pass time",
+                        "whole_iteration": {"algorithmic_bytes": B["total"],
+                                            "achieved_GBs": B["total"] / (wall_max / args.steps) / 1e9,
+                                            "frac": B["total"] / (wall_max / args.steps) / 1e9 / HBM_PEAK_GBS}}
         out = {
             "metric": "EM iterations/sec", "value": world * args.steps / wall_max,
             "unit": "EM iterations/s", "n_gpus": world, "steps": args.steps,
@@ -905,37 +1033,17 @@ def main():
                                   "build)" % binfo["balance_seconds"]) if binfo["balanced_cell"] else "default build",
                        "build_info": binfo,
                        "host_setup_s": {"generate": round(t_gen, 1), "upload+transpose": round(t_up, 2)}},
-            "roofline": {"bound": "hbm",
-                         "kernel": "%s (%s pass)" % (
-                             "vrx_spmm_lds<MODE %d, FORM %d>" % (dom == "cell", kinfo["cell_form"] if dom == "cell" else kinfo["var_form"])
-                             if kinfo["lds_" + dom]
-                             else "vrx_spmm<..,%d,fmt%d>" % (dom == "cell", kinfo["fmt_" + dom]), dom),
-                         "kernel_info": kinfo,
-                         "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": ach / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": B[dom],
-                         "avg_launch_ms": avg,
-                         "per_iteration_ms": {"variant_pass": avg_v, "cell_pass": avg_c,
-                                              "dense_kernels": avg_d},
-                         "event_runs_ms": [{"variant_pass": r[0][_lib.KERN_VARIANT_PASS] / max(r[1][_lib.KERN_VARIANT_PASS], 1),
-                                            "cell_pass": r[0][_lib.KERN_CELL_PASS] / max(r[1][_lib.KERN_CELL_PASS], 1),
-                                            "dense_kernels": r[0][_lib.KERN_DENSE] / max(args.steps, 1)}
-                                           for r in prof_runs],
-                         "event_runs_note": "the K iterations three times with HIP events around every pass; "
-                                            "`avg_launch_ms` / `per_iteration_ms` are the run with the median pass time",
-                         "whole_iteration": {"algorithmic_bytes": B["total"],
-                                             "achieved_GBs": B["total"] / (wall_max / args.steps) / 1e9,
-                                             "frac": B["total"] / (wall_max / args.steps) / 1e9 / HBM_PEAK_GBS}},
+            "roofline": roofline,
             "comm": comm_rec,
             "preceded_by": preceded_by,
             # what precedes the timed window differs with the flags, so `value` is
             # like-for-like only between lines that carry the same tag
-            "protocol": {"version": "r6", "warmup": args.warmup, "steps": args.steps,
+            # (a plain run -- no --full -- is its own protocol: the fit and the clock ramp, nothing else)
+            "protocol": {"version": "r6" if args.full else "plain", "warmup": args.warmup, "steps": args.steps,
                          "legs_before_timed_region": len(preceded_by),
-                         "flags": {"no_cpu": bool(args.no_cpu), "no_c4": bool(args.no_c4),
+                         "flags": {"full": bool(args.full), "no_cpu": bool(args.no_cpu), "no_c4": bool(args.no_c4),
                                    "no_side_legs": bool(args.no_side_legs)},
-                         "tag": "r6:w%d:k%d:%s" % (args.warmup, args.steps, "+".join(
+                         "tag": "%s:w%d:k%d:%s" % ("r6" if args.full else "plain", args.warmup, args.steps, "+".join(
                              x for x, on in (("c2c5", c2 is not None), ("c4", c4 is not None),
                                              ("parity", parity_gpu is not None)) if on) or "bare")},
             "cpu_baseline": cpu,
@@ -951,7 +1059,7 @@ def main():
                                     "min": round(min(repeats), 4), "median": round(float(np.median(repeats)), 4),
                                     "max": round(max(repeats), 4),
                                     "note": "run 0 is the timed run `value` comes from; runs 1-4 "
-                                            "repeat the same K iterations on this rank"},
+                                            "repeat the same K iterations on this rank"} if args.full else None,
         }
         if cpu:
             out["speedup_vs_cpu_1core"] = out["value"] / cpu["value"]

@@ -217,7 +217,7 @@ def test_bench_launches_its_own_ranks(va):
     lines = {}
     for n in (2, 1):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--config", "c2",
-                            "--steps", "20", "--warmup", "5", "--only-headline", "--comm", "tcp"],
+                            "--steps", "20", "--warmup", "5", "--full", "--only-headline", "--comm", "tcp"],
                            env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert p.returncode == 0, p.stderr[-2000:]
         out = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -251,7 +251,7 @@ def test_bench_line_names_its_communicator_rccl_world1(va):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "VIREO_COMM", "VIREO_DEVICE"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--steps", "20",
-                        "--warmup", "5", "--only-headline"], env=env, capture_output=True, text=True,
+                        "--warmup", "5", "--full", "--only-headline"], env=env, capture_output=True, text=True,
                        timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     out = [ln for ln in p.stdout.splitlines() if ln.strip()]

@@ -654,6 +654,46 @@ def test_bench_side_legs_cannot_cost_the_headline(capsys):
     assert B["cell"] == 12 * 99006675 + 4 * 50001 + 16 * 100000 * 16 + 8 * 50000 * 16
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+@pytest.mark.parametrize("config", ["small", "c2", "x1m"])
+def test_bench_inputs_are_the_generators(config):
+    """bench.py's faster sort of the inputs yields synth.donor_workload's arrays bit for bit"""
+    from vireo_amd import synth
+    got = _bench_module().donor_workload(*synth.CONFIGS[config], seed=0)
+    want = synth.donor_workload(*synth.CONFIGS[config], seed=0)
+    assert got["shape"] == want["shape"] and set(got) == set(want)
+    for k in ("colptr", "rowidx", "ad", "dp", "GT", "z"):
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
+
+
+def test_bench_dump_outputs_stays_within_its_limit(tmp_path):
+    """--dump-outputs: float64 .npy files; whole arrays while they fit, a seeded row sample beyond"""
+    bench = _bench_module()
+    rng = np.random.default_rng(3)
+    arrays = dict(elbo=rng.random(20), ID=rng.random((500, 16)), GT=rng.random((4000, 16, 3)))
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    limit = 600000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= limit
+    rows = np.load(tmp_path / "a" / "GT_rows.npy").astype(np.int64)
+    got = np.load(tmp_path / "a" / "GT.npy")
+    assert 0 < len(rows) < 4000 and np.all(np.diff(rows) > 0) and np.array_equal(got, arrays["GT"][rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "elbo.npy"), arrays["elbo"])
+    for f in (tmp_path / "a").iterdir():
+        assert np.array_equal(np.load(f), np.load(tmp_path / "b" / f.name))
+
+
 # ---------------------------------------------------------------- round 6: first contact with a multi-GPU node
 def test_free_port_reserves_the_three_rendezvous_ports():
     """MASTER_PORT, the unique-id port (+ 1) and the TcpComm harness's port (+ 2) are all free"""
