@@ -1212,13 +1212,10 @@ def test_balanced_slabs_small_problem_vs_oracle_and_default_build(va, monkeypatc
           % (kb["pad_variant"], kb["pad_cell"], kd["pad_variant"], kd["pad_cell"]))
     assert build(True).digest() == cb.digest()
     # the same stream by every route: the greedy on host threads (the specification; by default it runs on the
-    # device, and VIREO_BALANCE_CHECK=1 -- set above -- makes every build compare the two bit for bit), with
-    # the cell orientation's share beside the upload or inside build_tiled, the orientations one after the other
+    # device, and VIREO_BALANCE_CHECK=1 -- set above -- makes every build compare the two bit for bit), the
+    # orientations one after the other
     monkeypatch.setenv("VIREO_BALANCE_GREEDY", "host")
     assert build(True).digest() == cb.digest()
-    monkeypatch.setenv("VIREO_BALANCE_EARLY", "0")
-    assert build(True).digest() == cb.digest()
-    monkeypatch.delenv("VIREO_BALANCE_EARLY")
     monkeypatch.delenv("VIREO_BALANCE_GREEDY")
     monkeypatch.setenv("VIREO_BUILD_CONCURRENT", "0")
     assert build(True).digest() == cb.digest()
@@ -1320,3 +1317,38 @@ def test_balanced_slabs_with_rows_cut_into_pieces(va, monkeypatch):
         assert np.array_equal(a.ID_prob.argmax(1)[sure], ref.ID_prob.argmax(1)[sure])
         np.testing.assert_allclose(a.ELBO_, d.ELBO_, rtol=1e-10)
         np.testing.assert_allclose(a.ID_prob, d.ID_prob, rtol=1e-7, atol=1e-290)
+
+
+def test_guard_rejecting_one_balanced_orientation_leaves_no_stale_stream(va, monkeypatch):
+    """A balanced device build whose padding guard rejects exactly one orientation is rebuilt by the host
+    builder, unbalanced.  The orientation the guard kept must not keep its balanced-slab permutation: the
+    problem says neither stream is balanced, and a fit on it is bit for bit the fit on the same problem
+    built without balancing (a stale permutation would stage the wrong rows of every slab)."""
+    from vireo_amd.counts import DeviceCounts
+    from vireo_amd.engine import DeviceModel
+    from vireo_amd import _lib
+    AD, DP = O.synth_donor(2600, 2300, 6, 0.03, seed=3)
+    N, M = AD.shape
+    monkeypatch.setenv("VIREO_BUILD", "device")
+    monkeypatch.setenv("VIREO_LDS_SLAB_CELL", "32")    # short cell slabs: that orientation pads the most
+    monkeypatch.setenv("VIREO_LDS", "1")               # (the guard off: both orientations balance)
+    assert DeviceCounts(AD, DP, balance=True).build_info()["balanced_cell"]
+    monkeypatch.delenv("VIREO_LDS")                    # the guard on, and the streams for any size
+    monkeypatch.setenv("VIREO_LDS_MIN_NNZ", "0")
+    monkeypatch.setenv("VIREO_LDS_MIN_NNZ_VAR", "0")
+    monkeypatch.setenv("VIREO_LDS_MAX_PAD", "4")       # variant stream ~2.1 (balanced) / 3.0 words per entry
+    cb, cd = DeviceCounts(AD, DP, balance=True), DeviceCounts(AD, DP, balance=False)  # cell ~4.3 / 4.9
+    info = DeviceModel(cb, _lib.KIND_VIREO, 6).info()
+    assert info["lds_cell"] != info["lds_variant"], info   # the guard kept exactly one stream
+    ib = cb.build_info()
+    assert not ib["balanced_variant"] and not ib["balanced_cell"] and not ib["device_built"], ib
+
+    def fit(counts):
+        np.random.seed(4)
+        m = va.Vireo(n_var=N, n_cell=M, n_donor=6)
+        m.fit(counts, None, min_iter=5, max_iter=25, delay_fit_theta=2, verbose=False)
+        return m
+
+    a, d = fit(cb), fit(cd)
+    for name in ("ELBO_", "ID_prob", "GT_prob", "beta_mu", "beta_sum"):
+        assert np.array_equal(getattr(a, name), getattr(d, name)), name

@@ -24,6 +24,22 @@
 
 constexpr int VRX_BAL_LOAD_MAX = 127;
 
+// FORM 1 (AD / BD words, vrx_kernels.h): a count becomes entries of at most three significant bits each,
+// largest first (9 = 8 + 1, 45 = 40 + 5).  The next such entry of v != 0 (with v's sign), and the number of
+// entries of v -- what the balancing weighs an entry by, and what both stream builders emit.
+VRX_BAL_HD inline int64_t vrx_form1_chunk(int64_t v) {
+    const uint64_t mag = (uint64_t)(v < 0 ? -v : v);
+    const int len = 64 - __builtin_clzll(mag), sh = len > 3 ? len - 3 : 0;
+    const int64_t c = (int64_t)((mag >> sh) << sh);
+    return v < 0 ? -c : c;
+}
+
+VRX_BAL_HD inline int vrx_form1_words(int64_t v) {
+    int n = 0;
+    for (; v != 0; ++n) v -= vrx_form1_chunk(v);
+    return n;
+}
+
 struct VrxBalBlocks {
     int nb, bs;  // number of blocks, slabs per block (the last block: n_slab - (nb - 1) * bs)
 };

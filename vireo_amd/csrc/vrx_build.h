@@ -100,20 +100,6 @@ __global__ __launch_bounds__(VRX_BLOCK) void vrx_virt_fill(int64_t n_var, const 
     }
 }
 
-// number of FORM 1 entries a count becomes (build_tiled's push_value: top three significant bits
-// at a time)
-__device__ __forceinline__ int vrx_chunks(int64_t v) {
-    int n = 0;
-    while (v != 0) {
-        const uint64_t mag = (uint64_t)(v < 0 ? -v : v);
-        const int len = 64 - __clzll((long long)mag), sh = len > 3 ? len - 3 : 0;
-        const int64_t c = (int64_t)((mag >> sh) << sh);
-        v -= v < 0 ? -c : c;
-        ++n;
-    }
-    return n;
-}
-
 __device__ __forceinline__ int64_t vrx_lower_bound(const int32_t* a, int64_t lo, int64_t hi, int64_t key) {
     while (lo < hi) {
         const int64_t mid = (lo + hi) >> 1;
@@ -270,7 +256,7 @@ __global__ __launch_bounds__(VRX_BLOCK) void vrx_build_words(int64_t nnz, const 
     const int64_t e = (int64_t)blockIdx.x * VRX_BLOCK + threadIdx.x;
     if (e >= nnz) return;
     const int2 x = val[e];
-    words[e] = (uint8_t)min(vrx_chunks(x.x) + vrx_chunks((int64_t)x.y - x.x), 255);
+    words[e] = (uint8_t)min(vrx_form1_words(x.x) + vrx_form1_words((int64_t)x.y - x.x), 255);
 }
 
 __global__ __launch_bounds__(VRX_BLOCK) void vrx_build_relabel_gather(int64_t nnz, const uint64_t* __restrict__ keys,
@@ -307,7 +293,7 @@ __global__ __launch_bounds__(VRX_BLOCK) void vrx_bal_keys(int64_t nnz, int64_t n
             hi = mid - 1;
     }
     const int2 x = val[e];
-    const int w = min(vrx_chunks(x.x) + vrx_chunks((int64_t)x.y - x.x), 255);
+    const int w = min(vrx_form1_words(x.x) + vrx_form1_words((int64_t)x.y - x.x), 255);
     const int32_t tp = tpos_of_unit[lo];
     if (tp < 0 || w == 0) {
         keys[e] = (uint64_t)n_tile << cbits;  // (the tile behind the last one)
@@ -586,7 +572,7 @@ __global__ __launch_bounds__(VRX_BLOCK) void vrx_build_count(VrxTileArgs A, uint
                     ++n;
                 } else {
                     const int2 x = A.val[e];
-                    const int ca = vrx_chunks(x.x), cb = vrx_chunks((int64_t)x.y - x.x);
+                    const int ca = vrx_form1_words(x.x), cb = vrx_form1_words((int64_t)x.y - x.x);
                     if (A.form == 1) {
                         n += ca + cb;
 #ifdef VRX_CAP_PROBE

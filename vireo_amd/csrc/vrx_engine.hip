@@ -276,22 +276,27 @@ static int build_orient(Orient& o, int64_t n_rows, int64_t n_contract, const int
 // form 1 (cell pass): every (ad, dp) entry becomes single-valued entries of AD and of
 // BD = DP - AD (none for a zero, several for a value outside 15 signed bits), see FORM 1 in
 // vrx_kernels.h.  Word = value:15 | (2 * slab-local index + half) * 128.
-// `dev` != nullptr: the rows of this orientation live on the device (idx / val are then unused
-// host pointers) and the stream is built there (vrx_build.h); ptr is always the host copy.
 struct DevRows {
     const int64_t* ptr;
     const int32_t* idx;
     const int2* val;
 };
-// the same rows on the host, where the caller still has them (the cell orientation IS the CSC input)
-struct HostCounts {
+// The rows a stream is built from: the row pointer on the host, the entries on the host (idx / val: the host
+// builder) or on the device (dev.ptr != nullptr: the device builder, vrx_build.h).  virt: the VIRTUAL rows of
+// the variant pass (vrx_build.h).
+struct TileRows {
+    const int64_t* ptr;
     const int32_t* idx;
-    const int32_t *ad, *dp;
+    const int2* val;
+    DevRows dev;
+    int64_t n_rows, n_contract, nnz;
+    bool virt;
 };
-// ... or what the balancing needs of them, already brought back from the device by the caller
-struct HostWords {
-    const int32_t* idx;
-    const uint8_t* words;
+// The stream asked for: rows per wave, slab height, word form (0 pairs, 1 AD / BD words, 2 AD / BD phases),
+// pass (0 variant, 1 cell), the padding guard (VIREO_LDS_MAX_PAD), balanced slabs (TiledStream::perm).
+struct TileShape {
+    int RW, slab_rows, form, mode;
+    bool guard, balance;
 };
 
 // Work list of an LDS-resident pass (TiledStream::items).  The (tile, slab) visits, tile-major,
@@ -428,75 +433,69 @@ static void derive_virtual_rows(int64_t n_var, const int64_t* rptr, const int32_
     });
 }
 
+// smallest b >= 1 with 2^b >= n: the key bits of a radix sort over n values
+static int bits_for(int64_t n) {
+    int b = 1;
+    while (((int64_t)1 << b) < n) ++b;
+    return b;
+}
+
+// VIREO_BUILD_TIMING=1: where a build spends its wall clock, lap by lap (a lap waits for the stream first)
+struct LapTimer {
+    hipStream_t s;
+    std::string label;
+    int width;
+    bool on = env_int("VIREO_BUILD_TIMING", 0) != 0;
+    double begin = now(), last = begin;
+    static double now() {
+        return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    }
+    void operator()(const char* what) {
+        if (!on) return;
+        (void)hipStreamSynchronize(s);
+        const double t1 = now();
+        fprintf(stderr, "[vrx build] %s %-*s %.3f s\n", label.c_str(), width, what, t1 - last);
+        last = t1;
+    }
+};
+
 // ---- balanced slabs (r6; TiledStream::perm) -------------------------------------------------------
 // The padding of a round is the maximum over its 16 rows of their words in ONE slab; which contracted
 // rows share a slab is free per tile.  Greedy, per tile: the contracted rows ("columns" of the tile's
 // sub-matrix) most-covered first, each to the slab -- among those with room -- where the sum of the
 // present loads of the rows it touches is smallest (ties: the lowest slab); columns without an entry in
 // the tile fill what is left.  Counted on the c3 matrix: 1.62 -> 1.17 executed slots per word.
-// Deterministic (the result is part of the stream both builders must agree on).
-static inline int words_of_count(int64_t v) {  // FORM 1 words of one count (push_value / vrx_chunks)
-    int n = 0;
-    while (v != 0) {
-        const uint64_t mag = (uint64_t)(v < 0 ? -v : v);
-        const int len = 64 - __builtin_clzll(mag), sh = std::max(0, len - 3);
-        const int64_t c = (int64_t)((mag >> sh) << sh);
-        v -= v < 0 ? -c : c;
-        ++n;
-    }
-    return n;
-}
+// Deterministic (the result is part of the stream both greedy routes must agree on).
 
 // (the greedy itself: vrx_host.cpp, vrx_balance_tile -- host only, built with AVX2 clones of its inner loops)
 void vrx_balance_tile(const int32_t* rows, int64_t n_rows_tile, const int64_t* ptr, const int32_t* idx,
                       const uint8_t* words, int64_t n_contract, int n_slab, int slab_rows, int max_block,
                       int32_t* posmap, int32_t* perm);
 
-// The host half of a tiled stream that needs nothing but the row pointer: the pieces long rows are cut
-// into, the tile / slab geometry, and which piece sits at which tile position.  A function of its own so
-// that device_build can run it -- and the balanced-slab greedy behind it -- on a helper thread while the
-// counts are still being uploaded and transposed.
+// Stage (a), the host half of a tiled stream that needs nothing but the row pointer: the pieces long rows are
+// cut into, the tile / slab geometry, and which piece sits at which tile position.
 struct TileLayout {
-    // what it was computed for
-    const int64_t* ptr = nullptr;
-    int64_t n_rows = -1, n_contract = -1, nnz = -1;
-    int RW = 0, slab_rows_in = 0, form = -1, n_cu = -1;
-    // the layout
     std::vector<int32_t> vptr, vrow_row, split_rows, rowmap;
     int64_t n_vrows = 0;
     bool split = false;
     int n_tile = 0, n_slab = 0, slab_rows = 0;
-    // balanced slabs, when the greedy already ran (cell orientation, from the caller's arrays)
-    bool greedy_done = false;
-    std::vector<int32_t> posmap, perm, tile_of_row;
-    double greedy_seconds = 0.0;
-    bool matches(const int64_t* p, int64_t nr, int64_t nc, int64_t nz, int rw, int sr, int f, int cu) const {
-        return ptr == p && n_rows == nr && n_contract == nc && nnz == nz && RW == rw && slab_rows_in == sr &&
-               form == f && n_cu == cu;
-    }
 };
 
-static int tile_layout(TileLayout& L, const int64_t* ptr, int64_t o_n_rows, int64_t o_n_contract, int64_t o_nnz,
-                       int RW, int slab_rows, int form, int n_cu) {
+static int tile_layout(TileLayout& L, const TileRows& R, const TileShape& S, int n_cu) {
     constexpr int G = 64 / VRX_LDS_LPE;
-    L.ptr = ptr;
-    L.n_rows = o_n_rows;
-    L.n_contract = o_n_contract;
-    L.nnz = o_nnz;
-    L.RW = RW;
-    L.slab_rows_in = slab_rows;
-    L.form = form;
-    L.n_cu = n_cu;
+    const int64_t* ptr = R.ptr;
+    const int RW = S.RW;
+    int slab_rows = S.slab_rows;
     L.slab_rows = slab_rows;
-    L.n_slab = (int)((o_n_contract + slab_rows - 1) / slab_rows);
+    L.n_slab = (int)((R.n_contract + slab_rows - 1) / slab_rows);
     // ---- pieces ------------------------------------------------------------------------
-    const double mean = (double)o_nnz / (double)std::max<int64_t>(o_n_rows, 1);
+    const double mean = (double)R.nnz / (double)std::max<int64_t>(R.n_rows, 1);
     const int64_t cap = std::max<int64_t>(
         64, (int64_t)(mean * (double)env_int("VIREO_LDS_SPLIT_X10", 20) / 10.0 + 0.5));
     const bool reorder = env_int("VIREO_LDS_SORT", 1) != 0;
     std::vector<int32_t>& vptr = L.vptr;
-    vptr.assign((size_t)o_n_rows + 1, 0);
-    for (int64_t r = 0; r < o_n_rows; ++r) {
+    vptr.assign((size_t)R.n_rows + 1, 0);
+    for (int64_t r = 0; r < R.n_rows; ++r) {
         const int64_t len = ptr[r + 1] - ptr[r];
         const int64_t P = reorder ? std::max<int64_t>(1, (len + cap - 1) / cap) : 1;
         if ((int64_t)vptr[(size_t)r] + P >= INT32_MAX) {
@@ -505,16 +504,16 @@ static int tile_layout(TileLayout& L, const int64_t* ptr, int64_t o_n_rows, int6
         }
         vptr[(size_t)r + 1] = vptr[(size_t)r] + (int32_t)P;
     }
-    const int64_t n_vrows = vptr[(size_t)o_n_rows];
+    const int64_t n_vrows = vptr[(size_t)R.n_rows];
     L.n_vrows = n_vrows;
-    L.split = n_vrows != o_n_rows;
+    L.split = n_vrows != R.n_rows;
     std::vector<int32_t>& split_rows = L.split_rows;  // rows cut into several pieces: folded by vrx_fold_split
     split_rows.clear();
-    for (int64_t r = 0; r < o_n_rows; ++r)
+    for (int64_t r = 0; r < R.n_rows; ++r)
         if (vptr[(size_t)r + 1] - vptr[(size_t)r] > 1) split_rows.push_back((int32_t)r);
     std::vector<int32_t>& vrow_row = L.vrow_row;
     vrow_row.assign((size_t)n_vrows, 0);
-    for (int64_t r = 0; r < o_n_rows; ++r)
+    for (int64_t r = 0; r < R.n_rows; ++r)
         for (int32_t v = vptr[(size_t)r]; v < vptr[(size_t)r + 1]; ++v) vrow_row[(size_t)v] = (int32_t)r;
     const int64_t tile_rows = VRX_LDS_WAVES * (int64_t)RW;
     L.n_tile = (int)((n_vrows + tile_rows - 1) / tile_rows);
@@ -534,10 +533,10 @@ static int tile_layout(TileLayout& L, const int64_t* ptr, int64_t o_n_rows, int6
         if (L.n_slab <= 2) spread_tiles();
         if ((int64_t)L.n_tile * L.n_slab < n_cu) {
             const int64_t want = (n_cu + L.n_tile - 1) / L.n_tile;
-            const int64_t sr = std::min<int64_t>(slab_rows, std::max<int64_t>(64, ((o_n_contract + want - 1) / want + 15) / 16 * 16));
+            const int64_t sr = std::min<int64_t>(slab_rows, std::max<int64_t>(64, ((R.n_contract + want - 1) / want + 15) / 16 * 16));
             slab_rows = (int)sr;
             L.slab_rows = slab_rows;
-            L.n_slab = (int)((o_n_contract + slab_rows - 1) / slab_rows);
+            L.n_slab = (int)((R.n_contract + slab_rows - 1) / slab_rows);
             if ((int64_t)L.n_tile * L.n_slab < n_cu) spread_tiles();
         }
     }
@@ -545,43 +544,85 @@ static int tile_layout(TileLayout& L, const int64_t* ptr, int64_t o_n_rows, int6
     // ---- tile position -> piece (-1 = padding position) ---------------------------------
     std::vector<int32_t>& rowmap = L.rowmap;
     rowmap.assign((size_t)(n_wave * RW), -1);
-    {
-        std::vector<int32_t> order((size_t)n_vrows);
-        for (int64_t v = 0; v < n_vrows; ++v) order[(size_t)v] = (int32_t)v;
-        if (reorder) {
-            auto piece_len = [&](int32_t v) {
-                const int32_t r = vrow_row[(size_t)v];
-                return (ptr[r + 1] - ptr[r]) / (vptr[(size_t)r + 1] - vptr[(size_t)r]);
-            };
-            std::stable_sort(order.begin(), order.end(),
-                             [&](int32_t a, int32_t b) { return piece_len(a) > piece_len(b); });
-        }
-        const int64_t n_unit = (n_vrows + G - 1) / G;
-        for (int64_t u = 0; u < n_unit; ++u) {
-            const int64_t j = u / n_wave, i = u % n_wave;  // stratum j -> round j of the wave
-            const int64_t w = reorder && (j & 1) ? n_wave - 1 - i : i;
-            for (int g = 0; g < G && u * G + g < n_vrows; ++g)
-                rowmap[(size_t)(w * RW + j * G + g)] = order[(size_t)(u * G + g)];
-        }
+    std::vector<int32_t> order((size_t)n_vrows);
+    for (int64_t v = 0; v < n_vrows; ++v) order[(size_t)v] = (int32_t)v;
+    if (reorder) {
+        auto piece_len = [&](int32_t v) {
+            const int32_t r = vrow_row[(size_t)v];
+            return (ptr[r + 1] - ptr[r]) / (vptr[(size_t)r + 1] - vptr[(size_t)r]);
+        };
+        std::stable_sort(order.begin(), order.end(),
+                         [&](int32_t a, int32_t b) { return piece_len(a) > piece_len(b); });
     }
-    L.slab_rows = slab_rows;
+    const int64_t n_unit = (n_vrows + G - 1) / G;
+    for (int64_t u = 0; u < n_unit; ++u) {
+        const int64_t j = u / n_wave, i = u % n_wave;  // stratum j -> round j of the wave
+        const int64_t w = reorder && (j & 1) ? n_wave - 1 - i : i;
+        for (int g = 0; g < G && u * G + g < n_vrows; ++g)
+            rowmap[(size_t)(w * RW + j * G + g)] = order[(size_t)(u * G + g)];
+    }
     return VRX_OK;
 }
 
-// The greedy of every tile (vrx_balance_tile), tiles in parallel: the tile of every unit (row, or piece where
-// rows are cut), posmap / perm per tile.  `unit_ptr`, `idx`, `words`: the units' entries on the host.
-static void greedy_tiles(const TileLayout& L, bool pieces, const int64_t* unit_ptr, const int32_t* idx,
-                         const uint8_t* words, int64_t n_unit_rows, std::vector<int32_t>& posmap,
-                         std::vector<int32_t>& perm, std::vector<int32_t>& tile_of_row) {
-    const int64_t tile_pos = (int64_t)VRX_LDS_WAVES * L.RW, slots = (int64_t)L.n_slab * L.slab_rows;
-    const int64_t n_contract = L.n_contract;
+// The word geometry of a stream, as the device builder's kernels take it; the host walk reads the same
+// fields (the device pointers are set by the device builder).
+static VrxTileArgs tile_args(const TileRows& R, const TileShape& S, const TileLayout& L) {
+    constexpr int G = 64 / VRX_LDS_LPE;
+    VrxTileArgs A{};
+    A.ptr = R.dev.ptr;
+    A.idx = R.dev.idx;
+    A.val = R.dev.val;
+    A.RW = S.RW;
+    A.NR = S.RW / G;
+    A.G = G;
+    A.U = VRX_LDS_U;
+    A.n_slab = L.n_slab;
+    A.slab_rows = L.slab_rows;
+    A.form = S.form;
+    A.PH = S.form == 2 ? 2 : 1;  // phases of a round (form 2: AD entries, then BD entries)
+    // the entry bit that selects the LDS bank half of a 128-B dense row: half (form 1), parity
+    // of the slab-local index (variant pass); none for the 256-B rows of the (ad, dp) cell pass
+    A.bit_shift = S.form != 0 ? 7 : (S.mode == 0 ? 22 : -1);
+    A.pairing = env_int("VIREO_LDS_PARITY", 1) != 0 ? 1 : 0;
+    A.xor_partner = 24 / VRX_LDS_LPE;
+    // form 1 words carry the LDS address of their half row: the slab starts behind the rings
+    A.f1_base = (uint32_t)VRX_LDS_WAVES * VRX_RING * 4u;
+    A.pad_word = S.form != 0 ? A.f1_base : 0u;
+    A.n_wave = (int64_t)L.n_tile * VRX_LDS_WAVES;
+#ifdef VRX_CAP_PROBE
+    A.cap = R.virt ? env_int("VIREO_CAP_PROBE_VAR", 0) : env_int("VIREO_CAP_PROBE_CELL", 0);
+#endif
+    return A;
+}
+
+// Balanced slabs apply to AD/BD words (form 1) of several slabs.  The kernel stages a balanced slab through the
+// gather of its precise instances only, and its perm path hard-codes the lane mapping of 16 waves loading at
+// most 8 registers each (lane 32 + 4 i + q <- slab-local row 4 * wave + 64 i + q).
+static_assert(VRX_LDS_WAVES == 16 && VRX_LDS_PF <= 8,
+              "balanced slabs: the perm path of vrx_spmm_lds assumes 16 waves and at most 8 prefetch registers");
+static bool balance_applies(const TileRows& R, const TileShape& S, const TileLayout& L) {
+    return VRX_LDS_PRECISE && S.balance && S.form == 1 && L.n_slab > 1 && R.n_contract < ((int64_t)1 << 24) &&
+           L.n_vrows < ((int64_t)1 << 31) && (!L.split || env_int("VIREO_BALANCE_SPLIT", 1) != 0);
+}
+
+// The rows the greedy and the relabel work on: the stream's rows, or -- rows cut into pieces (heavy-tailed
+// data) -- the PIECES, whose entries are copied out as rows of their own (entry k of a row -> piece k % P), so
+// that every unit belongs to exactly one tile and is relabelled by that tile's permutation.
+struct BalanceUnits {
+    const int64_t* ptr;  // row pointer on the host
+    DevRows dev;         // the same rows on the device
+    int64_t n, nnz, n_contract;
+    std::vector<int32_t> tile, tpos;  // tile and tile position of every unit (-1: none)
+};
+
+// The greedy of every tile (vrx_balance_tile) on host threads, tiles in parallel: posmap / perm per tile.
+static void greedy_tiles(const TileLayout& L, int RW, bool pieces, const BalanceUnits& U, const int32_t* idx,
+                         const uint8_t* words, std::vector<int32_t>& posmap, std::vector<int32_t>& perm) {
+    const int64_t tile_pos = (int64_t)VRX_LDS_WAVES * RW, slots = (int64_t)L.n_slab * L.slab_rows;
     const int max_block = env_int("VIREO_BALANCE_BLOCK", 64);
-    posmap.resize((size_t)(L.n_tile * n_contract));
+    posmap.resize((size_t)(L.n_tile * U.n_contract));
     perm.resize((size_t)(L.n_tile * slots));
-    tile_of_row.assign((size_t)n_unit_rows, -1);
     auto unit_of = [&](int32_t v) { return pieces ? v : L.vrow_row[(size_t)v]; };
-    for (int64_t pos = 0; pos < (int64_t)L.n_tile * tile_pos; ++pos)
-        if (L.rowmap[(size_t)pos] >= 0) tile_of_row[(size_t)unit_of(L.rowmap[(size_t)pos])] = (int32_t)(pos / tile_pos);
     std::atomic<int64_t> next_tile{0};  // (tiles cost about the same: first come, first served)
     parallel_chunks(std::min<int64_t>(L.n_tile, balance_threads()), balance_threads(), [&](int64_t, int64_t, int) {
         std::vector<int32_t> rows;
@@ -589,550 +630,386 @@ static void greedy_tiles(const TileLayout& L, bool pieces, const int64_t* unit_p
             rows.clear();
             for (int64_t pos = tl * tile_pos; pos < (tl + 1) * tile_pos; ++pos)
                 if (L.rowmap[(size_t)pos] >= 0) rows.push_back(unit_of(L.rowmap[(size_t)pos]));
-            vrx_balance_tile(rows.data(), (int64_t)rows.size(), unit_ptr, idx, words, n_contract, L.n_slab,
-                             L.slab_rows, max_block, posmap.data() + tl * n_contract, perm.data() + tl * slots);
+            vrx_balance_tile(rows.data(), (int64_t)rows.size(), U.ptr, idx, words, U.n_contract, L.n_slab,
+                             L.slab_rows, max_block, posmap.data() + tl * U.n_contract, perm.data() + tl * slots);
         }
     });
 }
 
-// one byte per entry: the FORM 1 words of the caller's (ad, dp), on all host threads; false if an index is
-// outside [0, n_contract) (the caller's arrays may not have been validated yet)
-static bool host_words(const HostCounts& hc, int64_t nnz, int64_t n_contract, std::vector<uint8_t>& words) {
-    words.resize((size_t)nnz);
-    std::atomic<bool> bad{false};
-    parallel_chunks(nnz, host_threads(), [&](int64_t e0, int64_t e1, int) {
-        bool b = false;
-        for (int64_t e = e0; e < e1; ++e) {
-            b |= hc.idx[e] < 0 || hc.idx[e] >= n_contract;
-            words[(size_t)e] = (uint8_t)std::min(words_of_count(hc.ad[e]) + words_of_count((int64_t)hc.dp[e] - hc.ad[e]), 255);
-        }
-        if (b) bad = true;
-    });
-    return !bad;
+// The greedy on the device (vrx_build.h, vrx_balance_greedy): no entry leaves the GPU.  Prepared by two radix
+// sorts and a scan whose key / value buffers (k_*, v_*) the relabel uses afterwards.  *declined: a column deeper
+// than 4095 tile rows or a block without room -- the host greedy takes over.
+static int greedy_device(const BalanceUnits& U, const TileLayout& L, int RW, VrxBalBlocks blocks, DevBuf<uint64_t>& k_in,
+                         DevBuf<uint64_t>& k_out, DevBuf<uint32_t>& v_in, DevBuf<uint32_t>& v_out,
+                         DevBuf<int32_t>& d_posmap, DevBuf<int32_t>& perm, hipStream_t s, LapTimer& lap, bool* declined) {
+    const int64_t tile_pos = (int64_t)VRX_LDS_WAVES * RW, slots = (int64_t)L.n_slab * L.slab_rows;
+    const int64_t nnz = U.nnz, n_contract = U.n_contract;
+    const int64_t n_cols_all = (int64_t)L.n_tile * n_contract, n_groups = (int64_t)L.n_tile * blocks.nb;
+    DevBuf<int32_t> d_tpos, d_flags;
+    DevBuf<uint64_t> ok_in, ok_out;
+    DevBuf<uint32_t> d_cptr, d_deg, d_ostart, d_ovals;
+    DevBuf<int64_t> d_seg;
+    DevBuf<char> tmp;
+    const int cbits = bits_for(n_contract), tbits = bits_for((int64_t)L.n_tile + 1), gbits = bits_for(n_groups);
+    const unsigned nbe = (unsigned)((nnz + VRX_BLOCK - 1) / VRX_BLOCK);
+    const unsigned nbc = (unsigned)((n_cols_all + 1 + VRX_BLOCK - 1) / VRX_BLOCK);
+    VRX_HIP(d_tpos.upload(U.tpos.data(), U.tpos.size(), s));
+    const int32_t zero2[2] = {0, 0};
+    VRX_HIP(d_flags.upload(zero2, 2, s));
+    vrx_bal_keys<<<nbe, VRX_BLOCK, 0, s>>>(nnz, U.n, U.dev.ptr, U.dev.idx, U.dev.val, d_tpos.p, (int)tile_pos,
+                                           L.n_tile, cbits, k_in.p, v_in.p);
+    VRX_HIP(hipGetLastError());
+    size_t tmp_bytes = 0, tmp2 = 0, tmp3 = 0;
+    VRX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, k_in.p, k_out.p, v_in.p, v_out.p,
+                                               (size_t)nnz, 0, cbits + tbits, s));
+    VRX_HIP(ok_in.alloc((size_t)n_cols_all));
+    VRX_HIP(ok_out.alloc((size_t)n_cols_all));
+    VRX_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp2, ok_in.p, ok_out.p, (size_t)n_cols_all, 0,
+                                              cbits + 12 + gbits, s));
+    VRX_HIP(d_deg.alloc((size_t)n_cols_all));
+    VRX_HIP(d_ostart.alloc((size_t)n_cols_all));
+    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp3, d_deg.p, d_ostart.p, (size_t)n_cols_all, s));
+    VRX_HIP(tmp.alloc(std::max(tmp_bytes, std::max(tmp2, tmp3))));
+    VRX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, k_in.p, k_out.p, v_in.p, v_out.p,
+                                               (size_t)nnz, 0, cbits + tbits, s));
+    VRX_HIP(d_cptr.alloc((size_t)n_cols_all + 1));
+    vrx_bal_cptr<<<nbc, VRX_BLOCK, 0, s>>>(n_cols_all, n_contract, nnz, k_out.p, cbits, d_cptr.p);
+    VRX_HIP(hipGetLastError());
+    vrx_bal_order_keys<<<nbc, VRX_BLOCK, 0, s>>>(n_cols_all, n_contract, d_cptr.p, L.slab_rows, blocks.bs,
+                                                 blocks.nb, cbits, ok_in.p, d_flags.p);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.p, tmp2, ok_in.p, ok_out.p, (size_t)n_cols_all, 0,
+                                              cbits + 12 + gbits, s));
+    VRX_HIP(d_seg.alloc((size_t)n_groups + 1));
+    vrx_bal_groups<<<(unsigned)((n_groups + 1 + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
+        n_groups, n_cols_all, ok_out.p, 12 + cbits, d_seg.p);
+    VRX_HIP(hipGetLastError());
+    vrx_bal_degrees<<<nbc, VRX_BLOCK, 0, s>>>(n_cols_all, ok_out.p, cbits, d_deg.p);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp3, d_deg.p, d_ostart.p, (size_t)n_cols_all, s));
+    uint32_t n_stream = 0;  // the entries that count = first entry of the column behind the last one
+    VRX_HIP(hipMemcpyAsync(&n_stream, d_cptr.p + n_cols_all, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VRX_HIP(d_ovals.alloc((size_t)nnz));
+    vrx_bal_stream<<<nbc, VRX_BLOCK, 0, s>>>(n_cols_all, n_contract, ok_out.p, cbits, blocks.nb, d_cptr.p,
+                                             v_out.p, d_ostart.p, d_ovals.p);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(d_posmap.alloc((size_t)n_cols_all));
+    VRX_HIP(perm.alloc((size_t)(L.n_tile * slots)));
+    VRX_HIP(hipMemsetAsync(perm.p, 0, (size_t)(L.n_tile * slots) * sizeof(int32_t), s));
+    VRX_HIP(hipStreamSynchronize(s));  // (n_stream)
+    const size_t lds = (size_t)(tile_pos + 1) * 64 + 2 * VRX_BAL_BATCH * sizeof(uint32_t);
+    VRX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(vrx_balance_greedy),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    vrx_balance_greedy<<<(unsigned)n_groups, 64, lds, s>>>(ok_out.p, d_seg.p, d_ostart.p, d_ovals.p,
+                                                          (int64_t)n_stream, n_contract, cbits, L.n_slab,
+                                                          L.slab_rows, blocks.bs, blocks.nb, (int)tile_pos,
+                                                          d_posmap.p, perm.p, d_flags.p + 1);
+    VRX_HIP(hipGetLastError());
+    int32_t flags[2] = {0, 0};
+    VRX_HIP(hipMemcpyAsync(flags, d_flags.p, sizeof flags, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    lap("greedy on the device");
+    *declined = flags[0] || flags[1];
+    if (*declined && lap.on)
+        fprintf(stderr, "[vrx build] balanced slabs: device greedy declined (%d, %d)\n", flags[0], flags[1]);
+    return VRX_OK;
 }
 
-// may this layout be balanced on the host from the caller's arrays alone?  (the same conditions build_tiled
-// applies; pieces need the device's copy of the rows)
-static bool host_balance_applies(const TileLayout& L) {
-    return L.form == 1 && L.n_slab > 1 && L.n_contract < ((int64_t)1 << 24) && L.n_vrows < ((int64_t)1 << 31) && !L.split;
-}
-
-static int build_tiled(Orient& o, const int64_t* ptr, const int32_t* idx, const int2* val,
-                       int RW, int slab_rows, bool guard, int form, int mode, hipStream_t s,
-                       int n_cu, const DevRows* dev = nullptr, int64_t virt_rows = -1,
-                       int64_t virt_contract = -1, int64_t virt_nnz = -1, const HostCounts* hc = nullptr,
-                       const HostWords* hw = nullptr, TileLayout* pre = nullptr) {
-    constexpr int G = 64 / VRX_LDS_LPE, U = VRX_LDS_U;
-    const int NR = RW / G;
-    TiledStream& t = o.tiled;
-    // (virt_rows >= 0: ptr / idx / val are the VIRTUAL rows of the variant pass, vrx_build.h)
-    t.virt = virt_rows >= 0;
-    const int64_t o_n_rows = t.virt ? virt_rows : o.n_rows;
-    const int64_t o_n_contract = t.virt ? virt_contract : o.n_contract;
-    const int64_t o_nnz = t.virt ? virt_nnz : o.nnz;
-    t.n_contract = o_n_contract;
-    t.form = form;
-    t.rw = RW;
-    t.slab_rows = slab_rows;
-    t.n_slab = (int)((o_n_contract + slab_rows - 1) / slab_rows);
-    // ---- pieces, tile / slab geometry, tile position -> piece (tile_layout) ---------------------
-    TileLayout own_layout;
-    const bool have_pre = pre && pre->matches(ptr, o_n_rows, o_n_contract, o_nnz, RW, slab_rows, form, n_cu);
-    TileLayout& L = have_pre ? *pre : own_layout;
-    if (!have_pre) {
-        const int rc_layout = tile_layout(L, ptr, o_n_rows, o_n_contract, o_nnz, RW, slab_rows, form, n_cu);
-        if (rc_layout) return rc_layout;
-    }
-    std::vector<int32_t>&vptr = L.vptr, &vrow_row = L.vrow_row, &split_rows = L.split_rows, &rowmap = L.rowmap;
-    const int64_t n_vrows = L.n_vrows;
-    t.n_vrows = n_vrows;
-    t.split = L.split;
-    t.n_split = (int64_t)split_rows.size();
-    t.n_tile = L.n_tile;
-    slab_rows = L.slab_rows;
-    t.slab_rows = slab_rows;
-    t.n_slab = L.n_slab;
-    const int64_t n_wave = (int64_t)t.n_tile * VRX_LDS_WAVES;
-    const int PH = form == 2 ? 2 : 1;  // phases of a round (form 2: AD entries, then BD entries)
-    const int64_t per_wave = (int64_t)t.n_slab * NR * PH + 1;
-    std::vector<int64_t> wave_start((size_t)n_wave), wave_len((size_t)n_wave, 0);
-    std::vector<int32_t> bnd((size_t)(n_wave * per_wave));
-    std::atomic<bool> too_long{false};
-    // One wave's stream: walks its RW pieces slab by slab, records the (slab, round) offsets
-    // and appends the words to the wave's own buffer.  Waves are independent.
-    const bool parity_order = env_int("VIREO_LDS_PARITY", 1) != 0;
-    // the entry bit that selects the LDS bank half of a 128-B dense row: half (form 1), parity
-    // of the slab-local index (variant pass); none for the 256-B rows of the (ad, dp) cell pass
-    const int bit_shift = form != 0 ? 7 : (mode == 0 ? 22 : -1);
-    // form 1 words carry the LDS address of their half row: the slab starts behind the rings
-    const uint32_t f1_base = (uint32_t)VRX_LDS_WAVES * VRX_RING * 4u, pad_word = form != 0 ? f1_base : 0u;
-    // FORM 1 value field: the top 14 bits of the IEEE double (sign, exponent, 2 mantissa bits).
-    // A value with more than three significant bits becomes several entries (9 = 8 + 1, ...).
-    auto push_value = [](std::vector<uint32_t>& out, int64_t v, uint32_t off) {
-        while (v != 0) {
-            const uint64_t mag = (uint64_t)(v < 0 ? -v : v);
-            const int len = 64 - __builtin_clzll(mag), sh = std::max(0, len - 3);
-            const int64_t c = (int64_t)((mag >> sh) << sh) * (v < 0 ? -1 : 1);
-            const double d = (double)c;
-            uint64_t bits;
-            std::memcpy(&bits, &d, 8);
-            out.push_back((uint32_t)(bits >> 50) << 18 | off);
-            v -= c;
-        }
-    };
-    if (dev) {  // ---- the stream is built on the device --------------------------------------
-        DevBuf<int32_t> d_rowmap, d_vptr, d_vrow, rlen, d_too;
-        DevBuf<uint32_t> seg_lo, seg_hi;  // entry offsets (< 2^32: device_build's limit)
-        VRX_REQUIRE(o_nnz < (int64_t)UINT32_MAX, "tiled stream: more than 2^32 - 1 entries");
-        VRX_HIP(d_rowmap.upload(rowmap.data(), rowmap.size(), s));
-        VRX_HIP(d_vptr.upload(vptr.data(), vptr.size(), s));
-        VRX_HIP(d_vrow.upload(vrow_row.data(), vrow_row.size(), s));
-        VrxTileArgs A;
-        A.ptr = dev->ptr;
-        A.idx = dev->idx;
-        A.val = dev->val;
-        A.rowmap = d_rowmap.p;
-        A.vptr = d_vptr.p;
-        A.vrow_row = d_vrow.p;
-        A.RW = RW;
-        A.NR = NR;
-        A.G = G;
-        A.U = U;
-        A.n_slab = t.n_slab;
-        A.slab_rows = slab_rows;
-        A.form = form;
-        A.PH = PH;
-        A.bit_shift = bit_shift;
-        A.pairing = parity_order ? 1 : 0;
-        A.xor_partner = 24 / VRX_LDS_LPE;
-        A.f1_base = f1_base;
-        A.pad_word = pad_word;
-        A.n_wave = n_wave;
-#ifdef VRX_CAP_PROBE
-        A.cap = t.virt ? env_int("VIREO_CAP_PROBE_VAR", 0) : env_int("VIREO_CAP_PROBE_CELL", 0);
-#endif
-        // ---- balanced slabs: per-tile permutation of the contracted rows, entries relabelled + re-sorted
-        DevBuf<int32_t> d_idx2, d_tile_of_row, d_posmap;
-        DevBuf<int2> d_val2;
-        t.balanced = false;
-        t.perm.release();
-        DevBuf<int64_t> d_pptr;       // (split rows: the pieces as rows of their own, see vrx_build_pieces)
-        DevBuf<int32_t> d_pidx, d_iota;
-        DevBuf<int2> d_pval;
-        if (form == 1 && t.want_balance && t.n_slab > 1 && o_n_contract < ((int64_t)1 << 24) &&
-            n_vrows < ((int64_t)1 << 31) && (!t.split || env_int("VIREO_BALANCE_SPLIT", 1) != 0)) {
-            const int64_t tile_pos = (int64_t)VRX_LDS_WAVES * RW, slots = (int64_t)t.n_slab * slab_rows;
-            const bool timing = env_int("VIREO_BUILD_TIMING", 0) != 0;
-            auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-            double tm0 = now();
-            const double tm_begin = tm0;
-            auto lap = [&](const char* what) {
-                if (!timing) return;
-                (void)hipStreamSynchronize(s);
-                const double t1 = now();
-                fprintf(stderr, "[vrx build] balanced slabs (mode %d): %-28s %.3f s\n", mode, what, t1 - tm0);
-                tm0 = t1;
-            };
-            // what the greedy reads: every entry's contracted index and its FORM 1 word count.  The cell
-            // orientation's rows are the caller's CSC arrays; otherwise the indices and one byte per entry
-            // (vrx_build_words) come back from the device
-            std::vector<int32_t> h_idx;
-            std::vector<uint8_t> h_words;
-            // Rows cut into pieces (heavy-tailed data): the unit of everything below is the PIECE -- its
-            // entries are copied out as a row of their own (entry k of the row -> piece k % P), so that
-            // every unit belongs to exactly one tile and is relabelled by that tile's permutation
-            const bool pieces = t.split;
-            std::vector<int64_t> pptr;
-            const int64_t* u_ptr = ptr;         // row pointer of the units (host) ...
-            const int64_t* du_ptr = dev->ptr;   // ... and on the device, with their entries
-            const int32_t* du_idx = dev->idx;
-            const int2* du_val = dev->val;
-            const int64_t n_unit_rows = pieces ? n_vrows : o_n_rows;
-            if (pieces) {
-                pptr.assign((size_t)n_vrows + 1, 0);
-                for (int64_t r = 0; r < o_n_rows; ++r) {
-                    const int64_t L = ptr[r + 1] - ptr[r];
-                    const int32_t v0 = vptr[(size_t)r], P = vptr[(size_t)r + 1] - v0;
-                    for (int32_t q = 0; q < P; ++q) pptr[(size_t)(v0 + q) + 1] = (L - q + P - 1) / P;
-                }
-                for (int64_t v = 0; v < n_vrows; ++v) pptr[(size_t)v + 1] += pptr[(size_t)v];
-                VRX_HIP(d_pptr.upload(pptr.data(), pptr.size(), s));
-                VRX_HIP(d_pidx.alloc((size_t)o_nnz));
-                VRX_HIP(d_pval.alloc((size_t)o_nnz));
-                vrx_build_pieces<<<(unsigned)((o_nnz + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
-                    o_nnz, o_n_rows, dev->ptr, d_vptr.p, d_pptr.p, dev->idx, dev->val, d_pidx.p, d_pval.p);
-                VRX_HIP(hipGetLastError());
-                u_ptr = pptr.data();
-                du_ptr = d_pptr.p;
-                du_idx = d_pidx.p;
-                du_val = d_pval.p;
-                hc = nullptr;  // (the caller's arrays are the whole rows)
-                hw = nullptr;
-            }
-            const bool pre_done = have_pre && L.greedy_done && !pieces;  // device_build's helper thread already did it
-            // the tile position of every unit (what both routes of the greedy start from)
-            std::vector<int32_t> tile_of_row_own((size_t)n_unit_rows, -1), tpos((size_t)n_unit_rows, -1);
-            for (int64_t pos = 0; pos < (int64_t)t.n_tile * tile_pos; ++pos)
-                if (rowmap[(size_t)pos] >= 0) {
-                    const int32_t u = pieces ? rowmap[(size_t)pos] : vrow_row[(size_t)rowmap[(size_t)pos]];
-                    tile_of_row_own[(size_t)u] = (int32_t)(pos / tile_pos);
-                    tpos[(size_t)u] = (int32_t)pos;
-                }
-            VRX_HIP(d_tile_of_row.upload(tile_of_row_own.data(), tile_of_row_own.size(), s));
-            // ---- the greedy on the device (vrx_build.h, vrx_balance_greedy): no entry leaves the GPU ----------
-            const int max_block = env_int("VIREO_BALANCE_BLOCK", 64);
-            const VrxBalBlocks blocks = vrx_bal_blocks(t.n_slab, max_block);
-            const bool check = env_int("VIREO_BALANCE_CHECK", 0) != 0;
-            const char* gm = getenv("VIREO_BALANCE_GREEDY");
-            const int64_t n_cols_all = (int64_t)t.n_tile * o_n_contract, n_groups = (int64_t)t.n_tile * blocks.nb;
-            bool dev_greedy = !(gm && !strcmp(gm, "host")) && !pre_done && blocks.bs <= 64 &&
-                              (tile_pos + 1) * 64 + 2 * VRX_BAL_BATCH * 4 <= 160 * 1024 && tile_pos <= 4095 && n_cols_all < (int64_t)INT32_MAX &&
-                              n_groups < ((int64_t)1 << 20) && (int64_t)t.n_tile * tile_pos < (int64_t)INT32_MAX;
-            // (the sort buffers of the greedy's preparation serve the relabel below as well: multi-GB
-            //  allocations and releases are what a large build spends its time on)
-            DevBuf<uint64_t> k_in, k_out;
-            DevBuf<uint32_t> v_in, v_out;
-            VRX_HIP(k_in.alloc((size_t)o_nnz));
-            VRX_HIP(k_out.alloc((size_t)o_nnz));
-            VRX_HIP(v_in.alloc((size_t)o_nnz));
-            VRX_HIP(v_out.alloc((size_t)o_nnz));
-            if (dev_greedy) {
-                DevBuf<int32_t> d_tpos, d_flags;
-                DevBuf<uint64_t> ok_in, ok_out;
-                DevBuf<uint32_t> d_cptr, d_deg, d_ostart, d_ovals;
-                DevBuf<uint64_t>&bk_in = k_in, &bk_out = k_out;
-                DevBuf<uint32_t>&bv_in = v_in, &bv_out = v_out;
-                DevBuf<int64_t> d_seg;
-                DevBuf<char> tmp;
-                int cbits = 1, tbits = 1, gbits = 1;
-                while (((int64_t)1 << cbits) < o_n_contract) ++cbits;
-                while (((int64_t)1 << tbits) < (int64_t)t.n_tile + 1) ++tbits;
-                while (((int64_t)1 << gbits) < n_groups) ++gbits;
-                const unsigned nbe = (unsigned)((o_nnz + VRX_BLOCK - 1) / VRX_BLOCK);
-                const unsigned nbc = (unsigned)((n_cols_all + 1 + VRX_BLOCK - 1) / VRX_BLOCK);
-                VRX_HIP(d_tpos.upload(tpos.data(), tpos.size(), s));
-                const int32_t zero2[2] = {0, 0};
-                VRX_HIP(d_flags.upload(zero2, 2, s));
-                vrx_bal_keys<<<nbe, VRX_BLOCK, 0, s>>>(o_nnz, n_unit_rows, du_ptr, du_idx, du_val, d_tpos.p, (int)tile_pos,
-                                                       t.n_tile, cbits, bk_in.p, bv_in.p);
-                VRX_HIP(hipGetLastError());
-                size_t tmp_bytes = 0, tmp2 = 0, tmp3 = 0;
-                VRX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, bk_in.p, bk_out.p, bv_in.p, bv_out.p,
-                                                           (size_t)o_nnz, 0, cbits + tbits, s));
-                VRX_HIP(ok_in.alloc((size_t)n_cols_all));
-                VRX_HIP(ok_out.alloc((size_t)n_cols_all));
-                VRX_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp2, ok_in.p, ok_out.p, (size_t)n_cols_all, 0,
-                                                          cbits + 12 + gbits, s));
-                VRX_HIP(d_deg.alloc((size_t)n_cols_all));
-                VRX_HIP(d_ostart.alloc((size_t)n_cols_all));
-                VRX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp3, d_deg.p, d_ostart.p, (size_t)n_cols_all, s));
-                VRX_HIP(tmp.alloc(std::max(tmp_bytes, std::max(tmp2, tmp3))));
-                VRX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, bk_in.p, bk_out.p, bv_in.p, bv_out.p,
-                                                           (size_t)o_nnz, 0, cbits + tbits, s));
-                VRX_HIP(d_cptr.alloc((size_t)n_cols_all + 1));
-                vrx_bal_cptr<<<nbc, VRX_BLOCK, 0, s>>>(n_cols_all, o_n_contract, o_nnz, bk_out.p, cbits, d_cptr.p);
-                VRX_HIP(hipGetLastError());
-                vrx_bal_order_keys<<<nbc, VRX_BLOCK, 0, s>>>(n_cols_all, o_n_contract, d_cptr.p, slab_rows, blocks.bs,
-                                                             blocks.nb, cbits, ok_in.p, d_flags.p);
-                VRX_HIP(hipGetLastError());
-                VRX_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.p, tmp2, ok_in.p, ok_out.p, (size_t)n_cols_all, 0,
-                                                          cbits + 12 + gbits, s));
-                VRX_HIP(d_seg.alloc((size_t)n_groups + 1));
-                vrx_bal_groups<<<(unsigned)((n_groups + 1 + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
-                    n_groups, n_cols_all, ok_out.p, 12 + cbits, d_seg.p);
-                VRX_HIP(hipGetLastError());
-                vrx_bal_degrees<<<nbc, VRX_BLOCK, 0, s>>>(n_cols_all, ok_out.p, cbits, d_deg.p);
-                VRX_HIP(hipGetLastError());
-                VRX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp3, d_deg.p, d_ostart.p, (size_t)n_cols_all, s));
-                uint32_t n_stream = 0;  // the entries that count = first entry of the column behind the last one
-                VRX_HIP(hipMemcpyAsync(&n_stream, d_cptr.p + n_cols_all, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                VRX_HIP(d_ovals.alloc((size_t)o_nnz));
-                vrx_bal_stream<<<nbc, VRX_BLOCK, 0, s>>>(n_cols_all, o_n_contract, ok_out.p, cbits, blocks.nb, d_cptr.p,
-                                                         bv_out.p, d_ostart.p, d_ovals.p);
-                VRX_HIP(hipGetLastError());
-                VRX_HIP(d_posmap.alloc((size_t)n_cols_all));
-                VRX_HIP(t.perm.alloc((size_t)(t.n_tile * slots)));
-                VRX_HIP(hipMemsetAsync(t.perm.p, 0, (size_t)(t.n_tile * slots) * sizeof(int32_t), s));
-                VRX_HIP(hipStreamSynchronize(s));  // (n_stream)
-                const size_t lds = (size_t)(tile_pos + 1) * 64 + 2 * VRX_BAL_BATCH * sizeof(uint32_t);
-                VRX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(vrx_balance_greedy),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                vrx_balance_greedy<<<(unsigned)n_groups, 64, lds, s>>>(ok_out.p, d_seg.p, d_ostart.p, d_ovals.p,
-                                                                      (int64_t)n_stream, o_n_contract, cbits, t.n_slab,
-                                                                      slab_rows, blocks.bs, blocks.nb, (int)tile_pos,
-                                                                      d_posmap.p, t.perm.p, d_flags.p + 1);
-                VRX_HIP(hipGetLastError());
-                int32_t flags[2] = {0, 0};
-                VRX_HIP(hipMemcpyAsync(flags, d_flags.p, sizeof flags, hipMemcpyDeviceToHost, s));
-                VRX_HIP(hipStreamSynchronize(s));
-                lap("greedy on the device");
-                if (flags[0] || flags[1]) {  // a column deeper than 4095 tile rows / a block without room: cannot be
-                    dev_greedy = false;
-                    if (timing) fprintf(stderr, "[vrx build] balanced slabs: device greedy declined (%d, %d)\n", flags[0], flags[1]);
-                }
-            }
-            std::vector<int32_t> posmap_own, perm_own, tor_unused;
-            if (!dev_greedy || check) {  // ---- the greedy on host threads (the specification) -----------------
-                if (!hc && !hw && !pre_done) {
-                    DevBuf<uint8_t> d_words;
-                    VRX_HIP(d_words.alloc((size_t)o_nnz));
-                    vrx_build_words<<<(unsigned)((o_nnz + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(o_nnz, du_val, d_words.p);
-                    VRX_HIP(hipGetLastError());
-                    h_idx.resize((size_t)o_nnz);
-                    h_words.resize((size_t)o_nnz);
-                    VRX_HIP(hipMemcpyAsync(h_idx.data(), du_idx, (size_t)o_nnz * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                    VRX_HIP(hipMemcpyAsync(h_words.data(), d_words.p, (size_t)o_nnz, hipMemcpyDeviceToHost, s));
-                    VRX_HIP(hipStreamSynchronize(s));
-                }
-                lap("download rows");
-                if (!pre_done) {
-                    if (hc) (void)host_words(*hc, o_nnz, o_n_contract, h_words);  // (validated by now)
-                    const int32_t* g_idx = hc ? hc->idx : hw ? hw->idx : h_idx.data();
-                    const uint8_t* g_words = hw ? hw->words : h_words.data();
-                    greedy_tiles(L, pieces, u_ptr, g_idx, g_words, n_unit_rows, posmap_own, perm_own, tor_unused);
-                }
-                std::vector<int32_t>&posmap = pre_done ? L.posmap : posmap_own, &perm = pre_done ? L.perm : perm_own;
-                if (pre_done && timing)
-                    fprintf(stderr, "[vrx build] balanced slabs (mode %d): greedy ran beside the upload     %.3f s (hidden)\n", mode, L.greedy_seconds);
-                lap("greedy (host threads)");
-                std::vector<int32_t>().swap(h_idx);
-                std::vector<uint8_t>().swap(h_words);
-                if (dev_greedy) {  // VIREO_BALANCE_CHECK=1: the device's result against the specification, bit for bit
-                    std::vector<int32_t> dp((size_t)n_cols_all), dq((size_t)(t.n_tile * slots));
-                    VRX_HIP(hipMemcpyAsync(dp.data(), d_posmap.p, dp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                    VRX_HIP(hipMemcpyAsync(dq.data(), t.perm.p, dq.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                    VRX_HIP(hipStreamSynchronize(s));
-                    for (int64_t i = 0; i < n_cols_all; ++i)
-                        if (dp[(size_t)i] != posmap[(size_t)i]) {
-                            vrx_set_error("balanced slabs: the device greedy differs from the host's at tile %lld, contracted "
-                                          "row %lld (%d against %d)", (long long)(i / o_n_contract),
-                                          (long long)(i % o_n_contract), dp[(size_t)i], posmap[(size_t)i]);
-                            return VRX_ERR_UNSUPPORTED;
-                        }
-                    if (dq != perm) {
-                        vrx_set_error("balanced slabs: the device greedy's slab lists differ from the host's");
-                        return VRX_ERR_UNSUPPORTED;
-                    }
-                    if (timing) fprintf(stderr, "[vrx build] balanced slabs (mode %d): device greedy == host greedy (%lld columns)\n", mode, (long long)n_cols_all);
-                } else {
-                    VRX_HIP(d_posmap.upload(posmap.data(), posmap.size(), s));
-                    VRX_HIP(t.perm.upload(perm.data(), perm.size(), s));
-                }
-            }
-            const unsigned nbe = (unsigned)((o_nnz + VRX_BLOCK - 1) / VRX_BLOCK);
-            int rbits = 1, pbits = 1;  // key = row << pbits | position: as few radix passes as the sizes need
-            while (((int64_t)1 << rbits) < n_unit_rows) ++rbits;
-            while (((int64_t)1 << pbits) < std::max<int64_t>(slots, o_n_contract)) ++pbits;
-            vrx_build_relabel<<<nbe, VRX_BLOCK, 0, s>>>(o_nnz, n_unit_rows, o_n_contract, du_ptr, du_idx,
-                                                        d_tile_of_row.p, d_posmap.p, pbits, k_in.p, v_in.p);
-            VRX_HIP(hipGetLastError());
-            size_t tmp_bytes = 0;
-            VRX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, k_in.p, k_out.p, v_in.p, v_out.p,
-                                                       (size_t)o_nnz, 0, pbits + rbits, s));
-            DevBuf<char> tmp;
-            VRX_HIP(tmp.alloc(tmp_bytes));
-            VRX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, k_in.p, k_out.p, v_in.p, v_out.p,
-                                                       (size_t)o_nnz, 0, pbits + rbits, s));
-            VRX_HIP(d_idx2.alloc((size_t)o_nnz));
-            VRX_HIP(d_val2.alloc((size_t)o_nnz));
-            vrx_build_relabel_gather<<<nbe, VRX_BLOCK, 0, s>>>(o_nnz, k_out.p, v_out.p, du_val, pbits, d_idx2.p, d_val2.p);
-            VRX_HIP(hipGetLastError());
-            if (pieces) {  // the stream's rows are the pieces now: one piece per "row", nothing left to cut
-                std::vector<int32_t> iota((size_t)n_vrows + 1);
-                for (int64_t v = 0; v <= n_vrows; ++v) iota[(size_t)v] = (int32_t)v;
-                VRX_HIP(d_iota.upload(iota.data(), iota.size(), s));
-                VRX_HIP(hipStreamSynchronize(s));
-                A.ptr = d_pptr.p;
-                A.vptr = d_iota.p;
-                A.vrow_row = d_iota.p;
-            }
-            VRX_HIP(hipStreamSynchronize(s));
-            d_pidx.release();
-            d_pval.release();
-            lap("upload + relabel + sort");
-            t.balance_seconds = now() - tm_begin;
-            A.idx = d_idx2.p;
-            A.val = d_val2.p;
-            t.balanced = true;
-        }
-        const int64_t n_pos = n_wave * t.n_slab * RW, nsr = (int64_t)t.n_slab * NR * PH;
-        VRX_REQUIRE(n_pos < INT32_MAX * (int64_t)VRX_BLOCK, "tiled stream: too many segments");
-        VRX_HIP(seg_lo.alloc((size_t)n_pos));
-        VRX_HIP(seg_hi.alloc((size_t)n_pos));
-        VRX_HIP(rlen.alloc((size_t)(n_wave * nsr)));
-        VRX_HIP(d_too.alloc(1));
-        VRX_HIP(hipMemsetAsync(d_too.p, 0, sizeof(int32_t), s));
-        VRX_HIP(t.bnd.alloc((size_t)(n_wave * per_wave)));
-        DevBuf<int64_t> d_wlen;
-        VRX_HIP(d_wlen.alloc((size_t)n_wave));
-        vrx_build_count<<<(unsigned)((n_pos + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
-            A, seg_lo.p, seg_hi.p, rlen.p);
+// The greedy on host threads (the specification): the units' indices and one byte of FORM 1 words per entry
+// (vrx_build_words) come back from the device.
+static int greedy_host(const BalanceUnits& U, const TileLayout& L, int RW, bool pieces, hipStream_t s, LapTimer& lap,
+                       std::vector<int32_t>& posmap, std::vector<int32_t>& perm) {
+    std::vector<int32_t> h_idx((size_t)U.nnz);
+    std::vector<uint8_t> h_words((size_t)U.nnz);
+    {
+        DevBuf<uint8_t> d_words;
+        VRX_HIP(d_words.alloc((size_t)U.nnz));
+        vrx_build_words<<<(unsigned)((U.nnz + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(U.nnz, U.dev.val, d_words.p);
         VRX_HIP(hipGetLastError());
-        vrx_build_offsets<<<(unsigned)((n_wave + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
-            A, rlen.p, t.bnd.p, d_wlen.p, d_too.p);
-        VRX_HIP(hipGetLastError());
-        int32_t h_too = 0;
-        VRX_HIP(hipMemcpyAsync(wave_len.data(), d_wlen.p, (size_t)n_wave * sizeof(int64_t),
-                               hipMemcpyDeviceToHost, s));
-        VRX_HIP(hipMemcpyAsync(&h_too, d_too.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipMemcpyAsync(h_idx.data(), U.dev.idx, (size_t)U.nnz * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipMemcpyAsync(h_words.data(), d_words.p, (size_t)U.nnz, hipMemcpyDeviceToHost, s));
         VRX_HIP(hipStreamSynchronize(s));
-        if (h_too) {
-            vrx_set_error("tiled stream: wave stream >= 2^31 words");
+    }
+    lap("download rows");
+    greedy_tiles(L, RW, pieces, U, h_idx.data(), h_words.data(), posmap, perm);
+    lap("greedy (host threads)");
+    return VRX_OK;
+}
+
+// VIREO_BALANCE_CHECK=1: the device greedy's result against the specification, bit for bit
+static int check_greedy(const DevBuf<int32_t>& d_posmap, const DevBuf<int32_t>& d_perm, const std::vector<int32_t>& posmap,
+                        const std::vector<int32_t>& perm, int64_t n_contract, int mode, bool timing, hipStream_t s) {
+    std::vector<int32_t> dp(posmap.size()), dq(perm.size());
+    VRX_HIP(hipMemcpyAsync(dp.data(), d_posmap.p, dp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(dq.data(), d_perm.p, dq.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    for (size_t i = 0; i < dp.size(); ++i)
+        if (dp[i] != posmap[i]) {
+            vrx_set_error("balanced slabs: the device greedy differs from the host's at tile %lld, contracted "
+                          "row %lld (%d against %d)", (long long)(i / n_contract), (long long)(i % n_contract),
+                          dp[i], posmap[i]);
             return VRX_ERR_UNSUPPORTED;
         }
-        int64_t total = 0, longest_wave = 0;
-        for (int64_t w = 0; w < n_wave; ++w) {
-            wave_start[(size_t)w] = total;
-            total += wave_len[(size_t)w];
-            longest_wave = std::max(longest_wave, wave_len[(size_t)w]);
-        }
-        t.pad_ratio = o_nnz > 0 ? (double)total / (double)o_nnz : 0.0;
-        t.imbalance = total > 0 ? (double)longest_wave * (double)n_wave / (double)total : 1.0;
-        if (guard && t.pad_ratio * std::max(1.0, t.imbalance / 1.5) > (double)env_int("VIREO_LDS_MAX_PAD", 3)) {
-            t.bnd.release();
-            t.ready = false;
-            return VRX_OK;
-        }
-        VRX_HIP(t.ent.alloc((size_t)total + 8));
-        VRX_HIP(hipMemsetAsync(t.ent.p + total, 0, 8 * sizeof(uint32_t), s));
-        VRX_HIP(t.wave_start.upload(wave_start.data(), wave_start.size(), s));
-        const int64_t n_fill = n_wave * nsr * (G / 2);
-        VRX_REQUIRE(n_fill < INT32_MAX * (int64_t)VRX_BLOCK, "tiled stream: too many rounds");
-        vrx_build_fill<<<(unsigned)((n_fill + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
-            A, seg_lo.p, seg_hi.p, rlen.p, t.bnd.p, t.wave_start.p, t.ent.p);
-        VRX_HIP(hipGetLastError());
-        VRX_HIP(t.rowmap.upload(rowmap.data(), rowmap.size(), s));
-        if (t.split) {
-            VRX_HIP(t.vptr.upload(vptr.data(), vptr.size(), s));
-            VRX_HIP(t.split_rows.upload(split_rows.data(), split_rows.size(), s));
-        }
-        VRX_HIP(hipMemcpyAsync(bnd.data(), t.bnd.p, bnd.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        VRX_HIP(hipStreamSynchronize(s));
-        const int rc = plan_items(t, bnd.data(), n_wave, NR * PH, n_cu, rowmap.data(), mode, s);
-        if (rc) return rc;
-        t.ready = true;
-        return VRX_OK;
-    }
-    std::vector<std::vector<uint32_t>> wave_words((size_t)n_wave);
-    auto walk = [&](int64_t w) {
-        std::vector<uint32_t>& dst = wave_words[(size_t)w];
-        dst.reserve((size_t)((double)o_nnz / (double)n_wave * 2.3) + 1024);
-        const int32_t* rm = rowmap.data() + w * RW;
-        std::vector<int64_t> cursor((size_t)RW);
-        std::vector<uint32_t> segw[G], second;
-        for (int c = 0; c < RW; ++c) cursor[(size_t)c] = rm[c] >= 0 ? ptr[vrow_row[(size_t)rm[c]]] : 0;
-        int32_t* bw = bnd.data() + w * per_wave;
-        int64_t rel = 0;
-        for (int sl = 0; sl < t.n_slab; ++sl) {
-            const int64_t lim = (int64_t)(sl + 1) * slab_rows, base = (int64_t)sl * slab_rows;
-            for (int r = 0; r < NR; ++r) {
-                if (rel >= INT32_MAX - 4096) {
-                    too_long = true;
-                    return;
-                }
-                // the groups' segments of this slab
-                int64_t s_lo[G], s_hi[G], s_step[G];
-                for (int g = 0; g < G; ++g) {
-                    const int32_t v = rm[r * G + g];
-                    s_lo[g] = s_hi[g] = 0;
-                    s_step[g] = 1;
-                    if (v >= 0) {
-                        const int32_t row = vrow_row[(size_t)v];
-                        int64_t hi = cursor[(size_t)(r * G + g)];
-                        const int64_t seg = hi, stop = ptr[row + 1];
-                        while (hi < stop && idx[hi] < lim) ++hi;
-                        cursor[(size_t)(r * G + g)] = hi;
-                        // this piece's share of the row's slab segment [seg, hi)
-                        s_step[g] = vptr[(size_t)row + 1] - vptr[(size_t)row];
-                        s_lo[g] = seg + ((int64_t)(v - vptr[(size_t)row]) + sl) % s_step[g];
-                        s_hi[g] = hi;
-                    }
-                }
-                for (int ph = 0; ph < PH; ++ph) {
-                int64_t longest = 0;
-                for (int g = 0; g < G; ++g) {
-                    std::vector<uint32_t>& sw = segw[g];
-                    sw.clear();
-                    for (int64_t e = s_lo[g]; e < s_hi[g]; e += s_step[g]) {
-                        if (form == 0) {
-                            sw.push_back(((uint32_t)(idx[e] - base) << 22) |
-                                         ((uint32_t)val[e].x << 11) | (uint32_t)val[e].y);
-                        } else if (form == 1) {
-                            const uint32_t at = f1_base + (uint32_t)(idx[e] - base) * 256u;
-                            push_value(sw, val[e].x, at);
-                            push_value(sw, (int64_t)val[e].y - val[e].x, at + 128u);
-                        } else {  // form 2: AD entries in phase 0, BD entries in phase 1
-                            const uint32_t at = f1_base + (uint32_t)(idx[e] - base) * 128u;
-                            push_value(sw, ph == 0 ? (int64_t)val[e].x : (int64_t)val[e].y - val[e].x, at);
-                        }
-                    }
-                    longest = std::max<int64_t>(longest, (int64_t)sw.size());
-                }
-                // Bank conflicts.  The dense rows are 128 B (ID_prob rows; the AD / BD half
-                // rows), so the LDS bank of a slice depends on one address bit of the entry
-                // (index parity / half).  ds_read_b128 serves lane groups {0,3,5,6}, {1,2,4,7}
-                // (+8) together, and the two groups with the same slice rotation (g & 1) collide
-                // whenever that bit agrees.  The order of a segment's entries is free, and the
-                // zero words that pad a segment to the round's length can point at either
-                // parity: group P walks its bit-0 entries (then bit-0 padding) up to a split
-                // position z and its bit-1 entries after it, its partner Q the other way round.
-                // z exists whenever the pair's bit-0 entries and its bit-1 entries each fit
-                // into the round, i.e. almost always.
-                if (parity_order && bit_shift >= 0) {
-                    for (int g = 0; g < G; ++g) {
-                        // the group that shares g's rotation inside g's service group holds
-                        // lanes ^ 24 (ds_read_b128: {0-3,12-15,20-27}, {4-11,16-19,28-31}, +32)
-                        const int q = g ^ (24 / VRX_LDS_LPE);
-                        if (q < g) continue;
-                        std::vector<uint32_t> part[2][2];  // [P / Q][bit]
-                        for (int m = 0; m < 2; ++m)
-                            for (uint32_t wd : segw[m ? q : g]) part[m][(wd >> bit_shift) & 1u].push_back(wd);
-                        const int64_t p0 = (int64_t)part[0][0].size(), p1 = (int64_t)part[0][1].size();
-                        const int64_t q0 = (int64_t)part[1][0].size(), q1 = (int64_t)part[1][1].size();
-                        const int64_t zlo = std::max(p0, q1), zhi = std::min(longest - p1, longest - q0);
-                        if (zlo > zhi) {  // does not fit: opposite orders, as far as that goes
-                            segw[g] = part[0][0];
-                            segw[g].insert(segw[g].end(), part[0][1].begin(), part[0][1].end());
-                            segw[q] = part[1][1];
-                            segw[q].insert(segw[q].end(), part[1][0].begin(), part[1][0].end());
-                            continue;
-                        }
-                        const int64_t z = (zlo + zhi) / 2;
-                        const uint32_t pad0 = form != 0 ? f1_base : 0u, pad1 = pad0 | 1u << bit_shift;
-                        auto lay = [&](std::vector<uint32_t>& out, const std::vector<uint32_t>& first,
-                                       uint32_t pad_first, const std::vector<uint32_t>& rest,
-                                       uint32_t pad_rest) {
-                            out = first;
-                            out.resize((size_t)z, pad_first);
-                            out.insert(out.end(), rest.begin(), rest.end());
-                            out.resize((size_t)longest, pad_rest);
-                        };
-                        lay(segw[g], part[0][0], pad0, part[0][1], pad1);
-                        lay(segw[q], part[1][1], pad1, part[1][0], pad0);
-                    }
-                }
-                // offset | entries in the last trip (0 = full): the kernel skips the padding
-                bw[((int64_t)sl * NR + r) * PH + ph] = (int32_t)(rel | (longest % U));
-                longest = (longest + U - 1) / U * U;
-                dst.resize((size_t)(rel + longest * G));
-                for (int64_t j = 0; j < longest; ++j)
-                    for (int g = 0; g < G; ++g)  // padding: value 0 (forms 1, 2: at the slab's first row)
-                        dst[(size_t)(rel + vrx_trip_slot(j, g, G, U, form))] =
-                            j < (int64_t)segw[g].size() ? segw[g][(size_t)j] : pad_word;
-                rel += longest * G;  // (a multiple of 64 words: streams stay 16-B aligned)
-                }
-            }
-        }
-        bw[(int64_t)t.n_slab * NR * PH] = (int32_t)rel;
-        wave_len[(size_t)w] = rel;
-    };
-    parallel_chunks(n_wave, host_threads(), [&](int64_t b0, int64_t e0, int) {
-        for (int64_t w = b0; w < e0; ++w) walk(w);
-    });
-    if (too_long) {
-        vrx_set_error("tiled stream: wave stream >= 2^31 words");
+    if (dq != perm) {
+        vrx_set_error("balanced slabs: the device greedy's slab lists differ from the host's");
         return VRX_ERR_UNSUPPORTED;
     }
+    if (timing)
+        fprintf(stderr, "[vrx build] balanced slabs (mode %d): device greedy == host greedy (%lld columns)\n", mode,
+                (long long)dp.size());
+    return VRX_OK;
+}
+
+// Stage (b)'s result: the relabelled rows the device builder walks instead of the orientation's own, and the
+// per-tile permutation that becomes TiledStream::perm
+struct BalancedRows {
+    DevBuf<int64_t> ptr;    // (rows cut into pieces: the pieces' row pointer ...
+    DevBuf<int32_t> iota;   //  ... and the identity as vptr / vrow_row: one piece per row)
+    DevBuf<int32_t> idx;
+    DevBuf<int2> val;
+    DevBuf<int32_t> perm;
+};
+
+// Stage (b), balanced slabs: per-tile permutation of the contracted rows, entries relabelled + re-sorted.
+// d_vptr: the layout's vptr on the device.
+static int balance_slabs(const TileRows& R, const TileShape& S, const TileLayout& L, const int32_t* d_vptr,
+                         hipStream_t s, BalancedRows& B, double* seconds) {
+    LapTimer lap{s, "balanced slabs (mode " + std::to_string(S.mode) + "):", 28};
+    const int64_t nnz = R.nnz, n_contract = R.n_contract;
+    const int64_t tile_pos = (int64_t)VRX_LDS_WAVES * S.RW, slots = (int64_t)L.n_slab * L.slab_rows;
+    const bool pieces = L.split;
+    BalanceUnits U{R.ptr, R.dev, pieces ? L.n_vrows : R.n_rows, nnz, n_contract, {}, {}};
+    std::vector<int64_t> pptr;
+    DevBuf<int32_t> d_pidx;
+    DevBuf<int2> d_pval;
+    if (pieces) {
+        pptr.assign((size_t)L.n_vrows + 1, 0);
+        for (int64_t r = 0; r < R.n_rows; ++r) {
+            const int64_t len = R.ptr[r + 1] - R.ptr[r];
+            const int32_t v0 = L.vptr[(size_t)r], P = L.vptr[(size_t)r + 1] - v0;
+            for (int32_t q = 0; q < P; ++q) pptr[(size_t)(v0 + q) + 1] = (len - q + P - 1) / P;
+        }
+        for (int64_t v = 0; v < L.n_vrows; ++v) pptr[(size_t)v + 1] += pptr[(size_t)v];
+        VRX_HIP(B.ptr.upload(pptr.data(), pptr.size(), s));
+        VRX_HIP(d_pidx.alloc((size_t)nnz));
+        VRX_HIP(d_pval.alloc((size_t)nnz));
+        vrx_build_pieces<<<(unsigned)((nnz + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
+            nnz, R.n_rows, R.dev.ptr, d_vptr, B.ptr.p, R.dev.idx, R.dev.val, d_pidx.p, d_pval.p);
+        VRX_HIP(hipGetLastError());
+        U.ptr = pptr.data();
+        U.dev = DevRows{B.ptr.p, d_pidx.p, d_pval.p};
+    }
+    // the tile position of every unit (what both routes of the greedy start from)
+    U.tile.assign((size_t)U.n, -1);
+    U.tpos.assign((size_t)U.n, -1);
+    for (int64_t pos = 0; pos < (int64_t)L.n_tile * tile_pos; ++pos)
+        if (L.rowmap[(size_t)pos] >= 0) {
+            const int32_t u = pieces ? L.rowmap[(size_t)pos] : L.vrow_row[(size_t)L.rowmap[(size_t)pos]];
+            U.tile[(size_t)u] = (int32_t)(pos / tile_pos);
+            U.tpos[(size_t)u] = (int32_t)pos;
+        }
+    DevBuf<int32_t> d_tile_of_row, d_posmap;
+    VRX_HIP(d_tile_of_row.upload(U.tile.data(), U.tile.size(), s));
+    const VrxBalBlocks blocks = vrx_bal_blocks(L.n_slab, env_int("VIREO_BALANCE_BLOCK", 64));
+    const bool check = env_int("VIREO_BALANCE_CHECK", 0) != 0;
+    const char* gm = getenv("VIREO_BALANCE_GREEDY");
+    const int64_t n_cols_all = (int64_t)L.n_tile * n_contract, n_groups = (int64_t)L.n_tile * blocks.nb;
+    bool dev_greedy = !(gm && !strcmp(gm, "host")) && blocks.bs <= 64 &&
+                      (tile_pos + 1) * 64 + 2 * VRX_BAL_BATCH * 4 <= 160 * 1024 && tile_pos <= 4095 &&
+                      n_cols_all < (int64_t)INT32_MAX && n_groups < ((int64_t)1 << 20) &&
+                      (int64_t)L.n_tile * tile_pos < (int64_t)INT32_MAX;
+    // (the sort buffers of the greedy's preparation serve the relabel below as well: multi-GB
+    //  allocations and releases are what a large build spends its time on)
+    DevBuf<uint64_t> k_in, k_out;
+    DevBuf<uint32_t> v_in, v_out;
+    VRX_HIP(k_in.alloc((size_t)nnz));
+    VRX_HIP(k_out.alloc((size_t)nnz));
+    VRX_HIP(v_in.alloc((size_t)nnz));
+    VRX_HIP(v_out.alloc((size_t)nnz));
+    int rc;
+    if (dev_greedy) {
+        bool declined = false;
+        if ((rc = greedy_device(U, L, S.RW, blocks, k_in, k_out, v_in, v_out, d_posmap, B.perm, s, lap, &declined)))
+            return rc;
+        dev_greedy = !declined;
+    }
+    if (!dev_greedy || check) {
+        std::vector<int32_t> posmap, perm;
+        if ((rc = greedy_host(U, L, S.RW, pieces, s, lap, posmap, perm))) return rc;
+        if (dev_greedy) {
+            if ((rc = check_greedy(d_posmap, B.perm, posmap, perm, n_contract, S.mode, lap.on, s))) return rc;
+        } else {
+            VRX_HIP(d_posmap.upload(posmap.data(), posmap.size(), s));
+            VRX_HIP(B.perm.upload(perm.data(), perm.size(), s));
+            VRX_HIP(hipStreamSynchronize(s));  // (the host vectors die here)
+        }
+    }
+    // ---- relabel: key = unit << pbits | position -- as few radix passes as the sizes need
+    const unsigned nbe = (unsigned)((nnz + VRX_BLOCK - 1) / VRX_BLOCK);
+    const int rbits = bits_for(U.n), pbits = bits_for(std::max<int64_t>(slots, n_contract));
+    vrx_build_relabel<<<nbe, VRX_BLOCK, 0, s>>>(nnz, U.n, n_contract, U.dev.ptr, U.dev.idx, d_tile_of_row.p,
+                                                d_posmap.p, pbits, k_in.p, v_in.p);
+    VRX_HIP(hipGetLastError());
+    size_t tmp_bytes = 0;
+    VRX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, k_in.p, k_out.p, v_in.p, v_out.p,
+                                               (size_t)nnz, 0, pbits + rbits, s));
+    DevBuf<char> tmp;
+    VRX_HIP(tmp.alloc(tmp_bytes));
+    VRX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, k_in.p, k_out.p, v_in.p, v_out.p,
+                                               (size_t)nnz, 0, pbits + rbits, s));
+    VRX_HIP(B.idx.alloc((size_t)nnz));
+    VRX_HIP(B.val.alloc((size_t)nnz));
+    vrx_build_relabel_gather<<<nbe, VRX_BLOCK, 0, s>>>(nnz, k_out.p, v_out.p, U.dev.val, pbits, B.idx.p, B.val.p);
+    VRX_HIP(hipGetLastError());
+    if (pieces) {  // the stream's rows are the pieces now: one piece per "row", nothing left to cut
+        std::vector<int32_t> iota((size_t)L.n_vrows + 1);
+        for (int64_t v = 0; v <= L.n_vrows; ++v) iota[(size_t)v] = (int32_t)v;
+        VRX_HIP(B.iota.upload(iota.data(), iota.size(), s));
+    }
+    VRX_HIP(hipStreamSynchronize(s));
+    lap("upload + relabel + sort");
+    *seconds = LapTimer::now() - lap.begin;
+    return VRX_OK;
+}
+
+// FORM 1 value field: the top 14 bits of the IEEE double (sign, exponent, 2 mantissa bits) of every chunk of
+// the count (vrx_form1_chunk: 9 = 8 + 1, ...)
+static void push_value(std::vector<uint32_t>& out, int64_t v, uint32_t off) {
+    while (v != 0) {
+        const int64_t c = vrx_form1_chunk(v);
+        const double d = (double)c;
+        uint64_t bits;
+        std::memcpy(&bits, &d, 8);
+        out.push_back((uint32_t)(bits >> 50) << 18 | off);
+        v -= c;
+    }
+}
+
+// Stage (c), the host walk: one wave's stream walks its RW pieces slab by slab, records the (slab, round)
+// offsets in bw and appends the words to `dst`; returns its length, or -1 past 2^31 words.  Waves are independent.
+static int64_t walk_wave(const TileRows& R, const TileLayout& L, const VrxTileArgs& A, int64_t w, int32_t* bw,
+                         std::vector<uint32_t>& dst) {
+    constexpr int G = 64 / VRX_LDS_LPE;
+    const int RW = A.RW, NR = A.NR, U = A.U, PH = A.PH, form = A.form, bit_shift = A.bit_shift;
+    const int64_t* ptr = R.ptr;
+    const int32_t* idx = R.idx;
+    const int2* val = R.val;
+    dst.reserve((size_t)((double)R.nnz / (double)A.n_wave * 2.3) + 1024);
+    const int32_t* rm = L.rowmap.data() + w * RW;
+    std::vector<int64_t> cursor((size_t)RW);
+    std::vector<uint32_t> segw[G];
+    for (int c = 0; c < RW; ++c) cursor[(size_t)c] = rm[c] >= 0 ? ptr[L.vrow_row[(size_t)rm[c]]] : 0;
+    int64_t rel = 0;
+    for (int sl = 0; sl < A.n_slab; ++sl) {
+        const int64_t lim = (int64_t)(sl + 1) * A.slab_rows, base = (int64_t)sl * A.slab_rows;
+        for (int r = 0; r < NR; ++r) {
+            if (rel >= INT32_MAX - 4096) return -1;
+            // the groups' segments of this slab
+            int64_t s_lo[G], s_hi[G], s_step[G];
+            for (int g = 0; g < G; ++g) {
+                const int32_t v = rm[r * G + g];
+                s_lo[g] = s_hi[g] = 0;
+                s_step[g] = 1;
+                if (v >= 0) {
+                    const int32_t row = L.vrow_row[(size_t)v];
+                    int64_t hi = cursor[(size_t)(r * G + g)];
+                    const int64_t seg = hi, stop = ptr[row + 1];
+                    while (hi < stop && idx[hi] < lim) ++hi;
+                    cursor[(size_t)(r * G + g)] = hi;
+                    // this piece's share of the row's slab segment [seg, hi)
+                    s_step[g] = L.vptr[(size_t)row + 1] - L.vptr[(size_t)row];
+                    s_lo[g] = seg + ((int64_t)(v - L.vptr[(size_t)row]) + sl) % s_step[g];
+                    s_hi[g] = hi;
+                }
+            }
+            for (int ph = 0; ph < PH; ++ph) {
+            int64_t longest = 0;
+            for (int g = 0; g < G; ++g) {
+                std::vector<uint32_t>& sw = segw[g];
+                sw.clear();
+                for (int64_t e = s_lo[g]; e < s_hi[g]; e += s_step[g]) {
+                    if (form == 0) {
+                        sw.push_back(((uint32_t)(idx[e] - base) << 22) |
+                                     ((uint32_t)val[e].x << 11) | (uint32_t)val[e].y);
+                    } else if (form == 1) {
+                        const uint32_t at = A.f1_base + (uint32_t)(idx[e] - base) * 256u;
+                        push_value(sw, val[e].x, at);
+                        push_value(sw, (int64_t)val[e].y - val[e].x, at + 128u);
+                    } else {  // form 2: AD entries in phase 0, BD entries in phase 1
+                        const uint32_t at = A.f1_base + (uint32_t)(idx[e] - base) * 128u;
+                        push_value(sw, ph == 0 ? (int64_t)val[e].x : (int64_t)val[e].y - val[e].x, at);
+                    }
+                }
+                longest = std::max<int64_t>(longest, (int64_t)sw.size());
+            }
+            // Bank conflicts.  The dense rows are 128 B (ID_prob rows; the AD / BD half
+            // rows), so the LDS bank of a slice depends on one address bit of the entry
+            // (index parity / half).  ds_read_b128 serves lane groups {0,3,5,6}, {1,2,4,7}
+            // (+8) together, and the two groups with the same slice rotation (g & 1) collide
+            // whenever that bit agrees.  The order of a segment's entries is free, and the
+            // zero words that pad a segment to the round's length can point at either
+            // parity: group P walks its bit-0 entries (then bit-0 padding) up to a split
+            // position z and its bit-1 entries after it, its partner Q the other way round.
+            // z exists whenever the pair's bit-0 entries and its bit-1 entries each fit
+            // into the round, i.e. almost always.
+            if (A.pairing && bit_shift >= 0) {
+                for (int g = 0; g < G; ++g) {
+                    // the group that shares g's rotation inside g's service group holds
+                    // lanes ^ 24 (ds_read_b128: {0-3,12-15,20-27}, {4-11,16-19,28-31}, +32)
+                    const int q = g ^ A.xor_partner;
+                    if (q < g) continue;
+                    std::vector<uint32_t> part[2][2];  // [P / Q][bit]
+                    for (int m = 0; m < 2; ++m)
+                        for (uint32_t wd : segw[m ? q : g]) part[m][(wd >> bit_shift) & 1u].push_back(wd);
+                    const int64_t p0 = (int64_t)part[0][0].size(), p1 = (int64_t)part[0][1].size();
+                    const int64_t q0 = (int64_t)part[1][0].size(), q1 = (int64_t)part[1][1].size();
+                    const int64_t zlo = std::max(p0, q1), zhi = std::min(longest - p1, longest - q0);
+                    if (zlo > zhi) {  // does not fit: opposite orders, as far as that goes
+                        segw[g] = part[0][0];
+                        segw[g].insert(segw[g].end(), part[0][1].begin(), part[0][1].end());
+                        segw[q] = part[1][1];
+                        segw[q].insert(segw[q].end(), part[1][0].begin(), part[1][0].end());
+                        continue;
+                    }
+                    const int64_t z = (zlo + zhi) / 2;
+                    const uint32_t pad0 = A.pad_word, pad1 = pad0 | 1u << bit_shift;
+                    auto lay = [&](std::vector<uint32_t>& out, const std::vector<uint32_t>& first,
+                                   uint32_t pad_first, const std::vector<uint32_t>& rest,
+                                   uint32_t pad_rest) {
+                        out = first;
+                        out.resize((size_t)z, pad_first);
+                        out.insert(out.end(), rest.begin(), rest.end());
+                        out.resize((size_t)longest, pad_rest);
+                    };
+                    lay(segw[g], part[0][0], pad0, part[0][1], pad1);
+                    lay(segw[q], part[1][1], pad1, part[1][0], pad0);
+                }
+            }
+            // offset | entries in the last trip (0 = full): the kernel skips the padding
+            bw[((int64_t)sl * NR + r) * PH + ph] = (int32_t)(rel | (longest % U));
+            longest = (longest + U - 1) / U * U;
+            dst.resize((size_t)(rel + longest * G));
+            for (int64_t j = 0; j < longest; ++j)
+                for (int g = 0; g < G; ++g)  // padding: value 0 (forms 1, 2: at the slab's first row)
+                    dst[(size_t)(rel + vrx_trip_slot(j, g, G, U, form))] =
+                        j < (int64_t)segw[g].size() ? segw[g][(size_t)j] : A.pad_word;
+            rel += longest * G;  // (a multiple of 64 words: streams stay 16-B aligned)
+            }
+        }
+    }
+    bw[(int64_t)A.n_slab * NR * PH] = (int32_t)rel;
+    return rel;
+}
+
+// Stage (e), what both builders end with: the waves' offsets, the padding guard, the words (`emit(total,
+// wave_start)` fills t.ent), the boundaries (bnd: on the host, or already in t.bnd), the row tables and the
+// work list.  A stream the guard rejects stays not ready.
+template <class Emit>
+static int finish_stream(TiledStream& t, const TileShape& S, const TileLayout& L, const VrxTileArgs& A,
+                         const std::vector<int64_t>& wave_len, std::vector<int32_t>& bnd, bool bnd_on_device,
+                         int n_cu, int64_t nnz, hipStream_t s, Emit&& emit) {
+    const int64_t n_wave = A.n_wave;
+    std::vector<int64_t> wave_start((size_t)n_wave);
     int64_t total = 0, longest_wave = 0;
     for (int64_t w = 0; w < n_wave; ++w) {
         wave_start[(size_t)w] = total;
@@ -1141,16 +1018,51 @@ static int build_tiled(Orient& o, const int64_t* ptr, const int32_t* idx, const 
     }
     // Guard: past VIREO_LDS_MAX_PAD stream words per entry (default 3; padding x imbalance of
     // the slowest wave) the global-gather pass is the faster one, so no stream is kept.
-    t.pad_ratio = o_nnz > 0 ? (double)total / (double)o_nnz : 0.0;
+    t.pad_ratio = nnz > 0 ? (double)total / (double)nnz : 0.0;
     t.imbalance = total > 0 ? (double)longest_wave * (double)n_wave / (double)total : 1.0;
-    if (guard && t.pad_ratio * std::max(1.0, t.imbalance / 1.5) > (double)env_int("VIREO_LDS_MAX_PAD", 3)) {
-        t.ready = false;
+    if (S.guard && t.pad_ratio * std::max(1.0, t.imbalance / 1.5) > (double)env_int("VIREO_LDS_MAX_PAD", 3))
         return VRX_OK;
-    }
-    // the waves' buffers go to the device back to back (+ slack for the last dwordx4 refill)
+    // the waves' streams back to back (+ slack for the last dwordx4 refill)
     VRX_HIP(t.ent.alloc((size_t)total + 8));
     VRX_HIP(hipMemsetAsync(t.ent.p + total, 0, 8 * sizeof(uint32_t), s));
-    {
+    VRX_HIP(t.wave_start.upload(wave_start.data(), wave_start.size(), s));
+    int rc = emit(total, wave_start);
+    if (rc) return rc;
+    if (bnd_on_device)
+        VRX_HIP(hipMemcpyAsync(bnd.data(), t.bnd.p, bnd.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    else
+        VRX_HIP(t.bnd.upload(bnd.data(), bnd.size(), s));
+    VRX_HIP(t.rowmap.upload(L.rowmap.data(), L.rowmap.size(), s));
+    if (t.split) {
+        VRX_HIP(t.vptr.upload(L.vptr.data(), L.vptr.size(), s));
+        VRX_HIP(t.split_rows.upload(L.split_rows.data(), L.split_rows.size(), s));
+    }
+    VRX_HIP(hipStreamSynchronize(s));
+    rc = plan_items(t, bnd.data(), n_wave, A.NR * A.PH, n_cu, L.rowmap.data(), S.mode, s);
+    if (rc) return rc;
+    t.ready = true;
+    return VRX_OK;
+}
+
+static int stream_on_host(TiledStream& t, const TileRows& R, const TileShape& S, const TileLayout& L,
+                          const VrxTileArgs& A, int n_cu, hipStream_t s) {
+    const int64_t n_wave = A.n_wave, per_wave = (int64_t)A.n_slab * A.NR * A.PH + 1;
+    std::vector<int64_t> wave_len((size_t)n_wave, 0);
+    std::vector<int32_t> bnd((size_t)(n_wave * per_wave));
+    std::vector<std::vector<uint32_t>> wave_words((size_t)n_wave);
+    std::atomic<bool> too_long{false};
+    parallel_chunks(n_wave, host_threads(), [&](int64_t b0, int64_t e0, int) {
+        for (int64_t w = b0; w < e0 && !too_long; ++w) {
+            wave_len[(size_t)w] = walk_wave(R, L, A, w, bnd.data() + w * per_wave, wave_words[(size_t)w]);
+            if (wave_len[(size_t)w] < 0) too_long = true;
+        }
+    });
+    if (too_long) {
+        vrx_set_error("tiled stream: wave stream >= 2^31 words");
+        return VRX_ERR_UNSUPPORTED;
+    }
+    return finish_stream(t, S, L, A, wave_len, bnd, false, n_cu, R.nnz, s,
+                         [&](int64_t total, const std::vector<int64_t>& wave_start) {
         std::unique_ptr<uint32_t[]> all(new uint32_t[(size_t)total + 1]);
         parallel_chunks(n_wave, host_threads(), [&](int64_t b0, int64_t e0, int) {
             for (int64_t w = b0; w < e0; ++w) {
@@ -1160,22 +1072,102 @@ static int build_tiled(Orient& o, const int64_t* ptr, const int32_t* idx, const 
                 std::vector<uint32_t>().swap(src);
             }
         });
-        VRX_HIP(hipMemcpyAsync(t.ent.p, all.get(), (size_t)total * sizeof(uint32_t),
-                               hipMemcpyHostToDevice, s));
+        VRX_HIP(hipMemcpyAsync(t.ent.p, all.get(), (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         VRX_HIP(hipStreamSynchronize(s));
+        return VRX_OK;
+    });
+}
+
+// Stage (d), the device builder's walk (vrx_build.h): every segment's bounds and round length
+// (vrx_build_count), the waves' (slab, round) offsets into t.bnd and their lengths (vrx_build_offsets);
+// the words follow in stage (e) (vrx_build_fill).
+static int stream_on_device(TiledStream& t, const TileRows& R, const TileShape& S, const TileLayout& L,
+                            VrxTileArgs A, int n_cu, hipStream_t s, double* balance_seconds) {
+    VRX_REQUIRE(R.nnz < (int64_t)UINT32_MAX, "tiled stream: more than 2^32 - 1 entries");
+    DevBuf<int32_t> d_rowmap, d_vptr, d_vrow, rlen, d_too;
+    DevBuf<uint32_t> seg_lo, seg_hi;  // entry offsets (< 2^32: device_build's limit)
+    DevBuf<int64_t> d_wlen;
+    VRX_HIP(d_rowmap.upload(L.rowmap.data(), L.rowmap.size(), s));
+    VRX_HIP(d_vptr.upload(L.vptr.data(), L.vptr.size(), s));
+    VRX_HIP(d_vrow.upload(L.vrow_row.data(), L.vrow_row.size(), s));
+    A.rowmap = d_rowmap.p;
+    A.vptr = d_vptr.p;
+    A.vrow_row = d_vrow.p;
+    BalancedRows B;
+    if (balance_applies(R, S, L)) {
+        const int rc = balance_slabs(R, S, L, d_vptr.p, s, B, balance_seconds);
+        if (rc) return rc;
+        A.idx = B.idx.p;
+        A.val = B.val.p;
+        if (L.split) {
+            A.ptr = B.ptr.p;
+            A.vptr = A.vrow_row = B.iota.p;
+        }
+        t.perm = std::move(B.perm);
     }
-    VRX_HIP(t.wave_start.upload(wave_start.data(), wave_start.size(), s));
-    VRX_HIP(t.bnd.upload(bnd.data(), bnd.size(), s));
-    VRX_HIP(t.rowmap.upload(rowmap.data(), rowmap.size(), s));
-    if (t.split) {
-        VRX_HIP(t.vptr.upload(vptr.data(), vptr.size(), s));
-        VRX_HIP(t.split_rows.upload(split_rows.data(), split_rows.size(), s));
-    }
+    const int64_t n_wave = A.n_wave, nsr = (int64_t)A.n_slab * A.NR * A.PH, per_wave = nsr + 1;
+    const int64_t n_pos = n_wave * A.n_slab * A.RW;
+    VRX_REQUIRE(n_pos < INT32_MAX * (int64_t)VRX_BLOCK, "tiled stream: too many segments");
+    VRX_HIP(seg_lo.alloc((size_t)n_pos));
+    VRX_HIP(seg_hi.alloc((size_t)n_pos));
+    VRX_HIP(rlen.alloc((size_t)(n_wave * nsr)));
+    VRX_HIP(d_too.alloc(1));
+    VRX_HIP(hipMemsetAsync(d_too.p, 0, sizeof(int32_t), s));
+    VRX_HIP(t.bnd.alloc((size_t)(n_wave * per_wave)));
+    VRX_HIP(d_wlen.alloc((size_t)n_wave));
+    vrx_build_count<<<(unsigned)((n_pos + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(A, seg_lo.p, seg_hi.p, rlen.p);
+    VRX_HIP(hipGetLastError());
+    vrx_build_offsets<<<(unsigned)((n_wave + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(A, rlen.p, t.bnd.p,
+                                                                                            d_wlen.p, d_too.p);
+    VRX_HIP(hipGetLastError());
+    std::vector<int64_t> wave_len((size_t)n_wave);
+    int32_t h_too = 0;
+    VRX_HIP(hipMemcpyAsync(wave_len.data(), d_wlen.p, (size_t)n_wave * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(&h_too, d_too.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
-    const int rc = plan_items(t, bnd.data(), n_wave, NR * PH, n_cu, rowmap.data(), mode, s);
+    if (h_too) {
+        vrx_set_error("tiled stream: wave stream >= 2^31 words");
+        return VRX_ERR_UNSUPPORTED;
+    }
+    std::vector<int32_t> bnd((size_t)(n_wave * per_wave));
+    return finish_stream(t, S, L, A, wave_len, bnd, true, n_cu, R.nnz, s,
+                         [&](int64_t, const std::vector<int64_t>&) {
+        const int64_t n_fill = n_wave * nsr * (A.G / 2);
+        VRX_REQUIRE(n_fill < INT32_MAX * (int64_t)VRX_BLOCK, "tiled stream: too many rounds");
+        vrx_build_fill<<<(unsigned)((n_fill + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
+            A, seg_lo.p, seg_hi.p, rlen.p, t.bnd.p, t.wave_start.p, t.ent.p);
+        VRX_HIP(hipGetLastError());
+        return VRX_OK;
+    });
+}
+
+// One orientation's tiled stream: (a) the layout, then on the host (c) the walk, or on the device (b) balanced
+// slabs where they apply and (d) the count, and (e) the shared finish.  All or nothing: o.tiled becomes the
+// new stream only when it is ready; a stream the guard rejects, or a failed build, leaves a default (not
+// ready, unbalanced) TiledStream.  *balance_seconds: what stage (b) took (untouched without it).
+static int build_tiled(Orient& o, const TileRows& R, const TileShape& S, int n_cu, hipStream_t s,
+                       double* balance_seconds = nullptr) {
+    o.tiled = TiledStream();
+    TileLayout L;
+    int rc = tile_layout(L, R, S, n_cu);
     if (rc) return rc;
-    t.ready = true;
-    return VRX_OK;
+    TiledStream t;
+    t.virt = R.virt;
+    t.n_contract = R.n_contract;
+    t.form = S.form;
+    t.rw = S.RW;
+    t.slab_rows = L.slab_rows;
+    t.n_slab = L.n_slab;
+    t.n_tile = L.n_tile;
+    t.n_vrows = L.n_vrows;
+    t.split = L.split;
+    t.n_split = (int64_t)L.split_rows.size();
+    const VrxTileArgs A = tile_args(R, S, L);
+    double sec = 0.0;
+    rc = R.dev.ptr ? stream_on_device(t, R, S, L, A, n_cu, s, &sec) : stream_on_host(t, R, S, L, A, n_cu, s);
+    if (balance_seconds) *balance_seconds = sec;
+    if (rc == VRX_OK && t.ready) o.tiled = std::move(t);
+    return rc;
 }
 
 // Rows per wave of the cell pass.  The (tile, slab) visits of a pass are dealt to one workgroup
@@ -1212,20 +1204,11 @@ struct StreamForms {
     bool auto_pair;  // pairs chosen by the estimate: fall back to AD/BD when a count is >= 2048
 };
 static StreamForms pick_forms(int64_t nnz, const int32_t* ad, const int32_t* dp) {
-    auto chunks = [](int64_t v) {
-        int n = 0;
-        while (v > 0) {
-            const int len = 64 - __builtin_clzll((uint64_t)v), sh = std::max(0, len - 3);
-            v -= (v >> sh) << sh;
-            ++n;
-        }
-        return n;
-    };
     int64_t words = 0, seen = 0;
     for (int64_t e = 0; e < nnz; e += 61) {
         const int64_t a = ad[e], d = dp[e];
         if (a < 0 || d < a) continue;  // (rejected by the validation that follows)
-        words += chunks(a) + chunks(d - a);
+        words += vrx_form1_words(a) + vrx_form1_words(d - a);
         ++seen;
     }
     const double wpe = seen ? (double)words / (double)seen : 1.0;
@@ -1237,89 +1220,70 @@ static StreamForms pick_forms(int64_t nnz, const int32_t* ad, const int32_t* dp)
     return f;
 }
 
-// Large problems: everything from the merged CSC arrays onwards happens on the device
-// (vrx_build.h).  *built = false means "not applicable here" (small problem, counts the pair
-// words cannot hold, a stream the padding guard rejects): the caller then runs the host builder.
-static int device_build(vrx_problem* p, const int64_t* colptr, const int32_t* rowidx,
-                        const int32_t* ad, const int32_t* dp, int rw_cell, int slab_cell, int slab_var,
-                        StreamForms forms, bool guard, bool* built) {
-    *built = false;
+// once the largest count is known: the estimate chose pair words but a count does not fit their 11 bits --
+// AD/BD words after all
+static StreamForms settle_forms(StreamForms f, int32_t max_count) {
+    return max_count >= 2048 && f.auto_pair ? StreamForms{1, 3, false} : f;
+}
+
+// narrowest entry format that holds the counts and the contracted index (VIREO_ENTRY_FMT may only widen it)
+static int pick_fmt(int32_t max_count, int64_t n_contract) {
+    int f = VRX_FMT_WIDE;
+    if (max_count < (1 << 16)) f = VRX_FMT_P64;
+    if (max_count < 64 && n_contract <= (1 << 20)) f = VRX_FMT_P32;
+    const int forced = env_int("VIREO_ENTRY_FMT", -1);
+    return forced >= f && forced <= VRX_FMT_WIDE ? forced : f;
+}
+
+// what both builders' validations report: kind 1 = colptr, 3 = a negative count, else the row indices
+static int input_error(int kind, int64_t col) {
+    if (kind == 1)
+        vrx_set_error("vrx_problem_create: colptr not monotone at column %lld", (long long)col);
+    else if (kind == 3)
+        vrx_set_error("vrx_problem_create: negative count in column %lld", (long long)col);
+    else
+        vrx_set_error("vrx_problem_create: row indices of column %lld not strictly increasing / out of range",
+                      (long long)col);
+    return VRX_ERR_ARG;
+}
+
+// What problem_create2 settles for both builders: the stream forms the counts suggest, VIREO_LDS (0 / 1: the
+// LDS-resident passes off / on, 1 without the padding guard), the sizes from which they pay off, slab heights
+struct BuildPlan {
+    StreamForms forms;
+    int lds;
+    int64_t min_nnz_cell, min_nnz_var;
+    int slab_cell, slab_var;
+};
+
+// The device builder's copy of the input: the merged CSC arrays, validated, and the variant-major rows
+// transposed from them (+ the row pointer on the host)
+struct DeviceInput {
+    DevBuf<int64_t> colptr, rptr;
+    DevBuf<int32_t> row, ad, dp, ecol, ridx;
+    DevBuf<int2> cval, rval;
+    std::vector<int64_t> h_rptr;
+};
+
+// upload + validation (vrx_build_validate): p->n_vars and the largest count
+static int upload_validate(vrx_problem* p, const int64_t* colptr, const int32_t* rowidx, const int32_t* ad,
+                           const int32_t* dp, DeviceInput& D, int32_t* max_count) {
     const int64_t nnz = p->nnz, n_var = p->n_var, n_cell = p->n_cell;
     hipStream_t s = p->stream;
-    // Entry ids travel through the transposition as 32-bit sort values and the tiled builder keeps
-    // segment bounds as 32-bit entry offsets: up to 2^32 - 1 entries (r6: was 2^31 - 1, and the slow
-    // host builder took over without a word; 2.2e9 entries are built here in seconds,
-    // profiles/r06_big_probe_*.txt).  Beyond that the host builder below is the path.
-    if (nnz <= 0 || nnz >= (int64_t)UINT32_MAX - 4096) return VRX_OK;
     for (int64_t c = 0; c < n_cell; ++c)
-        if (colptr[c + 1] < colptr[c]) {
-            vrx_set_error("vrx_problem_create: colptr not monotone at column %lld", (long long)c);
-            return VRX_ERR_ARG;
-        }
-    const bool timing = env_int("VIREO_BUILD_TIMING", 0) != 0;
-    auto wall = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double lap_t = wall();
-    auto lap = [&](const char* what) {  // (VIREO_BUILD_TIMING=1: where a device build spends its wall clock)
-        if (!timing) return;
-        (void)hipStreamSynchronize(s);
-        const double t1 = wall();
-        fprintf(stderr, "[vrx build] device_build: %-36s %.3f s\n", what, t1 - lap_t);
-        lap_t = t1;
-    };
-    struct JoinGuard {  // (an early return must not leave a helper thread running on dying buffers)
-        std::thread& t;
-        ~JoinGuard() {
-            if (t.joinable()) t.join();
-        }
-    };
-    // Balanced slabs: the cell orientation's layout and greedy need nothing but the caller's arrays -- they
-    // run on a helper thread (and its own pool of host threads) from here on, beside the upload, the
-    // validation and the transposition on the device.  Used by build_tiled if the layout it asks for is
-    // this one (a count >= 2048 can still change the stream form below; then it is simply recomputed).
-    TileLayout cell_layout;
-    std::thread early;
-    // (only where the greedy runs on host threads, VIREO_BALANCE_GREEDY=host: by default it runs on the device)
-    const char* greedy_mode = getenv("VIREO_BALANCE_GREEDY");
-    const bool host_greedy = greedy_mode && !strcmp(greedy_mode, "host");
-    if (p->want_balance && host_greedy && forms.cell == 1 && env_int("VIREO_BALANCE_EARLY", 1) != 0) {
-        const int rw0 = rw_cell, form0 = forms.cell;
-        early = std::thread([&, rw0, form0] {
-          try {
-            const auto t0 = std::chrono::steady_clock::now();
-            TileLayout& L = cell_layout;
-            if (tile_layout(L, colptr, n_cell, n_var, nnz, rw0, slab_cell, form0, p->n_cu) != VRX_OK) {
-                L.ptr = nullptr;  // (matches nothing: build_tiled computes -- and reports -- by itself)
-                return;
-            }
-            if (!host_balance_applies(L)) return;
-            std::vector<uint8_t> words;
-            if (!host_words(HostCounts{rowidx, ad, dp}, nnz, n_var, words)) return;  // (the validation will say why)
-            greedy_tiles(L, false, colptr, rowidx, words.data(), n_cell, L.posmap, L.perm, L.tile_of_row);
-            L.greedy_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            L.greedy_done = true;
-          } catch (const std::exception&) {  // (out of memory: build_tiled computes -- or fails -- by itself)
-            cell_layout.ptr = nullptr;
-            cell_layout.greedy_done = false;
-          }
-        });
-    }
-    JoinGuard early_guard{early};
-    DevBuf<int64_t> d_colptr, d_rptr;
-    DevBuf<int32_t> d_row, d_ad, d_dp, d_ecol, d_nvars, d_status, d_ridx;
-    DevBuf<int2> d_cval, d_rval;
-    DevBuf<uint32_t> keys_in, keys_out, vals_in, vals_out;
-    VRX_HIP(d_colptr.upload(colptr, (size_t)n_cell + 1, s));
-    VRX_HIP(d_row.upload(rowidx, (size_t)nnz, s));
-    VRX_HIP(d_ad.upload(ad, (size_t)nnz, s));
-    VRX_HIP(d_dp.upload(dp, (size_t)nnz, s));
-    VRX_HIP(d_ecol.alloc((size_t)nnz));
+        if (colptr[c + 1] < colptr[c]) return input_error(1, c);
+    DevBuf<int32_t> d_nvars, d_status;
+    VRX_HIP(D.colptr.upload(colptr, (size_t)n_cell + 1, s));
+    VRX_HIP(D.row.upload(rowidx, (size_t)nnz, s));
+    VRX_HIP(D.ad.upload(ad, (size_t)nnz, s));
+    VRX_HIP(D.dp.upload(dp, (size_t)nnz, s));
+    VRX_HIP(D.ecol.alloc((size_t)nnz));
     VRX_HIP(d_nvars.alloc((size_t)n_cell));
     VRX_HIP(hipMemsetAsync(d_nvars.p, 0, (size_t)n_cell * sizeof(int32_t), s));
     const int32_t st0[3] = {INT32_MAX, 0, 0};
     VRX_HIP(d_status.upload(st0, 3, s));
-    const unsigned nb = (unsigned)((nnz + VRX_BLOCK - 1) / VRX_BLOCK);
-    vrx_build_validate<<<nb, VRX_BLOCK, 0, s>>>(nnz, n_var, n_cell, d_colptr.p, d_row.p, d_ad.p, d_dp.p,
-                                                d_ecol.p, d_nvars.p, d_status.p);
+    vrx_build_validate<<<(unsigned)((nnz + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
+        nnz, n_var, n_cell, D.colptr.p, D.row.p, D.ad.p, D.dp.p, D.ecol.p, d_nvars.p, d_status.p);
     VRX_HIP(hipGetLastError());
     int32_t st[3];
     p->n_vars.assign((size_t)n_cell, 0);
@@ -1327,35 +1291,26 @@ static int device_build(vrx_problem* p, const int64_t* colptr, const int32_t* ro
     VRX_HIP(hipMemcpyAsync(p->n_vars.data(), d_nvars.p, (size_t)n_cell * sizeof(int32_t),
                            hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
-    if (st[0] != INT32_MAX) {
-        if (st[1] == 3)
-            vrx_set_error("vrx_problem_create: negative count in column %lld", (long long)st[0]);
-        else
-            vrx_set_error("vrx_problem_create: row indices of column %lld not strictly "
-                          "increasing / out of range", (long long)st[0]);
-        return VRX_ERR_ARG;
-    }
-    const int32_t max_count = st[2];
-    if (max_count >= 2048 && forms.auto_pair) {
-        // the estimate chose pair words but a count does not fit them: AD/BD words after all, and
-        // the cell tile height that belongs to THAT form (the caller picked rw_cell for pairs)
-        forms = StreamForms{1, 3, false};
-        rw_cell = pick_rw_cell(n_var, n_cell, p->n_cu, forms.cell);
-    }
-    const int var_form = forms.var, cell_form = forms.cell;
-    // (pair words hold 11-bit counts; a forced pair form leaves such data to the host builder)
-    if ((var_form < 2 || cell_form != 1) && max_count >= 2048) return VRX_OK;
-    lap("upload + validate");
-    // ---- transposition: stable sort of (variant, entry) ---------------------------------------
+    if (st[0] != INT32_MAX) return input_error(st[1], st[0]);
+    *max_count = st[2];
+    return VRX_OK;
+}
+
+// transposition (stable radix sort of (variant, entry)) and the packed entry arrays of both orientations (no
+// segment tables: the LDS-resident passes serve every K)
+static int transpose_pack(vrx_problem* p, DeviceInput& D, int32_t max_count) {
+    const int64_t nnz = p->nnz, n_var = p->n_var, n_cell = p->n_cell;
+    hipStream_t s = p->stream;
+    const unsigned nb = (unsigned)((nnz + VRX_BLOCK - 1) / VRX_BLOCK);
+    DevBuf<uint32_t> keys_in, keys_out, vals_in, vals_out;
     VRX_HIP(keys_in.alloc((size_t)nnz));
     VRX_HIP(keys_out.alloc((size_t)nnz));
     VRX_HIP(vals_in.alloc((size_t)nnz));
     VRX_HIP(vals_out.alloc((size_t)nnz));
-    vrx_build_iota_keys<<<nb, VRX_BLOCK, 0, s>>>(nnz, d_row.p, keys_in.p, vals_in.p);
+    vrx_build_iota_keys<<<nb, VRX_BLOCK, 0, s>>>(nnz, D.row.p, keys_in.p, vals_in.p);
     VRX_HIP(hipGetLastError());
-    int bits = 1;
-    while (((int64_t)1 << bits) < n_var) ++bits;
     {
+        const int bits = bits_for(n_var);
         size_t tmp_bytes = 0;
         VRX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys_in.p, keys_out.p, vals_in.p,
                                                    vals_out.p, (size_t)nnz, 0, bits, s));
@@ -1367,39 +1322,29 @@ static int device_build(vrx_problem* p, const int64_t* colptr, const int32_t* ro
     }
     keys_in.release();
     vals_in.release();
-    VRX_HIP(d_rptr.alloc((size_t)n_var + 1));
+    VRX_HIP(D.rptr.alloc((size_t)n_var + 1));
     vrx_build_rptr<<<(unsigned)((n_var + 1 + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
-        n_var, nnz, keys_out.p, d_rptr.p);
+        n_var, nnz, keys_out.p, D.rptr.p);
     VRX_HIP(hipGetLastError());
-    VRX_HIP(d_ridx.alloc((size_t)nnz));
-    VRX_HIP(d_rval.alloc((size_t)nnz));
-    VRX_HIP(d_cval.alloc((size_t)nnz));
-    vrx_build_gather<<<nb, VRX_BLOCK, 0, s>>>(nnz, vals_out.p, d_ecol.p, d_ad.p, d_dp.p, d_ridx.p,
-                                              d_rval.p, d_cval.p);
+    VRX_HIP(D.ridx.alloc((size_t)nnz));
+    VRX_HIP(D.rval.alloc((size_t)nnz));
+    VRX_HIP(D.cval.alloc((size_t)nnz));
+    vrx_build_gather<<<nb, VRX_BLOCK, 0, s>>>(nnz, vals_out.p, D.ecol.p, D.ad.p, D.dp.p, D.ridx.p,
+                                              D.rval.p, D.cval.p);
     VRX_HIP(hipGetLastError());
-    std::vector<int64_t> rptr((size_t)n_var + 1);
-    VRX_HIP(hipMemcpyAsync(rptr.data(), d_rptr.p, rptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    D.h_rptr.resize((size_t)n_var + 1);
+    VRX_HIP(hipMemcpyAsync(D.h_rptr.data(), D.rptr.p, D.h_rptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
     keys_out.release();
     vals_out.release();
-    d_ecol.release();
-    d_ad.release();
-    d_dp.release();
-    // ---- the packed entry arrays of both orientations (no segment tables: the LDS-resident
-    //      passes below serve every K) ------------------------------------------------------------
-    auto pick_fmt = [&](int64_t n_contract) {
-        int f = VRX_FMT_WIDE;
-        if (max_count < (1 << 16)) f = VRX_FMT_P64;
-        if (max_count < 64 && n_contract <= (1 << 20)) f = VRX_FMT_P32;
-        const int forced = env_int("VIREO_ENTRY_FMT", -1);
-        return forced >= f && forced <= VRX_FMT_WIDE ? forced : f;
-    };
-    auto set_orient = [&](Orient& o, int64_t n_rows, int64_t n_contract, const int32_t* d_idx,
-                          const int2* d_val) {
+    D.ecol.release();
+    D.ad.release();
+    D.dp.release();
+    auto pack = [&](Orient& o, int64_t n_rows, int64_t n_contract, const int32_t* d_idx, const int2* d_val) {
         o.n_rows = n_rows;
         o.n_contract = n_contract;
         o.nnz = nnz;
-        o.fmt = pick_fmt(n_contract);
+        o.fmt = pick_fmt(max_count, n_contract);
         o.n_tiles = 1;
         o.n_seg = 0;
         o.n_multi = o.n_slots = 0;
@@ -1409,93 +1354,59 @@ static int device_build(vrx_problem* p, const int64_t* colptr, const int32_t* ro
         return VRX_OK;
     };
     int rc;
-    if ((rc = set_orient(p->by_cell, n_cell, n_var, d_row.p, d_cval.p))) return rc;
-    if ((rc = set_orient(p->by_var, n_var, n_cell, d_ridx.p, d_rval.p))) return rc;
-    const DevRows cell_rows{d_colptr.p, d_row.p, d_cval.p}, var_rows{d_rptr.p, d_ridx.p, d_rval.p};
-    p->by_cell.tiled.want_balance = p->by_var.tiled.want_balance = p->want_balance;
-    lap("transposition");
-    // the variant pass on virtual rows (vrx_build.h): derived FIRST, so that -- balanced slabs -- their
-    // indices and word counts can travel to the host on a second stream while the host balances the cell
-    // orientation (the greedy of vrx_balance_tile reads both orientations' entries on the host)
-    DevBuf<int64_t> d_cnt, d_vptr2;
-    DevBuf<int32_t> d_vidx;
-    DevBuf<int2> d_vval;
-    std::vector<int64_t> vptr2;
-    int64_t vnnz = 0;
-    std::vector<int32_t> hv_idx;
-    std::vector<uint8_t> hv_words;
-    std::thread helper;
-    hipError_t helper_err = hipSuccess;
-    if (var_form == 3) {
-        VRX_HIP(d_cnt.alloc((size_t)(2 * n_var)));
-        const unsigned nbv = (unsigned)((n_var + VRX_BLOCK - 1) / VRX_BLOCK);
-        vrx_virt_count<<<nbv, VRX_BLOCK, 0, s>>>(n_var, d_rptr.p, d_ridx.p, d_rval.p, d_cnt.p);
-        VRX_HIP(hipGetLastError());
-        vptr2.assign((size_t)(2 * n_var + 1), 0);
-        VRX_HIP(hipMemcpyAsync(vptr2.data() + 1, d_cnt.p, (size_t)(2 * n_var) * sizeof(int64_t),
-                               hipMemcpyDeviceToHost, s));
-        VRX_HIP(hipStreamSynchronize(s));
-        for (int64_t r = 0; r < 2 * n_var; ++r) vptr2[(size_t)r + 1] += vptr2[(size_t)r];
-        vnnz = vptr2[(size_t)(2 * n_var)];
-        VRX_HIP(d_vptr2.upload(vptr2.data(), vptr2.size(), s));
-        VRX_HIP(d_vidx.alloc((size_t)std::max<int64_t>(vnnz, 1)));
-        VRX_HIP(d_vval.alloc((size_t)std::max<int64_t>(vnnz, 1)));
-        vrx_virt_fill<<<nbv, VRX_BLOCK, 0, s>>>(n_var, d_rptr.p, d_ridx.p, d_rval.p, d_vptr2.p, d_vidx.p,
-                                                d_vval.p);
-        VRX_HIP(hipGetLastError());
-        if (p->want_balance && host_greedy && vnnz > 0) {
-            VRX_HIP(hipStreamSynchronize(s));
-            hv_idx.resize((size_t)vnnz);
-            hv_words.resize((size_t)vnnz);
-            const int dev_id = p->device;
-            helper = std::thread([&, dev_id] {
-                hipStream_t s2 = nullptr;
-                DevBuf<uint8_t> d_words;
-                auto ok = [&](hipError_t e) {
-                    if (e != hipSuccess && helper_err == hipSuccess) helper_err = e;
-                    return e == hipSuccess;
-                };
-                if (ok(hipSetDevice(dev_id)) && ok(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking)) &&
-                    ok(d_words.alloc((size_t)vnnz))) {
-                    vrx_build_words<<<(unsigned)((vnnz + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s2>>>(vnnz, d_vval.p, d_words.p);
-                    ok(hipGetLastError());
-                    ok(hipMemcpyAsync(hv_idx.data(), d_vidx.p, (size_t)vnnz * sizeof(int32_t), hipMemcpyDeviceToHost, s2));
-                    ok(hipMemcpyAsync(hv_words.data(), d_words.p, (size_t)vnnz, hipMemcpyDeviceToHost, s2));
-                    ok(hipStreamSynchronize(s2));
-                }
-                if (s2) (void)hipStreamDestroy(s2);
-            });
-        }
-    }
-    JoinGuard join_guard{helper};
-    lap("virtual rows");
-    // The two orientations' streams are independent from here on: the variant orientation is built by a second
-    // host thread on a stream of its own while this one builds the cell orientation (their host halves --
-    // layout, work list -- and their device halves -- the greedy of balanced slabs is a latency-bound kernel on
-    // half the CUs -- overlap).  Not for problems whose two sets of transient buffers would not fit together.
+    if ((rc = pack(p->by_cell, n_cell, n_var, D.row.p, D.cval.p))) return rc;
+    return pack(p->by_var, n_var, n_cell, D.ridx.p, D.rval.p);
+}
+
+// The variant pass on virtual rows (vrx_build.h, vrx_virt_count / vrx_virt_fill): their row pointer on both
+// sides, their entries on the device
+struct VirtualRows {
+    DevBuf<int64_t> ptr;
+    DevBuf<int32_t> idx;
+    DevBuf<int2> val;
+    std::vector<int64_t> h_ptr;
+    int64_t nnz = 0;
+};
+
+static int virtual_rows(const vrx_problem* p, const DeviceInput& D, VirtualRows& V) {
+    const int64_t n_var = p->n_var;
+    hipStream_t s = p->stream;
+    DevBuf<int64_t> d_cnt;
+    VRX_HIP(d_cnt.alloc((size_t)(2 * n_var)));
+    const unsigned nbv = (unsigned)((n_var + VRX_BLOCK - 1) / VRX_BLOCK);
+    vrx_virt_count<<<nbv, VRX_BLOCK, 0, s>>>(n_var, D.rptr.p, D.ridx.p, D.rval.p, d_cnt.p);
+    VRX_HIP(hipGetLastError());
+    V.h_ptr.assign((size_t)(2 * n_var + 1), 0);
+    VRX_HIP(hipMemcpyAsync(V.h_ptr.data() + 1, d_cnt.p, (size_t)(2 * n_var) * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    for (int64_t r = 0; r < 2 * n_var; ++r) V.h_ptr[(size_t)r + 1] += V.h_ptr[(size_t)r];
+    V.nnz = V.h_ptr[(size_t)(2 * n_var)];
+    VRX_HIP(V.ptr.upload(V.h_ptr.data(), V.h_ptr.size(), s));
+    VRX_HIP(V.idx.alloc((size_t)std::max<int64_t>(V.nnz, 1)));
+    VRX_HIP(V.val.alloc((size_t)std::max<int64_t>(V.nnz, 1)));
+    vrx_virt_fill<<<nbv, VRX_BLOCK, 0, s>>>(n_var, D.rptr.p, D.ridx.p, D.rval.p, V.ptr.p, V.idx.p, V.val.p);
+    VRX_HIP(hipGetLastError());
+    return VRX_OK;
+}
+
+// The two orientations' streams are independent: the variant orientation is built by a second host thread on
+// a stream of its own while this one builds the cell orientation (their host halves -- layout, work list --
+// and their device halves -- the greedy of balanced slabs is a latency-bound kernel on half the CUs --
+// overlap).  Not for problems whose two sets of transient buffers would not fit together.
+static int build_both_streams(vrx_problem* p, const TileRows& cell_rows, const TileShape& cell_shape,
+                              const TileRows& var_rows, const TileShape& var_shape, LapTimer& lap,
+                              double* balance_seconds) {
+    hipStream_t s = p->stream;
+    double sec_cell = 0.0, sec_var = 0.0;
     auto build_var = [&](hipStream_t sv) -> int {
-        int rcv;
-        if (var_form == 3) {
-            if (helper.joinable()) helper.join();
-            if (helper_err != hipSuccess) {
-                vrx_set_error("balanced slabs: download of the variant rows failed: %s", hipGetErrorString(helper_err));
-                return VRX_ERR_HIP;
-            }
-            const HostWords virt_host{hv_idx.data(), hv_words.data()};
-            const DevRows virt_rows{d_vptr2.p, d_vidx.p, d_vval.p};
-            rcv = build_tiled(p->by_var, vptr2.data(), nullptr, nullptr, VRX_LDS_RW_CELL, VRX_LDS_SLAB_BYTES / 256,
-                              guard, 1, 0, sv, p->n_cu, &virt_rows, 2 * n_var, (n_cell + 1) / 2, vnnz, nullptr,
-                              hv_idx.empty() ? nullptr : &virt_host);
-        } else {
-            rcv = build_tiled(p->by_var, rptr.data(), nullptr, nullptr, VRX_LDS_RW_VARIANT, slab_var, guard,
-                              var_form == 2 ? 2 : 0, 0, sv, p->n_cu, &var_rows);
-        }
+        const int rcv = build_tiled(p->by_var, var_rows, var_shape, p->n_cu, sv, &sec_var);
         if (rcv) return rcv;
         return hipStreamSynchronize(sv) == hipSuccess ? VRX_OK : VRX_ERR_HIP;
     };
     VRX_HIP(hipStreamSynchronize(s));  // (the rows both builds read are complete)
     const bool concurrent = env_int("VIREO_BUILD_CONCURRENT", 1) != 0 &&
-                            nnz < (int64_t)env_int("VIREO_BUILD_CONCURRENT_MAX_MNNZ", 1000) * 1000000;
+                            p->nnz < (int64_t)env_int("VIREO_BUILD_CONCURRENT_MAX_MNNZ", 1000) * 1000000;
     std::thread var_thread;
     int rc_var = VRX_OK;
     std::string err_var;
@@ -1524,11 +1435,13 @@ static int device_build(vrx_problem* p, const int64_t* colptr, const int32_t* ro
             }
         });
     }
-    JoinGuard var_guard{var_thread};
-    const HostCounts cell_host{rowidx, ad, dp};
-    if (early.joinable()) early.join();
-    rc = build_tiled(p->by_cell, colptr, nullptr, nullptr, rw_cell, slab_cell, guard, cell_form, 1, s,
-                     p->n_cu, &cell_rows, -1, -1, -1, &cell_host, nullptr, &cell_layout);
+    struct JoinGuard {  // (an early return must not leave the thread running on dying buffers)
+        std::thread& t;
+        ~JoinGuard() {
+            if (t.joinable()) t.join();
+        }
+    } var_guard{var_thread};
+    const int rc = build_tiled(p->by_cell, cell_rows, cell_shape, p->n_cu, s, &sec_cell);
     lap("cell stream");
     if (concurrent) {
         var_thread.join();
@@ -1543,22 +1456,57 @@ static int device_build(vrx_problem* p, const int64_t* colptr, const int32_t* ro
     }
     if (rc_var) return rc_var;
     VRX_HIP(hipStreamSynchronize(s));
+    *balance_seconds = sec_cell + sec_var;
+    return VRX_OK;
+}
+
+// Large problems: everything from the merged CSC arrays onwards happens on the device
+// (vrx_build.h).  *built = false means "not applicable here" (small problem, counts the pair
+// words cannot hold, a stream the padding guard rejects): the caller then runs the host builder
+// on a problem with both orientations as new.
+static int device_build(vrx_problem* p, const int64_t* colptr, const int32_t* rowidx, const int32_t* ad,
+                        const int32_t* dp, const BuildPlan& plan, bool* built) {
+    *built = false;
+    const int64_t nnz = p->nnz, n_var = p->n_var, n_cell = p->n_cell;
+    // Entry ids travel through the transposition as 32-bit sort values and the tiled builder keeps
+    // segment bounds as 32-bit entry offsets: up to 2^32 - 1 entries (r6: was 2^31 - 1, and the slow
+    // host builder took over without a word; 2.2e9 entries are built here in seconds,
+    // profiles/r06_big_probe_*.txt).  Beyond that the host builder below is the path.
+    if (nnz <= 0 || nnz >= (int64_t)UINT32_MAX - 4096) return VRX_OK;
+    LapTimer lap{p->stream, "device_build:", 36};
+    DeviceInput D;
+    int32_t max_count = 0;
+    int rc = upload_validate(p, colptr, rowidx, ad, dp, D, &max_count);
+    if (rc) return rc;
+    const StreamForms forms = settle_forms(plan.forms, max_count);
+    const int var_form = forms.var, cell_form = forms.cell;
+    const bool guard = plan.lds != 1;
+    // (pair words hold 11-bit counts; a forced pair form leaves such data to the host builder)
+    if ((var_form < 2 || cell_form != 1) && max_count >= 2048) return VRX_OK;
+    lap("upload + validate");
+    if ((rc = transpose_pack(p, D, max_count))) return rc;
+    lap("transposition");
+    VirtualRows V;
+    if (var_form == 3 && (rc = virtual_rows(p, D, V))) return rc;
+    lap("virtual rows");
+    const TileRows cell_rows{colptr, nullptr, nullptr, {D.colptr.p, D.row.p, D.cval.p}, n_cell, n_var, nnz, false};
+    const TileShape cell_shape{pick_rw_cell(n_var, n_cell, p->n_cu, cell_form), plan.slab_cell, cell_form, 1, guard,
+                               p->want_balance};
+    const TileRows var_rows = var_form == 3
+        ? TileRows{V.h_ptr.data(), nullptr, nullptr, {V.ptr.p, V.idx.p, V.val.p}, 2 * n_var, (n_cell + 1) / 2, V.nnz, true}
+        : TileRows{D.h_rptr.data(), nullptr, nullptr, {D.rptr.p, D.ridx.p, D.rval.p}, n_var, n_cell, nnz, false};
+    const TileShape var_shape = var_form == 3
+        ? TileShape{VRX_LDS_RW_CELL, VRX_LDS_SLAB_BYTES / 256, 1, 0, guard, p->want_balance}
+        : TileShape{VRX_LDS_RW_VARIANT, plan.slab_var, var_form == 2 ? 2 : 0, 0, guard, p->want_balance};
+    double balance_seconds = 0.0;
+    if ((rc = build_both_streams(p, cell_rows, cell_shape, var_rows, var_shape, lap, &balance_seconds))) return rc;
     if (!p->by_cell.tiled.ready || !p->by_var.tiled.ready) {  // rejected by the padding guard
-        for (Orient* o : {&p->by_cell, &p->by_var}) {
-            o->ent.release();
-            o->tiled.ent.release();
-            o->tiled.wave_start.release();
-            o->tiled.bnd.release();
-            o->tiled.rowmap.release();
-            o->tiled.vptr.release();
-            o->tiled.split_rows.release();
-            o->tiled.items.release();
-            o->tiled.wg_first.release();
-            o->tiled.npiece.release();
-            o->tiled.ready = false;
-        }
+        p->by_cell = Orient();
+        p->by_var = Orient();
         return VRX_OK;
     }
+    p->device_built = true;
+    p->balance_seconds = balance_seconds;
     *built = true;
     return VRX_OK;
 }
@@ -1589,6 +1537,9 @@ extern "C" int vrx_problem_create2(int device, int64_t n_var, int64_t n_cell, in
         return VRX_ERR_UNSUPPORTED;
     }
 }
+
+static int host_build(vrx_problem* p, const int64_t* colptr, const int32_t* rowidx, const int32_t* ad,
+                      const int32_t* dp, const BuildPlan& plan);
 
 static int problem_create2(int device, int64_t n_var, int64_t n_cell, int64_t nnz, const int64_t* colptr,
                            const int32_t* rowidx, const int32_t* ad, const int32_t* dp, int32_t flags,
@@ -1622,28 +1573,36 @@ static int problem_create2(int device, int64_t n_var, int64_t n_cell, int64_t nn
     // on the device; VIREO_BUILD=host keeps the host builder (the specification the device
     // build is tested against), VIREO_BUILD=device takes the device path whenever VIREO_LDS
     // allows the streams.
-    StreamForms forms = pick_forms(nnz, ad, dp);
-    {
-        const int lds0 = env_int("VIREO_LDS", -1);
-        const char* bm = getenv("VIREO_BUILD");
-        const bool force_dev = bm && !strcmp(bm, "device"), force_host = bm && !strcmp(bm, "host");
-        const bool big = nnz >= (int64_t)env_int("VIREO_LDS_MIN_NNZ", 4000000) &&
-                         nnz >= (int64_t)env_int("VIREO_LDS_MIN_NNZ_VAR", 32000000);
-        if (!force_host && lds0 != 0 && (force_dev || big)) {
-            bool built = false;
-            int rc = device_build(p.get(), colptr, rowidx, ad, dp, pick_rw_cell(n_var, n_cell, p->n_cu, forms.cell),
-                                  std::min(VRX_LDS_SLAB_BYTES / 256, std::max(16, env_int("VIREO_LDS_SLAB_CELL", VRX_LDS_SLAB_BYTES / 256))),
-                                  std::min(VRX_LDS_SLAB_BYTES / 128, std::max(16, env_int("VIREO_LDS_SLAB_VAR", VRX_LDS_SLAB_BYTES / 128))), forms,
-                                  lds0 != 1, &built);
-            if (rc) return rc;
-            if (built) {
-                p->balance_seconds = p->by_cell.tiled.balance_seconds + p->by_var.tiled.balance_seconds;
-                *out = p.release();
-                return VRX_OK;
-            }
+    BuildPlan plan;
+    plan.forms = pick_forms(nnz, ad, dp);
+    plan.lds = env_int("VIREO_LDS", -1);
+    plan.min_nnz_cell = env_int("VIREO_LDS_MIN_NNZ", 4000000);
+    plan.min_nnz_var = env_int("VIREO_LDS_MIN_NNZ_VAR", 32000000);
+    plan.slab_cell = std::min(VRX_LDS_SLAB_BYTES / 256, std::max(16, env_int("VIREO_LDS_SLAB_CELL", VRX_LDS_SLAB_BYTES / 256)));
+    plan.slab_var = std::min(VRX_LDS_SLAB_BYTES / 128, std::max(16, env_int("VIREO_LDS_SLAB_VAR", VRX_LDS_SLAB_BYTES / 128)));
+    const char* bm = getenv("VIREO_BUILD");
+    const bool force_dev = bm && !strcmp(bm, "device"), force_host = bm && !strcmp(bm, "host");
+    const bool big = nnz >= plan.min_nnz_cell && nnz >= plan.min_nnz_var;
+    int rc;
+    if (!force_host && plan.lds != 0 && (force_dev || big)) {
+        bool built = false;
+        if ((rc = device_build(p.get(), colptr, rowidx, ad, dp, plan, &built))) return rc;
+        if (built) {
+            *out = p.release();
+            return VRX_OK;
         }
     }
+    if ((rc = host_build(p.get(), colptr, rowidx, ad, dp, plan))) return rc;
+    *out = p.release();
+    return VRX_OK;
+}
 
+// The host builder (the specification the device builder is tested against): validation, transposition and
+// packing on host threads, gather tables of both orientations, and the tiled streams where VIREO_LDS and the
+// problem's size ask for them.
+static int host_build(vrx_problem* p, const int64_t* colptr, const int32_t* rowidx, const int32_t* ad,
+                      const int32_t* dp, const BuildPlan& plan) {
+    const int64_t nnz = p->nnz, n_var = p->n_var, n_cell = p->n_cell;
     // validate + interleave (ad, dp); count per-cell and per-variant entries.  Cells are cut
     // into one contiguous chunk per host thread; every thread keeps its own per-variant
     // histogram, which also gives it private write cursors for the transposition below
@@ -1687,21 +1646,7 @@ static int problem_create2(int device, int64_t n_var, int64_t n_cell, int64_t nn
     int32_t max_count = 0;
     for (int t = 0; t < nt; ++t) {
         max_count = std::max(max_count, tmax[(size_t)t]);
-        if (bad_kind[(size_t)t] == 1) {
-            vrx_set_error("vrx_problem_create: colptr not monotone at column %lld",
-                          (long long)bad_col[(size_t)t]);
-            return VRX_ERR_ARG;
-        }
-        if (bad_kind[(size_t)t] == 2) {
-            vrx_set_error("vrx_problem_create: row indices of column %lld not strictly "
-                          "increasing / out of range", (long long)bad_col[(size_t)t]);
-            return VRX_ERR_ARG;
-        }
-        if (bad_kind[(size_t)t] == 3) {
-            vrx_set_error("vrx_problem_create: negative count in column %lld",
-                          (long long)bad_col[(size_t)t]);
-            return VRX_ERR_ARG;
-        }
+        if (bad_kind[(size_t)t]) return input_error((int)bad_kind[(size_t)t], bad_col[(size_t)t]);
     }
     // rptr = exclusive scan of the per-variant totals; hist[t][r] becomes thread t's first
     // write position inside variant row r
@@ -1726,60 +1671,46 @@ static int problem_create2(int device, int64_t n_var, int64_t n_cell, int64_t nn
                 rval[(size_t)q] = cval[(size_t)e];
             }
     });
-    // narrowest entry format that holds the counts and the contracted index
-    auto pick_fmt = [&](int64_t n_contract) {
-        int f = VRX_FMT_WIDE;
-        if (max_count < (1 << 16)) f = VRX_FMT_P64;
-        if (max_count < 64 && n_contract <= (1 << 20)) f = VRX_FMT_P32;
-        const int forced = env_int("VIREO_ENTRY_FMT", -1);
-        return forced >= f && forced <= VRX_FMT_WIDE ? forced : f;  // may only widen
-    };
     const int tiles_c = pick_tiles(n_var, 256.0, "VIREO_TILES_CELL");   // W rows: 16 x 16 B
     const int tiles_v = pick_tiles(n_cell, 128.0, "VIREO_TILES_VAR");   // ID rows: 16 x 8 B
     int rc = build_orient(p->by_cell, n_cell, n_var, colptr, rowidx, cval.data(), rptr.data(),
-                          tiles_c, pick_fmt(n_var), p->stream);
+                          tiles_c, pick_fmt(max_count, n_var), p->stream);
     if (rc) return rc;
     rc = build_orient(p->by_var, n_var, n_cell, rptr.data(), ridx.data(), rval.data(), colptr,
-                      tiles_v, pick_fmt(n_cell), p->stream);
+                      tiles_v, pick_fmt(max_count, n_cell), p->stream);
     if (rc) return rc;
     // LDS-resident passes (vrx_spmm_lds) pay off on large problems (two-dimensional tiling,
     // one 160 KiB workgroup per CU); VIREO_LDS=0/1 forces them off/on.  Measured crossovers
     // against the gather kernels (K = 8 and 16): the cell pass wins from ~4 M non-zeros; the
     // variant pass (whose per-range partials also cost the theta kernel a wider read) only
     // ties at 8-16 M and wins clearly at 100 M.
-    const int lds = env_int("VIREO_LDS", -1);
-    if (max_count >= 2048 && forms.auto_pair) forms = StreamForms{1, 3, false};
-    const int cell_form = forms.cell;  // 1: AD/BD stream (any counts)
-    if ((max_count < 2048 || cell_form == 1) && lds != 0) {
+    const int lds = plan.lds;
+    const StreamForms f = settle_forms(plan.forms, max_count);
+    const int cell_form = f.cell, var_form = f.var;  // cell 1: AD/BD stream; variant 3: AD/BD virtual rows,
+    const bool pairs_fit = max_count < 2048;         // 2: AD/BD phases (any counts); else pairs (11-bit counts)
+    if ((pairs_fit || cell_form == 1) && lds != 0) {
         // cell pass: slabs of 512 W rows (128 KiB at K = 16); variant pass: 1024 ID rows
-        if (lds == 1 || nnz >= (int64_t)env_int("VIREO_LDS_MIN_NNZ", 4000000)) {
-            const int rw_cell = pick_rw_cell(n_var, n_cell, p->n_cu, cell_form);
-            if (cell_form == 1 || max_count < 2048) {
-                rc = build_tiled(p->by_cell, colptr, rowidx, cval.data(), rw_cell,
-                                 std::min(VRX_LDS_SLAB_BYTES / 256, std::max(16, env_int("VIREO_LDS_SLAB_CELL", VRX_LDS_SLAB_BYTES / 256))),
-                                 lds != 1, cell_form == 1 ? 1 : 0, 1, p->stream, p->n_cu);
-                if (rc) return rc;
-            }
+        if (lds == 1 || nnz >= plan.min_nnz_cell) {
+            const TileRows rows{colptr, rowidx, cval.data(), {}, n_cell, n_var, nnz, false};
+            const TileShape shape{pick_rw_cell(n_var, n_cell, p->n_cu, cell_form), plan.slab_cell, cell_form == 1 ? 1 : 0,
+                                  1, lds != 1, false};
+            if ((rc = build_tiled(p->by_cell, rows, shape, p->n_cu, p->stream))) return rc;
         }
-        const int var_form = forms.var;  // 3: AD / BD virtual rows, 2: AD / BD phases (any counts)
-        if (var_form == 3 && (lds == 1 || nnz >= (int64_t)env_int("VIREO_LDS_MIN_NNZ_VAR", 32000000))) {
+        if (var_form == 3 && (lds == 1 || nnz >= plan.min_nnz_var)) {
             std::vector<int64_t> vptr2;
             std::vector<int32_t> vidx;
             std::vector<int2> vval;
             derive_virtual_rows(n_var, rptr.data(), ridx.data(), rval.data(), vptr2, vidx, vval);
-            rc = build_tiled(p->by_var, vptr2.data(), vidx.data(), vval.data(), VRX_LDS_RW_CELL,
-                             VRX_LDS_SLAB_BYTES / 256, lds != 1, 1, 0, p->stream, p->n_cu, nullptr,
-                             2 * n_var, (n_cell + 1) / 2, (int64_t)vidx.size());
-            if (rc) return rc;
-        } else if ((var_form == 2 || max_count < 2048) &&
-            (lds == 1 || nnz >= (int64_t)env_int("VIREO_LDS_MIN_NNZ_VAR", 32000000))) {
-            rc = build_tiled(p->by_var, rptr.data(), ridx.data(), rval.data(), VRX_LDS_RW_VARIANT,
-                             std::min(VRX_LDS_SLAB_BYTES / 128, std::max(16, env_int("VIREO_LDS_SLAB_VAR", VRX_LDS_SLAB_BYTES / 128))),
-                             lds != 1, var_form == 2 ? 2 : 0, 0, p->stream, p->n_cu);
-            if (rc) return rc;
+            const TileRows rows{vptr2.data(), vidx.data(), vval.data(), {}, 2 * n_var, (n_cell + 1) / 2,
+                                (int64_t)vidx.size(), true};
+            const TileShape shape{VRX_LDS_RW_CELL, VRX_LDS_SLAB_BYTES / 256, 1, 0, lds != 1, false};
+            if ((rc = build_tiled(p->by_var, rows, shape, p->n_cu, p->stream))) return rc;
+        } else if ((var_form == 2 || pairs_fit) && (lds == 1 || nnz >= plan.min_nnz_var)) {
+            const TileRows rows{rptr.data(), ridx.data(), rval.data(), {}, n_var, n_cell, nnz, false};
+            const TileShape shape{VRX_LDS_RW_VARIANT, plan.slab_var, var_form == 2 ? 2 : 0, 0, lds != 1, false};
+            if ((rc = build_tiled(p->by_var, rows, shape, p->n_cu, p->stream))) return rc;
         }
     }
-    *out = p.release();
     return VRX_OK;
 }
 
@@ -1859,42 +1790,44 @@ extern "C" int vrx_problem_binom_const(vrx_problem* p, double* sum_out) {
     return VRX_OK;
 }
 
-// 64-bit FNV-1a of a device array (downloaded): tests compare the streams of the host and the
+// 64-bit FNV-1a of device arrays (downloaded), folded into *x: tests compare the streams of the host and the
 // device builder with it
+static constexpr uint64_t kFnvBasis = 1469598103934665603ull;
 template <class T>
-static int fnv_of(const DevBuf<T>& b, hipStream_t s, uint64_t* out) {
+static int fnv_fold(const DevBuf<T>& b, hipStream_t s, uint64_t* x) {
     std::vector<unsigned char> h(b.n * sizeof(T));
     if (!h.empty()) {
         VRX_HIP(hipMemcpyAsync(h.data(), b.p, h.size(), hipMemcpyDeviceToHost, s));
         VRX_HIP(hipStreamSynchronize(s));
     }
-    uint64_t x = 1469598103934665603ull;
-    for (unsigned char c : h) x = (x ^ c) * 1099511628211ull;
-    *out = x;
+    for (unsigned char c : h) *x = (*x ^ c) * 1099511628211ull;
     return VRX_OK;
 }
 
 extern "C" int vrx_problem_digest(vrx_problem* p, uint64_t* out12) {
     VRX_REQUIRE(p && out12, "vrx_problem_digest: null argument");
     VRX_HIP(hipSetDevice(p->device));
-    int rc, k = 0;
+    int rc;
+    for (int i = 0; i < 12; ++i) out12[i] = kFnvBasis;
+    uint64_t* x = out12;
     for (Orient* o : {&p->by_var, &p->by_cell}) {
-        if ((rc = fnv_of(o->ent, p->stream, out12 + k++))) return rc;
-        if ((rc = fnv_of(o->tiled.ent, p->stream, out12 + k++))) return rc;
-        if ((rc = fnv_of(o->tiled.bnd, p->stream, out12 + k++))) return rc;
-        if ((rc = fnv_of(o->tiled.wave_start, p->stream, out12 + k++))) return rc;
-        if ((rc = fnv_of(o->tiled.rowmap, p->stream, out12 + k++))) return rc;
-        out12[k++] = (uint64_t)o->n_seg;
+        if ((rc = fnv_fold(o->ent, p->stream, x++))) return rc;
+        if ((rc = fnv_fold(o->tiled.ent, p->stream, x++))) return rc;
+        if ((rc = fnv_fold(o->tiled.bnd, p->stream, x++))) return rc;
+        if ((rc = fnv_fold(o->tiled.wave_start, p->stream, x++))) return rc;
+        if ((rc = fnv_fold(o->tiled.rowmap, p->stream, x))) return rc;  // (+ the balanced slabs' permutation)
+        if ((rc = fnv_fold(o->tiled.perm, p->stream, x++))) return rc;
+        *x++ = (uint64_t)o->n_seg;
     }
     return VRX_OK;
 }
 
 extern "C" int vrx_problem_build_info(vrx_problem* p, double* info4) {
     VRX_REQUIRE(p && info4, "vrx_problem_build_info: null argument");
-    info4[0] = p->by_var.tiled.ready && p->by_var.tiled.balanced ? 1.0 : 0.0;
-    info4[1] = p->by_cell.tiled.ready && p->by_cell.tiled.balanced ? 1.0 : 0.0;
+    info4[0] = p->by_var.tiled.balanced() ? 1.0 : 0.0;
+    info4[1] = p->by_cell.tiled.balanced() ? 1.0 : 0.0;
     info4[2] = p->balance_seconds;
-    info4[3] = p->by_var.tiled.ready && p->by_cell.tiled.ready && p->by_var.n_seg == 0 ? 1.0 : 0.0;  // built on the device
+    info4[3] = p->device_built ? 1.0 : 0.0;
     return VRX_OK;
 }
 
@@ -2043,7 +1976,7 @@ static int prof_drain(vrx_model* m) {
 }
 
 template <int MODE>
-static bool lds_eligible(const Orient& o, int K);
+static bool lds_eligible(const vrx_problem& p, int K);
 
 extern "C" int vrx_model_create(vrx_problem* p, const vrx_model_cfg* cfg, vrx_model** out) {
     VRX_REQUIRE(p && cfg && out, "vrx_model_create: null argument");
@@ -2092,14 +2025,14 @@ extern "C" int vrx_model_create(vrx_problem* p, const vrx_model_cfg* cfg, vrx_mo
     VRX_HIP(m->PC.alloc((size_t)(p->by_cell.n_slots * m->Kt)));
     {
         const TiledStream &tv = p->by_var.tiled, &tc = p->by_cell.tiled;
-        if (lds_eligible<0>(p->by_var, m->Kt) && tv.virt)  // planar sums of the virtual rows
+        if (lds_eligible<0>(*p, m->Kt) && tv.virt)  // planar sums of the virtual rows
             VRX_HIP(m->RV.alloc((size_t)(tv.n_range * tv.n_vrows * m->Kt)));
-        else if (lds_eligible<0>(p->by_var, m->Kt) && (tv.n_range > 1 || tv.split))
+        else if (lds_eligible<0>(*p, m->Kt) && (tv.n_range > 1 || tv.split))
             VRX_HIP(m->RV.alloc((size_t)(tv.n_range * tv.n_vrows * m->Kt * 2)));
-        if (lds_eligible<1>(p->by_cell, m->Kt) && (tc.n_range > 1 || tc.split))
+        if (lds_eligible<1>(*p, m->Kt) && (tc.n_range > 1 || tc.split))
             VRX_HIP(m->RC.alloc((size_t)(tc.n_range * tc.n_vrows * m->Kt)));
     }
-    m->wform = lds_eligible<1>(p->by_cell, m->Kt) && p->by_cell.tiled.form == 1 ? 1 : 0;
+    m->wform = lds_eligible<1>(*p, m->Kt) && p->by_cell.tiled.form == 1 ? 1 : 0;
     // rows without entries are never written by the passes: zero once
     VRX_HIP(hipMemsetAsync(m->S.p, 0, (size_t)m->NKt * 2 * sizeof(double), s));
     VRX_HIP(hipMemsetAsync(m->LID.p, 0, (size_t)(m->M * m->Kt) * sizeof(double), s));
@@ -2548,11 +2481,12 @@ static void launch_spmm_fmt(const Orient& o, dim3 grid, hipStream_t s, const dou
 // LDS-resident pass: K <= 16 (4 columns per lane, the dense rows zero-padded to a multiple of
 // 4 columns in LDS), counts < 2048 (checked when the tiled stream is built)
 template <int MODE>
-static bool lds_eligible(const Orient& o, int K) {
+static bool lds_eligible(const vrx_problem& p, int K) {
     static const int mask = env_int("VIREO_LDS_PASS", 3);  // bit 0: variant pass, bit 1: cell pass
     static const int kmin = env_int("VIREO_LDS_MIN_K", 2);
     static const int kmax = env_int("VIREO_LDS_MAX_K", 1 << 20);  // > 16: column blocks of 16
-    if (o.tiled.ready && o.n_seg == 0) return true;  // (device-built: no gather tables)
+    const Orient& o = MODE == 0 ? p.by_var : p.by_cell;
+    if (p.device_built) return true;  // (no gather tables)
     return o.tiled.ready && (mask >> MODE & 1) && K <= kmax && K >= kmin;
 }
 
@@ -2635,7 +2569,7 @@ static int launch_lds_one(const Orient& o, hipStream_t s, const double* X, int K
                                      t.wg_first.p, t.n_slab,
                                      t.slab_rows, t.n_contract, t.n_vrows,
                                      X + (size_t)c0 * (f1 ? 1 : XD), kb, K, dst + (size_t)c0 * NV, ctl, R,
-                                     t.balanced ? t.perm.p : nullptr);
+                                     t.perm.p);  // (null: not balanced)
         VRX_HIP(hipGetLastError());
     }
     return VRX_OK;
@@ -2727,7 +2661,7 @@ static int launch_spmm(vrx_model* m, const Orient& o, const double* X, int K, do
 // S <- (AD @ ID_prob, DP @ ID_prob)        vireo_model.py:169-170,207-208; bmm_model.py:137-138
 static int variant_pass(vrx_model* m, bool defer_sum = false) {
     ProfScope ps(m, VRX_KERN_VARIANT_PASS);
-    if (lds_eligible<0>(m->p->by_var, m->Kt)) {
+    if (lds_eligible<0>(*m->p, m->Kt)) {
         const TiledStream& tv = m->p->by_var.tiled;
         m->s_pending = defer_sum && (tv.virt || (tv.n_range > 1 && !tv.split));
         return launch_spmm_lds<0>(m, m->p->by_var, m->ID.p, m->Kt, m->S.p, m->RV.p, defer_sum);
@@ -2738,7 +2672,7 @@ static int variant_pass(vrx_model* m, bool defer_sum = false) {
 // LID <- AD^T W1 + DP^T W2                 vireo_model.py:190-196; bmm_model.py:125-129
 static int cell_pass(vrx_model* m, bool defer_sum = false) {
     ProfScope ps(m, VRX_KERN_CELL_PASS);
-    if (lds_eligible<1>(m->p->by_cell, m->Kt)) {
+    if (lds_eligible<1>(*m->p, m->Kt)) {
         m->l_pending = defer_sum && (m->p->by_cell.tiled.n_range > 1 || m->p->by_cell.tiled.split);
         return launch_spmm_lds<1>(m, m->p->by_cell, m->W.p, m->Kt, m->LID.p, m->RC.p, defer_sum);
     }
@@ -2753,7 +2687,7 @@ static bool cell_softmax_fusable(const vrx_model* m) {
     const int on = env_int("VIREO_FUSE_SOFTMAX", 1);  // (read per call: the tests switch it)
     const Orient& o = m->p->by_cell;
     return on && m->R == 1 && m->Kt <= 16 && o.n_seg > 0 && o.n_multi == 0 && o.n_empty == 0 &&
-           !lds_eligible<1>(o, m->Kt);
+           !lds_eligible<1>(*m->p, m->Kt);
 }
 
 static int cell_pass_softmax(vrx_model* m) {
@@ -3279,8 +3213,8 @@ extern "C" int vrx_debug_probe(unsigned long long* rec) {
 extern "C" int vrx_model_info(vrx_model* m, int32_t* info) {
     VRX_REQUIRE(m && info, "vrx_model_info: null argument");
     const Orient &v = m->p->by_var, &c = m->p->by_cell;
-    info[0] = lds_eligible<0>(v, m->Kt);
-    info[1] = lds_eligible<1>(c, m->Kt);
+    info[0] = lds_eligible<0>(*m->p, m->Kt);
+    info[1] = lds_eligible<1>(*m->p, m->Kt);
     info[2] = v.fmt;
     info[3] = c.fmt;
     info[4] = v.n_tiles;
