@@ -1843,6 +1843,17 @@ extern "C" int vrx_problem_n_vars(vrx_problem* p, int32_t* out) {
 static constexpr int kTraceInit = 1 << 12;  // ELBO slots per restart a model starts with (ensure_trace grows them)
 static constexpr int kEventPairs = 1 << 13;
 
+// One of the four state arrays (ID, GT, beta_mu, beta_sum), each holding R restarts: restart r's
+// block is rows x cols at row stride R * cols and column offset r * cols -- ID (M, K), GT (N, K*T),
+// beta (1, th_rows * th_cols).
+struct StatePart {
+    DevBuf<double>* buf = nullptr;  // (null: the model kind has no such array -- GT of BMM)
+    int64_t rows = 0, cols = 0;
+    int norm = 0;  // a raw draw is normalised over groups of `norm` columns; 0: beta, never
+    size_t size(int R) const { return (size_t)(rows * R * cols); }
+    size_t block() const { return (size_t)(rows * cols); }
+};
+
 struct vrx_model {
     vrx_problem* p = nullptr;
     vrx_model_cfg cfg{};
@@ -1853,6 +1864,7 @@ struct vrx_model {
     int64_t th_rows = 1, th_cols = 0;  // shape of beta_mu / beta_sum
     // variational state
     DevBuf<double> ID, GT, mu, sm;
+    StatePart part[4];  // their layout: every state entry point walks this table
     // derived tables
     DevBuf<double> psi;  // [3][th_rows][T]   (Vireo)
     DevBuf<double> S;    // [N][K] double2  (sum ad*ID, sum dp*ID)
@@ -1878,19 +1890,19 @@ struct vrx_model {
     DevBuf<double> d_elbo, d_parts;
     int64_t trace_cap = 0;  // ELBO slots per restart in d_elbo
     DevBuf<int32_t> ctl;  // device-side loop control (VRX_CTL_*)
-    DevBuf<double> snapID, snapGT, snapTh;  // vrx_model_snapshot
+    DevBuf<double> snap[3];  // vrx_model_snapshot: ID, GT, beta_mu | beta_sum
     bool snap_valid = false;
-    // vrx_model_stage_raw: the NEXT restart's raw draws, uploaded on a copy stream while this
-    // one fits (two buffers; staged[b] / consumed[b] order the copy against its consumer)
-    DevBuf<double> stageID[2], stageGT[2];
+    // vrx_model_stage_raw: the NEXT restart's raw draws (ID, GT), uploaded on a copy stream while
+    // this one fits (two buffers; staged[b] / consumed[b] order the copy against its consumer)
+    DevBuf<double> stage[2][2];
     hipStream_t copy_stream = nullptr;
     hipEvent_t staged[2] = {nullptr, nullptr}, consumed[2] = {nullptr, nullptr};
     hipEvent_t polled[2] = {nullptr, nullptr};  // vrx_model_fit's pipelined polls
     double* h_pin = nullptr;  // pinned staging for scalar read-backs
     int wform = 0;            // layout of W: 0 (W1, W2) pairs, 1 planar (Wa | Wb) rows (FORM 1)
     bool w_valid = false;     // W matches (GT, psi) on the device
-    bool s_pending = false;   // S still sits in RV as per-range partials (sum fused downstream)
-    bool l_pending = false;   // logLik_ID still sits in RC as per-range partials
+    bool s_pending = false;   // S still sits in RV as per-range partials (take_S)
+    bool l_pending = false;   // logLik_ID still sits in RC as per-range partials (take_LID)
     // launch-bound problems: the ELBO of the iteration enqueued last has not been finalised yet --
     // it rides as an extra block in the next iteration's vrx_theta_partial (VrxElboRide)
     bool elbo_deferred = false;
@@ -2010,6 +2022,10 @@ extern "C" int vrx_model_create(vrx_problem* p, const vrx_model_cfg* cfg, vrx_mo
         m->th_rows = m->N;
         m->th_cols = m->K;
     }
+    m->part[0] = {&m->ID, m->M, m->K, m->K};
+    if (cfg->kind == VRX_KIND_VIREO) m->part[1] = {&m->GT, m->N, (int64_t)m->K * m->T, m->T};
+    m->part[2] = {&m->mu, 1, m->th_rows * m->th_cols, 0};
+    m->part[3] = {&m->sm, 1, m->th_rows * m->th_cols, 0};
     hipStream_t s = p->stream;
     const size_t th = (size_t)(m->R * m->th_rows * m->th_cols);
     VRX_HIP(m->ID.alloc((size_t)((m->M + 1) * m->Kt)));  // (+ a row: an odd M's last DOUBLE row, TiledStream::virt)
@@ -2098,49 +2114,53 @@ static int d2h(vrx_model* m, double* dst, const DevBuf<double>& src, size_t n) {
     return VRX_OK;
 }
 
+// raw draws -> rows that sum to one, in place: n values in rows of `cols`
+static int normalize_raw(hipStream_t s, double* x, size_t n, int cols) {
+    const int64_t rows = (int64_t)(n / (size_t)cols);
+    vrx_normalize_rows<<<(unsigned)((rows + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(rows, cols, x);
+    VRX_HIP(hipGetLastError());
+    return VRX_OK;
+}
+
+// (vrx_normalize_rows holds its row in registers)
+static int raw_supported(const vrx_model* m, const char* who) {
+    if (m->K <= 128 && m->T <= 128) return VRX_OK;
+    vrx_set_error("%s: more than 128 columns (normalise on the host)", who);
+    return VRX_ERR_UNSUPPORTED;
+}
+
+// whole state arrays (all R restarts) from the host; null sources are left as they are
+static int upload_state(vrx_model* m, const double* const src[4], bool raw) {
+    hipStream_t s = m->p->stream;
+    int rc;
+    for (int i = 0; i < 4; ++i) {
+        const StatePart& P = m->part[i];
+        if (!P.buf || !src[i]) continue;
+        if ((rc = h2d(m, *P.buf, src[i], P.size(m->R)))) return rc;
+        if (raw && P.norm)
+            if ((rc = normalize_raw(s, P.buf->p, P.size(m->R), P.norm))) return rc;
+    }
+    VRX_HIP(hipStreamSynchronize(s));
+    m->w_valid = false;
+    return VRX_OK;
+}
+
 extern "C" int vrx_model_set_state(vrx_model* m, const double* ID_prob, const double* GT_prob,
                                    const double* beta_mu, const double* beta_sum) {
     VRX_REQUIRE(m, "vrx_model_set_state: null model");
     VRX_HIP(hipSetDevice(m->p->device));
-    int rc;
-    if ((rc = h2d(m, m->ID, ID_prob, (size_t)(m->M * m->Kt)))) return rc;
-    if (m->cfg.kind == VRX_KIND_VIREO)
-        if ((rc = h2d(m, m->GT, GT_prob, (size_t)m->NKt * m->T))) return rc;
-    if ((rc = h2d(m, m->mu, beta_mu, (size_t)(m->R * m->th_rows * m->th_cols)))) return rc;
-    if ((rc = h2d(m, m->sm, beta_sum, (size_t)(m->R * m->th_rows * m->th_cols)))) return rc;
-    VRX_HIP(hipStreamSynchronize(m->p->stream));
-    m->w_valid = false;
-    return VRX_OK;
+    const double* src[4] = {ID_prob, GT_prob, beta_mu, beta_sum};
+    return upload_state(m, src, false);
 }
 
 extern "C" int vrx_model_set_state_raw(vrx_model* m, const double* ID_raw, const double* GT_raw,
                                        const double* beta_mu, const double* beta_sum) {
     VRX_REQUIRE(m, "vrx_model_set_state_raw: null model");
-    if (m->K > 128 || m->T > 128) {
-        vrx_set_error("vrx_model_set_state_raw: more than 128 columns (normalise on the host)");
-        return VRX_ERR_UNSUPPORTED;
-    }
+    int rc = raw_supported(m, "vrx_model_set_state_raw");
+    if (rc) return rc;
     VRX_HIP(hipSetDevice(m->p->device));
-    hipStream_t s = m->p->stream;
-    int rc;
-    if ((rc = h2d(m, m->ID, ID_raw, (size_t)(m->M * m->Kt)))) return rc;
-    if (ID_raw) {
-        const int64_t rows = m->M * m->R;  // [M][R][K]: one row per (cell, restart)
-        vrx_normalize_rows<<<(unsigned)((rows + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
-            rows, m->K, m->ID.p);
-        VRX_HIP(hipGetLastError());
-    }
-    if (m->cfg.kind == VRX_KIND_VIREO && GT_raw) {
-        if ((rc = h2d(m, m->GT, GT_raw, (size_t)m->NKt * m->T))) return rc;
-        vrx_normalize_rows<<<(unsigned)((m->NKt + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
-            m->NKt, m->T, m->GT.p);
-        VRX_HIP(hipGetLastError());
-    }
-    if ((rc = h2d(m, m->mu, beta_mu, (size_t)(m->R * m->th_rows * m->th_cols)))) return rc;
-    if ((rc = h2d(m, m->sm, beta_sum, (size_t)(m->R * m->th_rows * m->th_cols)))) return rc;
-    VRX_HIP(hipStreamSynchronize(s));
-    m->w_valid = false;
-    return VRX_OK;
+    const double* src[4] = {ID_raw, GT_raw, beta_mu, beta_sum};
+    return upload_state(m, src, true);  // ([M][R][K] and [N][R][K][T]: one row per restart)
 }
 
 // ---- staged uploads (vireo_wrap.py:64-87: the restarts run one after the other) -------------
@@ -2156,8 +2176,7 @@ extern "C" int vrx_model_stage_reserve(vrx_model* m) {
     if (m->copy_stream) return VRX_OK;
     VRX_HIP(hipSetDevice(m->p->device));
     for (int b = 0; b < 2; ++b) {
-        VRX_HIP(m->stageID[b].alloc((size_t)(m->M * m->K)));
-        VRX_HIP(m->stageGT[b].alloc((size_t)m->NK * m->T));
+        for (int i = 0; i < 2; ++i) VRX_HIP(m->stage[b][i].alloc(m->part[i].block()));
         VRX_HIP(hipEventCreateWithFlags(&m->staged[b], hipEventDisableTiming));
         VRX_HIP(hipEventCreateWithFlags(&m->consumed[b], hipEventDisableTiming));
     }
@@ -2174,8 +2193,10 @@ extern "C" int vrx_model_stage_raw(vrx_model* m, int32_t buf, const double* ID_r
     // (the buffer's previous content has been normalised into the state: consumed[buf] was
     //  recorded behind that; an event never recorded counts as complete)
     VRX_HIP(hipStreamWaitEvent(c, m->consumed[buf], 0));
-    VRX_HIP(hipMemcpyAsync(m->stageID[buf].p, ID_raw, m->stageID[buf].n * sizeof(double), hipMemcpyHostToDevice, c));
-    VRX_HIP(hipMemcpyAsync(m->stageGT[buf].p, GT_raw, m->stageGT[buf].n * sizeof(double), hipMemcpyHostToDevice, c));
+    const double* src[2] = {ID_raw, GT_raw};
+    for (int i = 0; i < 2; ++i)
+        VRX_HIP(hipMemcpyAsync(m->stage[buf][i].p, src[i], m->stage[buf][i].n * sizeof(double),
+                               hipMemcpyHostToDevice, c));
     VRX_HIP(hipEventRecord(m->staged[buf], c));
     VRX_HIP(hipStreamSynchronize(c));  // (the host arrays may be reused by the caller)
     return VRX_OK;
@@ -2186,26 +2207,19 @@ extern "C" int vrx_model_set_state_staged(vrx_model* m, int32_t buf, const doubl
     VRX_REQUIRE(m, "vrx_model_set_state_staged: null model");
     VRX_REQUIRE(buf == 0 || buf == 1, "vrx_model_set_state_staged: buffer %d", buf);
     VRX_REQUIRE(m->copy_stream, "vrx_model_set_state_staged: nothing was staged");
-    if (m->K > 128 || m->T > 128) {
-        vrx_set_error("vrx_model_set_state_staged: more than 128 columns (normalise on the host)");
-        return VRX_ERR_UNSUPPORTED;
-    }
+    int rc = raw_supported(m, "vrx_model_set_state_staged");
+    if (rc) return rc;
     VRX_HIP(hipSetDevice(m->p->device));
     hipStream_t s = m->p->stream;
-    int rc;
     VRX_HIP(hipStreamWaitEvent(s, m->staged[buf], 0));
-    VRX_HIP(hipMemcpyAsync(m->ID.p, m->stageID[buf].p, m->stageID[buf].n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    VRX_HIP(hipMemcpyAsync(m->GT.p, m->stageGT[buf].p, m->stageGT[buf].n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    for (int i = 0; i < 2; ++i)
+        VRX_HIP(hipMemcpyAsync(m->part[i].buf->p, m->stage[buf][i].p, m->stage[buf][i].n * sizeof(double),
+                               hipMemcpyDeviceToDevice, s));
     VRX_HIP(hipEventRecord(m->consumed[buf], s));
-    vrx_normalize_rows<<<(unsigned)((m->M + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(m->M, m->K, m->ID.p);
-    VRX_HIP(hipGetLastError());
-    vrx_normalize_rows<<<(unsigned)((m->NK + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(m->NK, m->T, m->GT.p);
-    VRX_HIP(hipGetLastError());
-    if ((rc = h2d(m, m->mu, beta_mu, (size_t)(m->th_rows * m->th_cols)))) return rc;
-    if ((rc = h2d(m, m->sm, beta_sum, (size_t)(m->th_rows * m->th_cols)))) return rc;
-    VRX_HIP(hipStreamSynchronize(s));
-    m->w_valid = false;
-    return VRX_OK;
+    for (int i = 0; i < 2; ++i)
+        if ((rc = normalize_raw(s, m->part[i].buf->p, m->stage[buf][i].n, m->part[i].norm))) return rc;
+    const double* beta[4] = {nullptr, nullptr, beta_mu, beta_sum};
+    return upload_state(m, beta, false);
 }
 
 // device-side copy of the variational state: the best restart so far is kept in HBM, no
@@ -2214,22 +2228,20 @@ extern "C" int vrx_model_snapshot(vrx_model* m, int32_t restore) {
     VRX_REQUIRE(m, "vrx_model_snapshot: null model");
     VRX_HIP(hipSetDevice(m->p->device));
     hipStream_t s = m->p->stream;
-    const size_t th = (size_t)(m->R * m->th_rows * m->th_cols);
     if (restore) {
         VRX_REQUIRE(m->snap_valid, "vrx_model_snapshot: nothing saved");
-    } else if (!m->snapID.p) {
-        VRX_HIP(m->snapID.alloc((size_t)(m->M * m->Kt)));
-        if (m->cfg.kind == VRX_KIND_VIREO) VRX_HIP(m->snapGT.alloc((size_t)m->NKt * m->T));
-        VRX_HIP(m->snapTh.alloc(2 * th));
+    } else if (!m->snap[0].p) {
+        for (int i = 0; i < 3; ++i)
+            if (m->part[i].buf) VRX_HIP(m->snap[i].alloc(m->part[i].size(m->R) * (i == 2 ? 2 : 1)));
     }
-    auto cp = [&](double* live, double* saved, size_t n) {
-        return restore ? hipMemcpyAsync(live, saved, n * sizeof(double), hipMemcpyDeviceToDevice, s)
-                       : hipMemcpyAsync(saved, live, n * sizeof(double), hipMemcpyDeviceToDevice, s);
-    };
-    VRX_HIP(cp(m->ID.p, m->snapID.p, (size_t)(m->M * m->Kt)));
-    if (m->cfg.kind == VRX_KIND_VIREO) VRX_HIP(cp(m->GT.p, m->snapGT.p, (size_t)m->NKt * m->T));
-    VRX_HIP(cp(m->mu.p, m->snapTh.p, th));
-    VRX_HIP(cp(m->sm.p, m->snapTh.p + th, th));
+    for (int i = 0; i < 4; ++i) {
+        const StatePart& P = m->part[i];
+        if (!P.buf) continue;
+        // (the two beta halves share a buffer: the runtime's copy kernels depend on the alignment)
+        double *live = P.buf->p, *saved = i < 3 ? m->snap[i].p : m->snap[2].p + P.size(m->R);
+        VRX_HIP(hipMemcpyAsync(restore ? live : saved, restore ? saved : live, P.size(m->R) * sizeof(double),
+                               hipMemcpyDeviceToDevice, s));
+    }
     VRX_HIP(hipStreamSynchronize(s));
     if (restore)
         m->w_valid = false;
@@ -2268,38 +2280,26 @@ extern "C" int vrx_model_set_restart(vrx_model* m, int32_t r, const double* ID, 
                                      const double* beta_mu, const double* beta_sum, int32_t raw) {
     VRX_REQUIRE(m, "vrx_model_set_restart: null model");
     VRX_REQUIRE(r >= 0 && r < m->R, "vrx_model_set_restart: slot %d outside the batch of %d", r, m->R);
-    if (raw && (m->K > 128 || m->T > 128)) {
-        vrx_set_error("vrx_model_set_restart: more than 128 columns (normalise on the host)");
-        return VRX_ERR_UNSUPPORTED;
-    }
+    int rc;
+    if (raw && (rc = raw_supported(m, "vrx_model_set_restart"))) return rc;
     VRX_HIP(hipSetDevice(m->p->device));
     hipStream_t s = m->p->stream;
-    int rc;
-    const size_t n_id = (size_t)(m->M * m->K), n_gt = (size_t)m->NK * m->T;
-    const size_t th = (size_t)(m->th_rows * m->th_cols);
-    if (ID) {
-        if (m->tmp.n != n_id) VRX_HIP(m->tmp.alloc(n_id));
-        VRX_HIP(hipMemcpyAsync(m->tmp.p, ID, n_id * sizeof(double), hipMemcpyHostToDevice, s));
-        if (raw)
-            vrx_normalize_rows<<<(unsigned)((m->M + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
-                m->M, m->K, m->tmp.p);
-        if ((rc = copy_block(s, m->M, m->K, m->tmp.p, m->K, 0, m->ID.p, m->Kt, (int64_t)r * m->K)))
-            return rc;
+    const double* src[4] = {ID, GT, beta_mu, beta_sum};
+    DevBuf<double>* tmp[2] = {&m->tmp, &m->tmp2};  // (ID, GT: through the device, into the strided slot)
+    for (int i = 0; i < 4; ++i) {
+        const StatePart& P = m->part[i];
+        if (!P.buf || !src[i]) continue;
+        const size_t n = P.block();
+        if (!P.norm) {  // beta: one row per restart, the slot is contiguous
+            VRX_HIP(hipMemcpyAsync(P.buf->p + r * P.cols, src[i], n * sizeof(double), hipMemcpyHostToDevice, s));
+            continue;
+        }
+        DevBuf<double>& t = *tmp[i];
+        if (t.n != n) VRX_HIP(t.alloc(n));
+        VRX_HIP(hipMemcpyAsync(t.p, src[i], n * sizeof(double), hipMemcpyHostToDevice, s));
+        if (raw && (rc = normalize_raw(s, t.p, n, P.norm))) return rc;
+        if ((rc = copy_block(s, P.rows, P.cols, t.p, P.cols, 0, P.buf->p, m->R * P.cols, r * P.cols))) return rc;
     }
-    if (GT && m->cfg.kind == VRX_KIND_VIREO) {
-        if (m->tmp2.n != n_gt) VRX_HIP(m->tmp2.alloc(n_gt));
-        VRX_HIP(hipMemcpyAsync(m->tmp2.p, GT, n_gt * sizeof(double), hipMemcpyHostToDevice, s));
-        if (raw)
-            vrx_normalize_rows<<<(unsigned)((m->NK + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
-                m->NK, m->T, m->tmp2.p);
-        const int64_t kt = (int64_t)m->K * m->T;
-        if ((rc = copy_block(s, m->N, kt, m->tmp2.p, kt, 0, m->GT.p, (int64_t)m->Kt * m->T, r * kt)))
-            return rc;
-    }
-    if (beta_mu)
-        VRX_HIP(hipMemcpyAsync(m->mu.p + r * th, beta_mu, th * sizeof(double), hipMemcpyHostToDevice, s));
-    if (beta_sum)
-        VRX_HIP(hipMemcpyAsync(m->sm.p + r * th, beta_sum, th * sizeof(double), hipMemcpyHostToDevice, s));
     VRX_HIP(hipStreamSynchronize(s));  // (the host arrays may be reused by the caller)
     m->w_valid = false;
     return VRX_OK;
@@ -2316,16 +2316,15 @@ extern "C" int vrx_model_copy_restart(vrx_model* dst, vrx_model* src, int32_t r)
     VRX_HIP(hipSetDevice(src->p->device));
     hipStream_t s = src->p->stream;
     int rc;
-    if ((rc = copy_block(s, src->M, src->K, src->ID.p, src->Kt, (int64_t)r * src->K, dst->ID.p, src->K, 0)))
-        return rc;
-    if (src->cfg.kind == VRX_KIND_VIREO) {
-        const int64_t kt = (int64_t)src->K * src->T;
-        if ((rc = copy_block(s, src->N, kt, src->GT.p, (int64_t)src->Kt * src->T, r * kt, dst->GT.p, kt, 0)))
+    for (int i = 0; i < 4; ++i) {
+        const StatePart& P = src->part[i];
+        if (!P.buf) continue;
+        double* to = dst->part[i].buf->p;
+        if (!P.norm)  // beta: one row per restart, the slot is contiguous
+            VRX_HIP(hipMemcpyAsync(to, P.buf->p + r * P.cols, P.block() * sizeof(double), hipMemcpyDeviceToDevice, s));
+        else if ((rc = copy_block(s, P.rows, P.cols, P.buf->p, src->R * P.cols, r * P.cols, to, P.cols, 0)))
             return rc;
     }
-    const size_t th = (size_t)(src->th_rows * src->th_cols);
-    VRX_HIP(hipMemcpyAsync(dst->mu.p, src->mu.p + r * th, th * sizeof(double), hipMemcpyDeviceToDevice, s));
-    VRX_HIP(hipMemcpyAsync(dst->sm.p, src->sm.p + r * th, th * sizeof(double), hipMemcpyDeviceToDevice, s));
     VRX_HIP(hipStreamSynchronize(s));
     dst->w_valid = false;
     return VRX_OK;
@@ -2335,12 +2334,10 @@ extern "C" int vrx_model_get_state(vrx_model* m, double* ID_prob, double* GT_pro
                                    double* beta_sum) {
     VRX_REQUIRE(m, "vrx_model_get_state: null model");
     VRX_HIP(hipSetDevice(m->p->device));
+    double* dst[4] = {ID_prob, GT_prob, beta_mu, beta_sum};
     int rc;
-    if ((rc = d2h(m, ID_prob, m->ID, (size_t)(m->M * m->Kt)))) return rc;
-    if (m->cfg.kind == VRX_KIND_VIREO)
-        if ((rc = d2h(m, GT_prob, m->GT, (size_t)m->NKt * m->T))) return rc;
-    if ((rc = d2h(m, beta_mu, m->mu, (size_t)(m->R * m->th_rows * m->th_cols)))) return rc;
-    if ((rc = d2h(m, beta_sum, m->sm, (size_t)(m->R * m->th_rows * m->th_cols)))) return rc;
+    for (int i = 0; i < 4; ++i)
+        if (m->part[i].buf && (rc = d2h(m, dst[i], *m->part[i].buf, m->part[i].size(m->R)))) return rc;
     VRX_HIP(hipStreamSynchronize(m->p->stream));
     return VRX_OK;
 }
@@ -2350,20 +2347,19 @@ int vrx_model_state_buffers(vrx_model* m, bool will_write, VrxModelBuffers* out)
     VRX_REQUIRE(m && out, "vrx_model_state_buffers: null argument");
     VRX_HIP(hipSetDevice(m->p->device));
     VRX_HIP(hipStreamSynchronize(m->p->stream));
-    const size_t th = (size_t)(m->R * m->th_rows * m->th_cols);
-    out->p[0] = m->ID.p;
-    out->n[0] = (size_t)(m->M * m->Kt);
-    out->p[1] = m->cfg.kind == VRX_KIND_VIREO ? m->GT.p : nullptr;
-    out->n[1] = m->cfg.kind == VRX_KIND_VIREO ? (size_t)m->NKt * m->T : 0;
-    out->p[2] = m->mu.p;
-    out->n[2] = th;
-    out->p[3] = m->sm.p;
-    out->n[3] = th;
+    for (int i = 0; i < 4; ++i) {
+        const StatePart& P = m->part[i];
+        out->p[i] = P.buf ? P.buf->p : nullptr;
+        out->n[i] = P.buf ? P.size(m->R) : 0;
+    }
     out->device = m->p->device;
     if (will_write) m->w_valid = false;
     return VRX_OK;
 }
 
+// logLik_ID as the last step (VRX_STEP_ID / VRX_STEP_LOGLIK) left it.  Not after a fit: on tiled cell
+// streams with several ranges or split rows, a fit's cell passes leave logLik_ID as partials in RC
+// (summed inside the softmax kernel, take_LID) and never write LID.
 extern "C" int vrx_model_get_loglik(vrx_model* m, double* out) {
     VRX_REQUIRE(m && out, "vrx_model_get_loglik: null argument");
     VRX_HIP(hipSetDevice(m->p->device));
@@ -2406,6 +2402,21 @@ static int upload_log_rows(vrx_model* m, DevBuf<double>& dst, const double* src,
     return VRX_OK;
 }
 
+// a prior of 0, 1 or one row per cell / variant: mode 0 (none), 1 (one row for all) or 2 (per row);
+// each row holds `tables` probability tables of `cols`, kept as row-normalised logs
+static int set_log_prior(vrx_model* m, DevBuf<double>& logq, int& mode, const double* src, int64_t rows,
+                         int64_t tables, int cols) {
+    if (rows == 0) {
+        mode = 0;
+        logq.release();
+        return VRX_OK;
+    }
+    int rc = upload_log_rows(m, logq, src, rows * tables, cols);
+    if (rc) return rc;
+    mode = rows == 1 ? 1 : 2;
+    return VRX_OK;
+}
+
 extern "C" int vrx_model_set_prior(vrx_model* m, const double* ID_prior, int64_t id_rows,
                                    const double* GT_prior, int64_t gt_rows, const double* s1_prior,
                                    const double* s2_prior, int64_t theta_prior_rows) {
@@ -2414,27 +2425,15 @@ extern "C" int vrx_model_set_prior(vrx_model* m, const double* ID_prior, int64_t
     VRX_REQUIRE(id_rows == 0 || id_rows == 1 || id_rows == m->M,
                 "vrx_model_set_prior: ID_prior must have 0, 1 or n_cell rows (got %lld)",
                 (long long)id_rows);
+    VRX_REQUIRE(id_rows == 0 || ID_prior, "vrx_model_set_prior: null ID_prior");
     int rc;
-    if (id_rows == 0) {
-        m->id_mode = 0;
-        m->logq_id.release();
-    } else {
-        VRX_REQUIRE(ID_prior, "vrx_model_set_prior: null ID_prior");
-        if ((rc = upload_log_rows(m, m->logq_id, ID_prior, id_rows, m->K))) return rc;
-        m->id_mode = id_rows == 1 ? 1 : 2;
-    }
+    if ((rc = set_log_prior(m, m->logq_id, m->id_mode, ID_prior, id_rows, 1, m->K))) return rc;
     if (m->cfg.kind == VRX_KIND_VIREO) {
         VRX_REQUIRE(gt_rows == 0 || gt_rows == 1 || gt_rows == m->N,
                     "vrx_model_set_prior: GT_prior must have 0, 1 or n_var rows (got %lld)",
                     (long long)gt_rows);
-        if (gt_rows == 0) {
-            m->gt_mode = 0;
-            m->logq_gt.release();
-        } else {
-            VRX_REQUIRE(GT_prior, "vrx_model_set_prior: null GT_prior");
-            if ((rc = upload_log_rows(m, m->logq_gt, GT_prior, gt_rows * m->K, m->T))) return rc;
-            m->gt_mode = gt_rows == 1 ? 1 : 2;
-        }
+        VRX_REQUIRE(gt_rows == 0 || GT_prior, "vrx_model_set_prior: null GT_prior");
+        if ((rc = set_log_prior(m, m->logq_gt, m->gt_mode, GT_prior, gt_rows, m->K, m->T))) return rc;
     }
     VRX_REQUIRE(s1_prior && s2_prior, "vrx_model_set_prior: null theta prior");
     VRX_REQUIRE(theta_prior_rows == 1 || theta_prior_rows == m->th_rows,
@@ -2480,21 +2479,18 @@ static void launch_spmm_fmt(const Orient& o, dim3 grid, hipStream_t s, const dou
 
 // LDS-resident pass: K <= 16 (4 columns per lane, the dense rows zero-padded to a multiple of
 // 4 columns in LDS), counts < 2048 (checked when the tiled stream is built)
+// (K > 16: column blocks of 16)
 template <int MODE>
 static bool lds_eligible(const vrx_problem& p, int K) {
-    static const int mask = env_int("VIREO_LDS_PASS", 3);  // bit 0: variant pass, bit 1: cell pass
-    static const int kmin = env_int("VIREO_LDS_MIN_K", 2);
-    static const int kmax = env_int("VIREO_LDS_MAX_K", 1 << 20);  // > 16: column blocks of 16
     const Orient& o = MODE == 0 ? p.by_var : p.by_cell;
     if (p.device_built) return true;  // (no gather tables)
-    return o.tiled.ready && (mask >> MODE & 1) && K <= kmax && K >= kmin;
+    return o.tiled.ready && K >= 2;
 }
 
 // kernel instance for K: zero-padded rows when K % 4, 2 / 4 entries at once when K <= 8 / 4
 template <int LPE, int MODE, int RW>
 static auto lds_kernel_rw(int K, bool strided) {
-    static const int split_on = env_int("VIREO_LDS_SPLIT_K", 1);
-    const int split = std::min(LPE, !split_on ? 1 : K <= 4 ? 4 : K <= 8 ? 2 : 1);
+    const int split = std::min(LPE, K <= 4 ? 4 : K <= 8 ? 2 : 1);
     // (the element-wise slab copy handles row strides and rows that do not fill whole lanes)
     const bool pad = K % (16 / LPE) != 0 || strided;
     if constexpr (LPE >= 4)
@@ -2584,17 +2580,8 @@ static int launch_spmm_lds(vrx_model* m, const Orient& o, const double* X, int K
     if (MODE == 0 && t.virt) {
         // virtual rows: the cell pass's kernel over (variant, AD) / (variant, BD) rows and the
         // operand as double rows; planar partial sums [slot][virtual piece][K], turned into
-        // S = (S1, S1 + S2) by the consumer (vrx_theta_partial) or by vrx_s_from_virtual
-        int rc = launch_lds_one<VRX_LDS_LPE, 1>(o, s, X, K, range_partial, m->ctl.p, m->R);
-        if (rc) return rc;
-        if (!defer_sum) {
-            const int64_t n = o.n_rows * K;
-            vrx_s_from_virtual<<<(unsigned)((n + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
-                o.n_rows, K, t.n_vrows, t.split ? t.vptr.p : nullptr, t.npiece.p, range_partial,
-                reinterpret_cast<double2*>(out), m->ctl.p, m->R);
-            VRX_HIP(hipGetLastError());
-        }
-        return VRX_OK;
+        // S = (S1, S1 + S2) by take_S or by its consumer (vrx_theta_partial)
+        return launch_lds_one<VRX_LDS_LPE, 1>(o, s, X, K, range_partial, m->ctl.p, m->R);
     }
     double* dst = t.n_range == 1 && !t.split ? out : range_partial;
     int rc;
@@ -2658,13 +2645,91 @@ static int launch_spmm(vrx_model* m, const Orient& o, const double* X, int K, do
     return VRX_OK;
 }
 
+// the rows a tiled stream cut into pieces: sum of all their terms -> slot 0 of the first piece
+// (vrx_fold_split), for the consumers that sum the partial arrays themselves.  NOT idempotent:
+// only take_S / take_LID run it, once per deferred pass.
+static int fold_split(vrx_model* m, const TiledStream& t, double* partial) {
+    if (t.n_split == 0) return VRX_OK;
+    const int64_t lanes = t.n_split * m->Kt * 8;  // eight lanes per (split row, column)
+    vrx_fold_split<<<(unsigned)((lanes + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, m->p->stream>>>(
+        t.n_split, t.split_rows.p, m->Kt, t.n_vrows, t.vptr.p, t.npiece.p, partial, m->ctl.p, m->R);
+    VRX_HIP(hipGetLastError());
+    return VRX_OK;
+}
+
+// How a consumer reads a pass output: npiece null -- the array is final; otherwise the consumer's
+// kernel sums the per-range (and per-piece) partials itself with these arguments.
+struct PassSum {
+    const uint16_t* npiece = nullptr;
+    const double* partial = nullptr;  // (RV / RC: passed whether or not they are summed)
+    int64_t n_vrows = 0;
+    const int32_t* vptr = nullptr;
+};
+
+// S for its consumer.  A deferred variant pass (s_pending) leaves S as partials in RV, summed by
+// exactly one consumer: f non-null -- the consumer can fuse the sum and *f gets its arguments;
+// f null -- S is formed here.  Either way S is final for everything after.
+static int take_S(vrx_model* m, PassSum* f) {
+    const TiledStream& tv = m->p->by_var.tiled;
+    if (f) {
+        *f = PassSum{};
+        f->partial = m->RV.p;
+    }
+    if (!m->s_pending) return VRX_OK;
+    m->s_pending = false;
+    if (f) {
+        if (tv.virt && tv.split) {  // rows cut into pieces: their terms first
+            int rc = fold_split(m, tv, m->RV.p);
+            if (rc) return rc;
+        }
+        f->npiece = tv.npiece.p;
+        f->n_vrows = tv.virt ? tv.n_vrows : 0;
+        f->vptr = tv.virt && tv.split ? tv.vptr.p : nullptr;
+        return VRX_OK;
+    }
+    if (tv.virt) {
+        const int64_t n = m->NKt;
+        vrx_s_from_virtual<<<(unsigned)((n + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, m->p->stream>>>(
+            m->N, m->Kt, tv.n_vrows, tv.split ? tv.vptr.p : nullptr, tv.npiece.p, m->RV.p,
+            reinterpret_cast<double2*>(m->S.p), m->ctl.p, m->R);
+    } else {
+        const int64_t n = m->NKt * 2;
+        vrx_sum_ranges<<<(unsigned)((n + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, m->p->stream>>>(
+            n, m->Kt * 2, tv.npiece.p, m->RV.p, m->S.p, m->ctl.p, m->R);
+    }
+    VRX_HIP(hipGetLastError());
+    return VRX_OK;
+}
+
+// logLik_ID for its one consumer, vrx_cell_softmax, which always fuses the sum of the partials a
+// deferred cell pass (l_pending) left in RC.  (n_vrows: rows of the array it reads, M when final)
+static int take_LID(vrx_model* m, PassSum* f) {
+    const TiledStream& tc = m->p->by_cell.tiled;
+    *f = PassSum{};
+    f->partial = m->RC.p;
+    f->n_vrows = m->M;
+    if (!m->l_pending) return VRX_OK;
+    m->l_pending = false;
+    if (tc.split) {  // rows cut into pieces: their terms first
+        int rc = fold_split(m, tc, m->RC.p);
+        if (rc) return rc;
+    }
+    f->npiece = tc.npiece.p;
+    f->n_vrows = tc.n_vrows;
+    f->vptr = tc.split ? tc.vptr.p : nullptr;
+    return VRX_OK;
+}
+
 // S <- (AD @ ID_prob, DP @ ID_prob)        vireo_model.py:169-170,207-208; bmm_model.py:137-138
+// defer_sum: per-range / virtual-row partials stay in RV for the consumer (take_S)
 static int variant_pass(vrx_model* m, bool defer_sum = false) {
     ProfScope ps(m, VRX_KERN_VARIANT_PASS);
     if (lds_eligible<0>(*m->p, m->Kt)) {
         const TiledStream& tv = m->p->by_var.tiled;
-        m->s_pending = defer_sum && (tv.virt || (tv.n_range > 1 && !tv.split));
-        return launch_spmm_lds<0>(m, m->p->by_var, m->ID.p, m->Kt, m->S.p, m->RV.p, defer_sum);
+        int rc = launch_spmm_lds<0>(m, m->p->by_var, m->ID.p, m->Kt, m->S.p, m->RV.p, true);
+        if (rc) return rc;
+        m->s_pending = tv.virt || (tv.n_range > 1 && !tv.split);  // (split pieces were summed above)
+        return defer_sum ? VRX_OK : take_S(m, nullptr);
     }
     return launch_spmm<0>(m, m->p->by_var, m->ID.p, m->Kt, m->S.p, m->PV.p);
 }
@@ -2704,54 +2769,19 @@ static int cell_pass_softmax(vrx_model* m) {
     return launch_spmm<1>(m, o, m->W.p, m->Kt, m->LID.p, m->PC.p, &F);
 }
 
-// the rows a tiled stream cut into pieces: sum of all their terms -> slot 0 of the first piece
-// (vrx_fold_split), for the consumers that sum the partial arrays themselves
-static int fold_split(vrx_model* m, const TiledStream& t, double* partial) {
-    if (t.n_split == 0) return VRX_OK;
-    const int64_t lanes = t.n_split * m->Kt * 8;  // eight lanes per (split row, column)
-    vrx_fold_split<<<(unsigned)((lanes + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, m->p->stream>>>(
-        t.n_split, t.split_rows.p, m->Kt, t.n_vrows, t.vptr.p, t.npiece.p, partial, m->ctl.p, m->R);
-    VRX_HIP(hipGetLastError());
-    return VRX_OK;
-}
-
-// a consumer that cannot fuse the range sum forms S / logLik_ID explicitly
-static int resolve_S(vrx_model* m) {
-    if (!m->s_pending) return VRX_OK;
-    const TiledStream& tv = m->p->by_var.tiled;
-    if (tv.virt) {
-        const int64_t n = m->NKt;
-        vrx_s_from_virtual<<<(unsigned)((n + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, m->p->stream>>>(
-            m->N, m->Kt, tv.n_vrows, tv.split ? tv.vptr.p : nullptr, tv.npiece.p, m->RV.p,
-            reinterpret_cast<double2*>(m->S.p), m->ctl.p, m->R);
-        VRX_HIP(hipGetLastError());
-        m->s_pending = false;
-        return VRX_OK;
-    }
-    const int64_t n = m->NKt * 2;
-    vrx_sum_ranges<<<(unsigned)((n + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, m->p->stream>>>(
-        n, m->Kt * 2, m->p->by_var.tiled.npiece.p, m->RV.p, m->S.p, m->ctl.p, m->R);
-    VRX_HIP(hipGetLastError());
-    m->s_pending = false;
-    return VRX_OK;
-}
-
-static int resolve_LID(vrx_model* m) {
-    if (!m->l_pending) return VRX_OK;
-    const int64_t n = m->M * m->Kt;
-    const TiledStream& tc = m->p->by_cell.tiled;
-    if (tc.split)
-        vrx_sum_pieces<<<(unsigned)((n + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, m->p->stream>>>(
-            m->M, m->Kt, tc.n_range, tc.n_vrows, tc.vptr.p, tc.npiece.p, m->RC.p, m->LID.p, m->ctl.p, m->R);
-    else
-    vrx_sum_ranges<<<(unsigned)((n + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, m->p->stream>>>(
-        n, m->Kt, m->p->by_cell.tiled.npiece.p, m->RC.p, m->LID.p, m->ctl.p, m->R);
-    VRX_HIP(hipGetLastError());
-    m->l_pending = false;
-    return VRX_OK;
-}
-
 static VrxElboIn elbo_inputs(vrx_model* m);
+
+// the ELBO a previous iteration left deferred (with its stop rule), as the extra block of the
+// theta launch that carries it; off when none waits
+static VrxElboRide take_ride(vrx_model* m) {
+    VrxElboRide E{};
+    if (!m->elbo_deferred) return E;
+    E.on = 1;
+    E.in = elbo_inputs(m);
+    E.rule = m->elbo_rule;
+    m->elbo_deferred = false;
+    return E;
+}
 
 // theta update (update=1) or just psi/KL from the current beta (update=0).  defer_final: the
 // caller runs gt_step next, whose kernel finalises the shared theta itself (VrxThetaFuse).
@@ -2759,32 +2789,27 @@ static int theta_step(vrx_model* m, int update, bool defer_final = false) {
     ProfScope ps(m, VRX_KERN_DENSE);
     hipStream_t s = m->p->stream;
     const auto& c = m->cfg;
-    const TiledStream& tvar = m->p->by_var.tiled;
-    const bool bmm_fuse = c.kind == VRX_KIND_BMM && update && m->s_pending && !tvar.virt && !tvar.split;
-    if ((c.kind == VRX_KIND_BMM || c.ase_mode) && !bmm_fuse) {
-        int rc = resolve_S(m);  // (the ASE kernel does not fuse the range sum)
-        if (rc) return rc;
-    }
+    int rc;
     if (c.kind == VRX_KIND_BMM) {
+        // the range sum fuses into an update on a stream that is neither virtual nor split
+        const TiledStream& tv = m->p->by_var.tiled;
+        PassSum f;
+        if ((rc = take_S(m, update && !tv.virt && !tv.split ? &f : nullptr))) return rc;
         // (fused range sum: 16 lanes per element; the KL partials are zero-filled past nb_nk blocks' worth)
-        const unsigned nb = bmm_fuse ? (unsigned)((m->NK * 16 + VRX_BLOCK - 1) / VRX_BLOCK) : (unsigned)m->nb_nk;
-        VrxElboRide E{};
-        if (m->elbo_deferred) {  // the previous iteration's ELBO + stop rule: one extra block, reading
-            E.on = 1;            // the KL_theta partials of the half this launch does not write
-            E.in = elbo_inputs(m);
-            E.rule = m->elbo_rule;
-            m->elbo_deferred = false;
-        }
+        const unsigned nb = f.npiece ? (unsigned)((m->NK * 16 + VRX_BLOCK - 1) / VRX_BLOCK) : (unsigned)m->nb_nk;
+        // the previous iteration's ELBO + stop rule reads the KL_theta partials of the half this
+        // launch does not write
+        const VrxElboRide E = take_ride(m);
         m->th_cur ^= 1;
         m->n_th_part = (int)nb;
         vrx_bmm_theta<<<dim3(nb + E.on, m->R), VRX_BLOCK, 0, s>>>(
-            m->NK, update, c.fix_beta_sum, reinterpret_cast<double2*>(m->S.p),
-            bmm_fuse ? tvar.npiece.p : nullptr, reinterpret_cast<const double2*>(m->RV.p), m->prior1.p,
+            m->NK, update, c.fix_beta_sum, reinterpret_cast<double2*>(m->S.p), f.npiece,
+            reinterpret_cast<const double2*>(m->RV.p), m->prior1.p,
             m->prior2.p, m->prior_rows == 1 ? 0 : 1, m->mu.p, m->sm.p, m->W.p, m->K, m->wform,
             m->part_th.p + (size_t)m->th_cur * m->th_cap, m->batch(), m->ctl.p, E);
-        if (bmm_fuse) m->s_pending = false;
         m->w_valid = true;
     } else if (c.ase_mode) {
+        if ((rc = take_S(m, nullptr))) return rc;  // (the ASE kernel does not fuse the range sum)
         vrx_theta_ase<<<dim3(m->nb_throws, m->R), VRX_BLOCK, 0, s>>>(
             m->N, m->K, m->T, update, c.fix_beta_sum, reinterpret_cast<const double2*>(m->S.p),
             m->GT.p, m->prior1.p, m->prior2.p, (int)m->prior_rows, m->mu.p, m->sm.p, m->psi.p,
@@ -2792,27 +2817,15 @@ static int theta_step(vrx_model* m, int update, bool defer_final = false) {
         m->w_valid = false;
     } else {
         if (update) {
-            const TiledStream& tv = m->p->by_var.tiled;
-            if (m->s_pending && tv.virt && tv.split) {  // rows cut into pieces: their terms first
-                int rc = fold_split(m, tv, m->RV.p);
-                if (rc) return rc;
-            }
-            const uint16_t* np = m->s_pending ? tv.npiece.p : nullptr;
+            PassSum f;
+            if ((rc = take_S(m, &f))) return rc;  // every layout fuses here
             auto* kern = m->T == 3 ? vrx_theta_partial<3> : vrx_theta_partial<VRX_MAXT>;
-            VrxElboRide E{};
-            if (m->elbo_deferred) {  // the previous iteration's ELBO + stop rule: one extra block
-                E.on = 1;
-                E.in = elbo_inputs(m);
-                E.rule = m->elbo_rule;
-                m->elbo_deferred = false;
-            }
+            const VrxElboRide E = take_ride(m);  // the previous iteration's ELBO + stop rule: one extra block
             kern<<<dim3(m->nb_theta + E.on, m->R), VRX_BLOCK, 0, s>>>(
-                m->NK, m->T, reinterpret_cast<double2*>(m->S.p), np,
-                reinterpret_cast<const double2*>(m->RV.p), m->s_pending && tv.virt ? tv.n_vrows : 0,
-                m->s_pending && tv.virt && tv.split ? tv.vptr.p : nullptr,
+                m->NK, m->T, reinterpret_cast<double2*>(m->S.p), f.npiece,
+                reinterpret_cast<const double2*>(f.partial), f.n_vrows, f.vptr,
                 m->GT.p, m->part_theta.p, m->batch(), m->ctl.p, E);
             VRX_HIP(hipGetLastError());
-            m->s_pending = false;
         }
         // Worth it only while the partials are few: every block of vrx_gt_update re-reads them
         // (c2, 157 partials: 43.4 -> 41.9 us per iteration; c3, 1024 partials = 128 KB per
@@ -2835,7 +2848,7 @@ static int theta_step(vrx_model* m, int update, bool defer_final = false) {
 static int gt_step(vrx_model* m, int learn) {
     ProfScope ps(m, VRX_KERN_DENSE);
     if (learn) {
-        int rc = resolve_S(m);
+        int rc = take_S(m, nullptr);
         if (rc) return rc;
     }
     VrxThetaFuse F{};
@@ -2888,21 +2901,15 @@ static int softmax_step(vrx_model* m, int update) {
     ProfScope ps(m, VRX_KERN_DENSE);
     hipStream_t s = m->p->stream;
     const double lu = -std::log((double)m->K);
-    const TiledStream& tcs = m->p->by_cell.tiled;
-    if (m->l_pending && tcs.split) {  // rows cut into pieces: their terms first
-        int rc = fold_split(m, tcs, m->RC.p);
-        if (rc) return rc;
-    }
-    const uint16_t* nr = m->l_pending ? tcs.npiece.p : nullptr;  // fused sum of the partials
-    const int32_t* vp = m->l_pending && tcs.split ? tcs.vptr.p : nullptr;  // ... of the pieces of long rows too
-    const int64_t nvr = m->l_pending ? tcs.n_vrows : m->M;
-    m->l_pending = false;
+    PassSum f;  // (fused sum of the partials, of the pieces of long rows too)
+    int rc = take_LID(m, &f);
+    if (rc) return rc;
     m->n_cell_part = m->nb_cell;
 #define VRX_SM_CASE(KPV)                                                                        \
     case KPV:                                                                                   \
         vrx_cell_softmax<KPV><<<dim3(m->nb_cell, m->R), VRX_BLOCK, 0, s>>>(                     \
-            m->M, m->K, update, m->LID.p, nr, m->RC.p, vp, nvr, m->logq_id.p, m->id_mode, lu, m->ID.p, \
-            m->part_cell.p, m->batch(), m->ctl.p);                                              \
+            m->M, m->K, update, m->LID.p, f.npiece, f.partial, f.vptr, f.n_vrows, m->logq_id.p, m->id_mode, lu, \
+            m->ID.p, m->part_cell.p, m->batch(), m->ctl.p);                                     \
         break;
     switch (m->KP) {
         VRX_SM_CASE(1)
@@ -2936,7 +2943,8 @@ static int flush_elbo(vrx_model* m) {
 }
 
 // shared-theta Vireo updates run vrx_theta_partial, which can carry the previous iteration's ELBO
-static bool elbo_can_ride(const vrx_model* m, int min_iter) {
+// (rule: the stop rule of the fit, inactive for vrx_model_run_iters)
+static bool elbo_can_ride(const vrx_model* m, const VrxStopRule& rule) {
     // Only where an iteration is short against a launch: when the rule fires, the next iteration's
     // variant pass has already run for nothing -- 8 us at c2 (a 29-us iteration minus 3 us, every
     // iteration), 0.3 ms at c3 (where one ELBO kernel per iteration is 1 % of it and a fit would
@@ -2944,12 +2952,13 @@ static bool elbo_can_ride(const vrx_model* m, int min_iter) {
     // 16 / 32 M: 10.5 / 6 / 4 / 2.8 % per iteration (profiles/r05_ab_elbo_ride_small_problems.txt);
     // the default stops at 2^25.  VIREO_ELBO_RIDE=0 / 1 forces it off / on (read per call).
     // Clone mode rides in vrx_bmm_theta, for the iterations whose stop rule cannot fire (it <=
-    // min_iter, see vrx_model_fit): its fits run min_iter >= 20 iterations by default
-    // (bmm_model.py:178), so there the rule is min_iter, not size -- nothing is ever wasted.
+    // min_iter, see enqueue_iterations): its fits run min_iter >= 20 iterations by default
+    // (bmm_model.py:178), so there the rule is min_iter, not size -- nothing is ever wasted;
+    // without a stop rule nothing is wasted either.
     const auto& c = m->cfg;
     if (c.kind == VRX_KIND_VIREO && (c.ase_mode || !c.learn_theta)) return false;
     const bool small = m->p->nnz * (int64_t)m->Kt < ((int64_t)1 << 25);
-    const bool dflt = small || (c.kind == VRX_KIND_BMM && min_iter >= 12);
+    const bool dflt = small || (c.kind == VRX_KIND_BMM && (!rule.active || rule.min_iter >= 12));
     return env_int("VIREO_ELBO_RIDE", dflt ? 1 : 0) != 0;
 }
 
@@ -2993,15 +3002,52 @@ static int enqueue_iteration(vrx_model* m, bool do_theta, const VrxStopRule& rul
     return elbo_step(m, rule);                 // ELBO + the stop rule, on the device
 }
 
+// The iterations of a fit or of a timed run: which update theta, and which leave their ELBO to
+// ride in the next iteration's theta launch
+struct Schedule {
+    VrxStopRule rule;  // (rule.it is set per iteration; active = 0: no stop rule)
+    int theta_from;    // the first iteration that updates theta (delay_fit_theta)
+    bool ride;         // elbo_can_ride, read once per call
+};
+
+static bool updates_theta(const vrx_model* m, const Schedule& sc, int it) {
+    return m->cfg.kind == VRX_KIND_VIREO && m->cfg.learn_theta && it >= sc.theta_from;
+}
+
+// Iterations [from, to).  The last one finalises its own ELBO (a fit's poll reads its stop word).
+static int enqueue_iterations(vrx_model* m, const Schedule& sc, int from, int to) {
+    for (int it = from; it < to; ++it) {
+        VrxStopRule rule = sc.rule;
+        rule.it = it;
+        // Vireo: an ELBO rides when the next iteration updates theta -- vrx_theta_partial writes
+        // S and partial sums only; the kernels that write state run behind the rider.
+        // Clone mode: vrx_bmm_theta WRITES model state (beta_mu, beta_sum, W), and its ordinary
+        // blocks read the stop word before the rider in the same launch has judged the previous
+        // iteration -- a stop found there would leave theta one update ahead of what
+        // bmm_model.py:190-199 breaks out with.  So an ELBO rides only while its rule cannot
+        // fire (it <= min_iter: `judge` of vrx_elbo_final_block is false); from min_iter + 1 on
+        // every iteration finalises its own.
+        const bool next_carries = m->cfg.kind == VRX_KIND_BMM ? !(rule.active && it > rule.min_iter)
+                                                               : updates_theta(m, sc, it + 1);
+        const bool defer = sc.ride && it + 1 < to && next_carries;
+        int rc = enqueue_iteration(m, updates_theta(m, sc, it), rule, defer);
+        if (rc) return rc;
+    }
+    return VRX_OK;
+}
+
 static int reset_ctl(vrx_model* m) {  // stop flag, stop iteration, warn flags (tickets stay 0)
     m->elbo_deferred = false;  // (a call that failed half-way may have left one waiting: dropped)
     VRX_HIP(hipMemsetAsync(m->ctl.p, 0, (size_t)m->R * VRX_CTL_WORDS * sizeof(int32_t), m->p->stream));
     return VRX_OK;
 }
 
+// the start of a fit / run of n iterations: an ELBO trace that holds them, clean control words,
 // psi / KL_theta (and, for fixed GT or BMM, W) consistent with the state just uploaded
-static int prepare(vrx_model* m) {
+static int prepare(vrx_model* m, int64_t n) {
     int rc;
+    if ((rc = ensure_trace(m, n))) return rc;
+    if ((rc = reset_ctl(m))) return rc;
     if ((rc = theta_step(m, 0))) return rc;
     if (m->cfg.kind == VRX_KIND_VIREO && !m->cfg.learn_gt)
         if ((rc = gt_step(m, 0))) return rc;
@@ -3014,14 +3060,10 @@ extern "C" int vrx_model_fit(vrx_model* m, int32_t max_iter, int32_t min_iter, d
     VRX_REQUIRE(m && elbo_trace && it_out, "vrx_model_fit: null argument");
     VRX_REQUIRE(max_iter >= 1, "vrx_model_fit: max_iter must be >= 1");
     VRX_HIP(hipSetDevice(m->p->device));
-    {   // (the reference takes any max_iter, vireo_model.py:251: its trace is np.zeros(max_iter))
-        int rc0 = ensure_trace(m, max_iter);
-        if (rc0) return rc0;
-    }
     hipStream_t s = m->p->stream;
     int rc;
-    if ((rc = reset_ctl(m))) return rc;
-    if ((rc = prepare(m))) return rc;
+    // (the reference takes any max_iter, vireo_model.py:251: its trace is np.zeros(max_iter))
+    if ((rc = prepare(m, max_iter))) return rc;
     // The stop rule runs on the device (vrx_elbo_final_block); the host enqueues a batch of
     // iterations, then reads three control words.  The first batch reaches the first iteration
     // the rule can fire at (min_iter + 1); a kernel launched after the stop returns at once, so
@@ -3037,37 +3079,23 @@ extern "C" int vrx_model_fit(vrx_model* m, int32_t max_iter, int32_t min_iter, d
     // iteration is long against a launch -- the criterion restarts.restart_batch uses.
     // VIREO_FIT_PIPELINE=1 / 0 forces it on / off (read per call: the tests switch it).
     const int pipeline = env_int("VIREO_FIT_PIPELINE", m->p->nnz * (int64_t)m->Kt >= ((int64_t)1 << 24) ? 1 : 0);
-    const bool ride = elbo_can_ride(m, min_iter);
+    VrxStopRule rule;
+    rule.it = 0;
+    rule.min_iter = min_iter;
+    rule.max_iter = max_iter;
+    rule.active = 1;
+    rule.eps = eps;
+    const Schedule sc{rule, delay_fit_theta, elbo_can_ride(m, rule)};
     const int R = m->R;  // elbo_trace [R][max_iter], it_out [R], warn_flags [R]
     // two pinned read-back buffers of R * VRX_CTL_WORDS <= 64 words inside h_pin (64 doubles)
     int32_t* hbuf[2] = {reinterpret_cast<int32_t*>(m->h_pin), reinterpret_cast<int32_t*>(m->h_pin) + 64};
     for (int b = 0; b < 2; ++b)
         if (!m->polled[b]) VRX_HIP(hipEventCreateWithFlags(&m->polled[b], hipEventDisableTiming));
-    int it = 0, next = 0, nb = 0;
+    int next = 0, nb = 0;
     auto enqueue_batch = [&]() -> int {  // iterations [next, upto) + the read-back of their control words
         const int upto = std::min(max_iter, next == 0 ? std::max(min_iter + 2, batch) : next + batch);
-        for (it = next; it < upto; ++it) {
-            VrxStopRule rule;
-            rule.it = it;
-            rule.min_iter = min_iter;
-            rule.max_iter = max_iter;
-            rule.active = 1;
-            rule.eps = eps;
-            const bool do_theta = m->cfg.kind == VRX_KIND_VIREO && m->cfg.learn_theta &&
-                                  it >= delay_fit_theta;
-            // (the last iteration of a batch finalises its ELBO itself: the poll reads its stop word)
-            // Clone mode: vrx_bmm_theta WRITES model state (beta_mu, beta_sum, W), and its ordinary
-            // blocks read the stop word before the rider in the same launch has judged the previous
-            // iteration -- a stop found there would leave theta one update ahead of what
-            // bmm_model.py:190-199 breaks out with.  So an ELBO rides only while its rule cannot
-            // fire (it <= min_iter: `judge` of vrx_elbo_final_block is false); from min_iter + 1 on
-            // every iteration finalises its own.  (Vireo's vrx_theta_partial writes S and partial
-            // sums only; the kernels that write state run behind the rider.)
-            const bool defer = ride && it + 1 < upto &&
-                               (m->cfg.kind == VRX_KIND_BMM ? it <= min_iter : it + 1 >= delay_fit_theta);
-            int rc2;
-            if ((rc2 = enqueue_iteration(m, do_theta, rule, defer))) return rc2;
-        }
+        int rc2 = enqueue_iterations(m, sc, next, upto);
+        if (rc2) return rc2;
         next = upto;
         VRX_HIP(hipMemcpyAsync(hbuf[nb & 1], m->ctl.p, (size_t)R * VRX_CTL_WORDS * sizeof(int32_t),
                                hipMemcpyDeviceToHost, s));
@@ -3097,7 +3125,7 @@ extern "C" int vrx_model_fit(vrx_model* m, int32_t max_iter, int32_t min_iter, d
         const int32_t* c = hctl + r * VRX_CTL_WORDS;
         any_stop = any_stop || c[VRX_CTL_STOP] != 0;
         // Python leaves `it` at the last executed index
-        it = c[VRX_CTL_STOP] ? c[VRX_CTL_IT] : max_iter - 1;
+        const int it = c[VRX_CTL_STOP] ? c[VRX_CTL_IT] : max_iter - 1;
         it_out[r] = it;
         if (warn_flags) warn_flags[r] = c[VRX_CTL_WARN];
         VRX_HIP(hipMemcpyAsync(elbo_trace + (size_t)r * max_iter, m->d_elbo.p + (size_t)r * m->trace_cap,
@@ -3114,22 +3142,12 @@ extern "C" int vrx_model_run_iters(vrx_model* m, int32_t n_iter, int32_t theta_f
                                    double* elbo_trace, double* ms_out) {
     VRX_REQUIRE(m && n_iter >= 1, "vrx_model_run_iters: bad argument");
     VRX_HIP(hipSetDevice(m->p->device));
-    {
-        int rc0 = ensure_trace(m, n_iter);
-        if (rc0) return rc0;
-    }
     hipStream_t s = m->p->stream;
     int rc;
-    if ((rc = reset_ctl(m))) return rc;
-    if ((rc = prepare(m))) return rc;
-    const bool ride = elbo_can_ride(m, 1 << 20);  // (no stop rule here: nothing is ever wasted)
+    if ((rc = prepare(m, n_iter))) return rc;
+    const Schedule sc{no_rule(0), theta_from_iter, elbo_can_ride(m, no_rule(0))};  // (no stop rule)
     VRX_HIP(hipEventRecord(m->t0, s));
-    for (int it = 0; it < n_iter; ++it) {
-        const bool do_theta = m->cfg.kind == VRX_KIND_VIREO && m->cfg.learn_theta &&
-                              it >= theta_from_iter;
-        const bool defer = ride && it + 1 < n_iter && (m->cfg.kind == VRX_KIND_BMM || it + 1 >= theta_from_iter);
-        if ((rc = enqueue_iteration(m, do_theta, no_rule(it), defer))) return rc;
-    }
+    if ((rc = enqueue_iterations(m, sc, 0, n_iter))) return rc;
     VRX_HIP(hipEventRecord(m->t1, s));
     VRX_HIP(hipStreamSynchronize(s));
     float ms = 0.f;
@@ -3267,6 +3285,30 @@ extern "C" int vrx_model_profile_read(vrx_model* m, double* ms_total, int64_t* l
 // ------------------------------------------------------------------------------------
 // one-shot cell log-likelihood against caller-supplied tables (doublet step)
 // ------------------------------------------------------------------------------------
+// psi1 / psi2 / psis, th values each -> the three planes of psi
+static int upload_psi(hipStream_t s, double* psi, const double* psi1, const double* psi2,
+                      const double* psis, size_t th) {
+    const double* src[3] = {psi1, psi2, psis};
+    for (int i = 0; i < 3; ++i)
+        VRX_HIP(hipMemcpyAsync(psi + i * th, src[i], th * sizeof(double), hipMemcpyHostToDevice, s));
+    return VRX_OK;
+}
+
+// W is in place: cell pass -> logLik; with prob_out, the ID prior and the softmax -> posterior
+static int loglik_and_posterior(vrx_model* m, const double* ID_prior, int64_t id_rows, double* logLik,
+                                double* prob_out) {
+    int rc;
+    if ((rc = cell_pass(m))) return rc;
+    if ((rc = d2h(m, logLik, m->LID, (size_t)(m->M * m->K)))) return rc;
+    if (prob_out) {
+        if ((rc = set_log_prior(m, m->logq_id, m->id_mode, ID_prior, id_rows, 1, m->K))) return rc;
+        if ((rc = softmax_step(m, 1))) return rc;
+        if ((rc = d2h(m, prob_out, m->ID, (size_t)(m->M * m->K)))) return rc;
+    }
+    VRX_HIP(hipStreamSynchronize(m->p->stream));
+    return VRX_OK;
+}
+
 extern "C" int vrx_problem_doublet(vrx_problem* p, int64_t n_donor, int64_t n_gt,
                                    const double* GT_prob, const double* psi1, const double* psi2,
                                    const double* psis, int64_t psi_rows, const double* ID_prior,
@@ -3298,26 +3340,13 @@ extern "C" int vrx_problem_doublet(vrx_problem* p, int64_t n_donor, int64_t n_gt
     VRX_HIP(gt.upload(GT_prob, n_gt_el, s));
     VRX_HIP(pairs.upload(hp.data(), hp.size(), s));
     VRX_HIP(psi.alloc(3 * th));
-    VRX_HIP(hipMemcpyAsync(psi.p, psi1, th * sizeof(double), hipMemcpyHostToDevice, s));
-    VRX_HIP(hipMemcpyAsync(psi.p + th, psi2, th * sizeof(double), hipMemcpyHostToDevice, s));
-    VRX_HIP(hipMemcpyAsync(psi.p + 2 * th, psis, th * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = upload_psi(s, psi.p, psi1, psi2, psis, th))) return rc;
     const int64_t n = p->n_var * C;
     vrx_doublet_w<<<(unsigned)((n + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, s>>>(
         p->n_var, (int)n_donor, (int)n_gt, (int)C, psi_rows == 1 ? 0 : 1, gt.p, pairs.p, psi.p,
         psi.p + th, psi.p + 2 * th, m->W.p, m->wform);
     VRX_HIP(hipGetLastError());
-    if ((rc = cell_pass(m))) return rc;
-    if ((rc = d2h(m, logLik, m->LID, (size_t)(m->M * m->K)))) return rc;
-    if (prob_out) {
-        if (id_rows > 0) {
-            if ((rc = upload_log_rows(m, m->logq_id, ID_prior, id_rows, m->K))) return rc;
-            m->id_mode = id_rows == 1 ? 1 : 2;
-        }
-        if ((rc = softmax_step(m, 1))) return rc;
-        if ((rc = d2h(m, prob_out, m->ID, (size_t)(m->M * m->K)))) return rc;
-    }
-    VRX_HIP(hipStreamSynchronize(s));
-    return VRX_OK;
+    return loglik_and_posterior(m, ID_prior, id_rows, logLik, prob_out);
 }
 
 extern "C" int vrx_problem_donor_reads(vrx_problem* p, int64_t n_col, const double* ID_prob,
@@ -3370,23 +3399,8 @@ extern "C" int vrx_problem_cell_loglik(vrx_problem* p, int64_t n_col, int64_t n_
     int rc = vrx_model_create(p, &cfg, &m);
     if (rc) return rc;
     std::unique_ptr<vrx_model> guard(m);
-    hipStream_t s = p->stream;
-    const size_t th = (size_t)(psi_rows * n_class);
     if ((rc = h2d(m, m->GT, GT, (size_t)m->NK * m->T))) return rc;
-    VRX_HIP(hipMemcpyAsync(m->psi.p, psi1, th * sizeof(double), hipMemcpyHostToDevice, s));
-    VRX_HIP(hipMemcpyAsync(m->psi.p + th, psi2, th * sizeof(double), hipMemcpyHostToDevice, s));
-    VRX_HIP(hipMemcpyAsync(m->psi.p + 2 * th, psis, th * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = upload_psi(p->stream, m->psi.p, psi1, psi2, psis, (size_t)(psi_rows * n_class)))) return rc;
     if ((rc = gt_step(m, 0))) return rc;
-    if ((rc = cell_pass(m))) return rc;
-    if ((rc = d2h(m, logLik, m->LID, (size_t)(m->M * m->K)))) return rc;
-    if (prob_out) {
-        if (id_rows > 0) {
-            if ((rc = upload_log_rows(m, m->logq_id, ID_prior, id_rows, m->K))) return rc;
-            m->id_mode = id_rows == 1 ? 1 : 2;
-        }
-        if ((rc = softmax_step(m, 1))) return rc;
-        if ((rc = d2h(m, prob_out, m->ID, (size_t)(m->M * m->K)))) return rc;
-    }
-    VRX_HIP(hipStreamSynchronize(s));
-    return VRX_OK;
+    return loglik_and_posterior(m, ID_prior, id_rows, logLik, prob_out);
 }
