@@ -233,6 +233,26 @@ int vrx_problem_cell_loglik(vrx_problem* p, int64_t n_col, int64_t n_class,
                             double* logLik /* n_cell x n_col */,
                             double* prob_out /* n_cell x n_col, may be NULL */);
 
+/* ---- ambient RNA (vrx_ambient.h) ---------------------------------------------------------
+ * vrx_problem_elbo_gain: gain[n_var] of variant_ELBO_gain(ID_prob, AD, DP, pseudocount)
+ * (vireoSNP/utils/variant_select.py:66-106): one variant pass for AD@ID, DP@ID and the row sums
+ * (BD@ID = DP@ID - AD@ID), then the digamma / logsumexp per variant on the device. */
+int vrx_problem_elbo_gain(vrx_problem* p, int64_t n_col, const double* ID_prob /* n_cell x n_col */,
+                          double pseudocount, double* gain /* n_var */);
+/* The per-cell EM of predit_ambient (vireoSNP/utils/vireo_doublet.py:213-273, _fit_EM_ambient :139-210),
+ * every cell in one launch: the cells' entries of the selected variants with dp > 0 are compacted from the
+ * problem's cell orientation (count, scan, scatter), then one wave per cell runs the EM from psi_init
+ * with the reference's stop rule (min_iter, max_iter, epsilon), its returned log-likelihood
+ * logLik[it - 1], the Cramer-Rao variance and the likelihood ratio against the one-hot psi at the
+ * first maximum.  theta: n_var x n_donor (the caller's np.tensordot(GT_prob, beta_mu[0])), selected: one
+ * byte per variant.  n_iter: the reference's loop index at exit.  A cell without selected counts gets
+ * NaN psi / var / llr and n_iter = max_iter - 1, as in the reference.  ms3 (may be NULL): milliseconds of
+ * the compaction, the EM kernel and the download. */
+int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double* theta, const uint8_t* selected,
+                        const double* psi_init /* n_cell x n_donor */, int32_t min_iter, int32_t max_iter,
+                        double epsilon, double* psi /* n_cell x n_donor */, double* var /* n_cell x n_donor */,
+                        double* llr /* n_cell */, int32_t* n_iter /* n_cell */, double* ms3);
+
 /* ---- timing (bench.py roofline leg) ---------------------------------------------------
  * When enabled, every launch of a pass kernel is bracketed by hipEvents on the model's
  * stream; totals are read back after a sync.  Kernel ids: */

@@ -72,6 +72,9 @@ SIGNATURES = {
                                       C.c_int64, _D, _D]),
     "vrx_problem_cell_loglik": (C.c_int, [_P, C.c_int64, C.c_int64, _D, _D, _D, _D, C.c_int64, _D,
                                           C.c_int64, _D, _D]),
+    "vrx_problem_elbo_gain": (C.c_int, [_P, C.c_int64, _D, C.c_double, _D]),
+    "vrx_problem_ambient": (C.c_int, [_P, C.c_int64, _D, C.POINTER(C.c_uint8), _D, C.c_int32, C.c_int32,
+                                      C.c_double, _D, _D, _D, _I32, _D]),
     "vrx_model_info": (C.c_int, [_P, _I32]),
     "vrx_model_profile": (C.c_int, [_P, C.c_int32]),
     "vrx_model_profile_read": (C.c_int, [_P, _D, _I64]),

@@ -150,6 +150,10 @@ struct vrx_problem {
     bool want_balance = false;     // vrx_problem_create2 flag VRX_PROBLEM_BALANCED (TiledStream::perm)
     double balance_seconds = 0.0;  // what the balanced slabs added to the build (both orientations)
     bool device_built = false;     // both orientations built by vrx_build.h (streams only, no gather tables)
+    // n_cell + 1 offsets of every cell's entries in by_cell.ent (every build route packs that array in
+    // the input's CSC order with original variant indices; the balanced slabs relabel only the tiled
+    // streams): what vrx_problem_ambient gathers a cell's entries by
+    DevBuf<int64_t> cell_ptr;
 };
 
 // vrx_comm.hip broadcasts a model's variational state in place (vrx_comm_bcast_model): the four

@@ -15,6 +15,7 @@
 #include "vrx_common.h"
 #include "vrx_kernels.h"
 #include "vrx_build.h"
+#include "vrx_ambient.h"
 
 // (vrx_set_error / vrx_last_error: vrx_host.cpp, so that the host-only translation unit links on
 //  its own for the sanitizer build of tests/test_host_sanitizers_cpu.py)
@@ -1584,15 +1585,13 @@ static int problem_create2(int device, int64_t n_var, int64_t n_cell, int64_t nn
     const bool force_dev = bm && !strcmp(bm, "device"), force_host = bm && !strcmp(bm, "host");
     const bool big = nnz >= plan.min_nnz_cell && nnz >= plan.min_nnz_var;
     int rc;
+    bool built = false;
     if (!force_host && plan.lds != 0 && (force_dev || big)) {
-        bool built = false;
         if ((rc = device_build(p.get(), colptr, rowidx, ad, dp, plan, &built))) return rc;
-        if (built) {
-            *out = p.release();
-            return VRX_OK;
-        }
     }
-    if ((rc = host_build(p.get(), colptr, rowidx, ad, dp, plan))) return rc;
+    if (!built && (rc = host_build(p.get(), colptr, rowidx, ad, dp, plan))) return rc;
+    VRX_HIP(p->cell_ptr.upload(colptr, (size_t)n_cell + 1, p->stream));
+    VRX_HIP(hipStreamSynchronize(p->stream));  // (the caller's colptr may go at return)
     *out = p.release();
     return VRX_OK;
 }
@@ -3403,4 +3402,138 @@ extern "C" int vrx_problem_cell_loglik(vrx_problem* p, int64_t n_col, int64_t n_
     if ((rc = upload_psi(p->stream, m->psi.p, psi1, psi2, psis, (size_t)(psi_rows * n_class)))) return rc;
     if ((rc = gt_step(m, 0))) return rc;
     return loglik_and_posterior(m, ID_prior, id_rows, logLik, prob_out);
+}
+
+// ---- ambient RNA (vrx_ambient.h) ------------------------------------------------------------
+
+extern "C" int vrx_problem_elbo_gain(vrx_problem* p, int64_t n_col, const double* ID_prob,
+                                     double pseudocount, double* gain) {
+    VRX_REQUIRE(p && ID_prob && gain, "vrx_problem_elbo_gain: null argument");
+    VRX_REQUIRE(n_col >= 1 && n_col < INT32_MAX - 1, "vrx_problem_elbo_gain: bad shape");
+    // one variant pass with ID_prob and a column of ones: AD@ID, DP@ID and the row sums together
+    const int64_t K1 = n_col + 1, M = p->n_cell, N = p->n_var;
+    std::vector<double> id1((size_t)(M * K1));
+    for (int64_t c = 0; c < M; ++c) {
+        std::memcpy(&id1[(size_t)(c * K1)], ID_prob + c * n_col, (size_t)n_col * sizeof(double));
+        id1[(size_t)(c * K1 + n_col)] = 1.0;
+    }
+    vrx_model_cfg cfg{};
+    cfg.kind = VRX_KIND_BMM;  // no genotype layer needed: only ID_prob and S
+    cfg.n_donor = (int32_t)K1;
+    vrx_model* m = nullptr;
+    int rc = vrx_model_create(p, &cfg, &m);
+    if (rc) return rc;
+    std::unique_ptr<vrx_model> guard(m);
+    if ((rc = h2d(m, m->ID, id1.data(), id1.size()))) return rc;
+    if ((rc = variant_pass(m))) return rc;
+    DevBuf<double> d_gain;
+    VRX_HIP(d_gain.alloc((size_t)N));
+    vrx_amb_gain<<<(unsigned)((N + VRX_BLOCK - 1) / VRX_BLOCK), VRX_BLOCK, 0, p->stream>>>(
+        N, (int)K1, pseudocount, m->S.p, d_gain.p);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(hipMemcpyAsync(gain, d_gain.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    VRX_HIP(hipStreamSynchronize(p->stream));
+    return VRX_OK;
+}
+
+template <int FMT>
+static int amb_compact(vrx_problem* p, const int32_t* d_rank, DevBuf<int64_t>& sptr, DevBuf<int32_t>& ev,
+                       DevBuf<int32_t>& ea, DevBuf<int32_t>& eb) {
+    const int64_t M = p->n_cell;
+    hipStream_t s = p->stream;
+    const unsigned nb = (unsigned)((M + VRX_AMB_CELLS - 1) / VRX_AMB_CELLS);
+    VRX_HIP(sptr.alloc((size_t)M + 1));
+    VRX_HIP(hipMemsetAsync(sptr.p, 0, sizeof(int64_t), s));
+    vrx_amb_count<FMT><<<nb, 64 * VRX_AMB_CELLS, 0, s>>>(M, p->cell_ptr.p, p->by_cell.ent.p, d_rank, sptr.p + 1);
+    VRX_HIP(hipGetLastError());
+    size_t tmp_bytes = 0;
+    VRX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, sptr.p + 1, sptr.p + 1, (size_t)M, s));
+    DevBuf<char> tmp;
+    VRX_HIP(tmp.alloc(tmp_bytes));
+    VRX_HIP(hipcub::DeviceScan::InclusiveSum(tmp.p, tmp_bytes, sptr.p + 1, sptr.p + 1, (size_t)M, s));
+    int64_t total = 0;
+    VRX_HIP(hipMemcpyAsync(&total, sptr.p + M, sizeof total, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    VRX_HIP(ev.alloc((size_t)std::max<int64_t>(total, 1)));
+    VRX_HIP(ea.alloc((size_t)std::max<int64_t>(total, 1)));
+    VRX_HIP(eb.alloc((size_t)std::max<int64_t>(total, 1)));
+    vrx_amb_scatter<FMT><<<nb, 64 * VRX_AMB_CELLS, 0, s>>>(M, p->cell_ptr.p, p->by_cell.ent.p, d_rank, sptr.p,
+                                                           ev.p, ea.p, eb.p);
+    VRX_HIP(hipGetLastError());
+    return VRX_OK;
+}
+
+extern "C" int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double* theta,
+                                   const uint8_t* selected, const double* psi_init, int32_t min_iter,
+                                   int32_t max_iter, double epsilon, double* psi, double* var,
+                                   double* llr, int32_t* n_iter, double* ms3) {
+    VRX_REQUIRE(p && theta && selected && psi_init && psi && var && llr && n_iter,
+                "vrx_problem_ambient: null argument");
+    VRX_REQUIRE(n_donor >= 1 && n_donor <= 4096, "vrx_problem_ambient: n_donor must be 1..4096");
+    VRX_REQUIRE(max_iter >= 2 && min_iter >= 0, "vrx_problem_ambient: max_iter >= 2, min_iter >= 0");
+    VRX_REQUIRE(p->cell_ptr.n == (size_t)p->n_cell + 1 && p->by_cell.ent.p, "vrx_problem_ambient: no cell entries");
+    VRX_HIP(hipSetDevice(p->device));
+    const int K = (int)n_donor;
+    const int64_t N = p->n_var, M = p->n_cell;
+    hipStream_t s = p->stream;
+    // the selected rows of theta, and every variant's row among them (-1: not selected)
+    std::vector<int32_t> rank((size_t)N);
+    std::vector<double> th_sel;
+    int32_t n_sel = 0;
+    for (int64_t v = 0; v < N; ++v) {
+        rank[(size_t)v] = selected[v] ? n_sel++ : -1;
+        if (selected[v]) th_sel.insert(th_sel.end(), theta + v * K, theta + (v + 1) * K);
+    }
+    if (th_sel.empty()) th_sel.assign((size_t)K, 0.5);
+    hipEvent_t ev_t[4] = {};
+    struct EventGuard {
+        hipEvent_t* e;
+        ~EventGuard() {
+            for (int i = 0; i < 4; ++i)
+                if (e[i]) (void)hipEventDestroy(e[i]);
+        }
+    } eg{ev_t};
+    for (auto& e : ev_t) VRX_HIP(hipEventCreate(&e));
+    DevBuf<int32_t> d_rank, ev, ea, eb;
+    DevBuf<double> d_theta, d_psi0, d_psi, d_var, d_llr;
+    DevBuf<int32_t> d_it;
+    DevBuf<int64_t> sptr;
+    VRX_HIP(d_rank.upload(rank.data(), rank.size(), s));
+    VRX_HIP(d_theta.upload(th_sel.data(), th_sel.size(), s));
+    VRX_HIP(d_psi0.upload(psi_init, (size_t)(M * K), s));
+    VRX_HIP(d_psi.alloc((size_t)(M * K)));
+    VRX_HIP(d_var.alloc((size_t)(M * K)));
+    VRX_HIP(d_llr.alloc((size_t)M));
+    VRX_HIP(d_it.alloc((size_t)M));
+    VRX_HIP(hipEventRecord(ev_t[0], s));
+    int rc = p->by_cell.fmt == VRX_FMT_P32   ? amb_compact<VRX_FMT_P32>(p, d_rank.p, sptr, ev, ea, eb)
+             : p->by_cell.fmt == VRX_FMT_P64 ? amb_compact<VRX_FMT_P64>(p, d_rank.p, sptr, ev, ea, eb)
+                                             : amb_compact<VRX_FMT_WIDE>(p, d_rank.p, sptr, ev, ea, eb);
+    if (rc) return rc;
+    VRX_HIP(hipEventRecord(ev_t[1], s));
+    // theta rows of a cell's entries stay in LDS up to this budget per wave (VIREO_AMBIENT_LDS bytes)
+    const size_t budget = (size_t)std::max(env_int("VIREO_AMBIENT_LDS", 16384), 0);
+    const size_t fixed = vrx_amb_lds_bytes(K, 0);
+    const int cap = budget > fixed ? (int)std::min<size_t>((budget - fixed) / ((size_t)(K | 1) * sizeof(double)), INT32_MAX)
+                                   : 0;
+    const size_t lds = vrx_amb_lds_bytes(K, cap);
+    VRX_REQUIRE(lds <= 64 * 1024, "vrx_problem_ambient: %zu bytes of LDS per cell (n_donor too large)", lds);
+    vrx_amb_em<<<(unsigned)M, 64, lds, s>>>(K, sptr.p, ev.p, ea.p, eb.p, d_theta.p, d_psi0.p, min_iter, max_iter,
+                                            epsilon, cap, d_psi.p, d_var.p, d_llr.p, d_it.p);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(hipEventRecord(ev_t[2], s));
+    VRX_HIP(hipMemcpyAsync(psi, d_psi.p, (size_t)(M * K) * sizeof(double), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(var, d_var.p, (size_t)(M * K) * sizeof(double), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(llr, d_llr.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(n_iter, d_it.p, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipEventRecord(ev_t[3], s));
+    VRX_HIP(hipStreamSynchronize(s));
+    if (ms3) {
+        float t;
+        for (int i = 0; i < 3; ++i) {
+            VRX_HIP(hipEventElapsedTime(&t, ev_t[i], ev_t[i + 1]));
+            ms3[i] = t;
+        }
+    }
+    return VRX_OK;
 }

@@ -145,7 +145,8 @@ def _write_table_gz(path, header, row_names, table):
 
 
 def write_donor_id(out_dir, donor_names, cell_names, n_vars, res_vireo):
-    """donor_ids.tsv, summary.tsv, prob_singlet.tsv.gz, prob_doublet.tsv.gz, _log.txt with the
+    """donor_ids.tsv, summary.tsv, prob_singlet.tsv.gz, prob_doublet.tsv.gz, _log.txt (and
+    prop_ambient.tsv when the result carries ambient_Psi) with the
     reference's thresholds (prob_max < 0.9 -> unassigned, doublet >= 0.9, n_vars < 10 ->
     unassigned) and number formats (io_utils.py:91-170)."""
     ID_prob, doublet_prob = res_vireo['ID_prob'], res_vireo['doublet_prob']
@@ -179,6 +180,14 @@ def write_donor_id(out_dir, donor_names, cell_names, n_vars, res_vireo):
             f.write("\t".join([cell_names[i], donor_ids[i], "%.2e" % prob_max[i],
                                "%.2e" % prob_dbl[i], "%d" % n_vars[i], best_singlet[i],
                                best_doublet[i], "%.3f" % res_vireo['doublet_LLR'][i]]) + "\n")
+
+    if res_vireo.get('ambient_Psi') is not None:      # io_utils.py:157-164, not gzipped
+        psi, llr = res_vireo['ambient_Psi'], res_vireo['Psi_LLRatio']
+        with open(out_dir + "/prop_ambient.tsv", "w") as f:
+            f.write("\t".join(["cell"] + list(donor_names) + ['logLik_ratio']) + "\n")
+            for i in range(len(cell_names)):
+                f.write("\t".join([cell_names[i]] + ["%.4e" % x for x in psi[i, :]] +
+                                   ["%.2f" % llr[i]]) + "\n")
 
     for name, header, table in (("prob_singlet.tsv", donor_names, ID_prob),
                                 ("prob_doublet.tsv", pair_names, doublet_prob)):

@@ -6,8 +6,9 @@ registered as ``vireo`` in setup.py:53-55):
     python -m vireo_amd.vireo -c CELL_DATA -N n_donor -o OUT_DIR [-d DONOR_VCF] ...
 
 The model fits run on the GPU (vireo_amd.vireo_wrap); loading and writing text files is
-host work.  Not carried over: the genotype-distance figure (``--noPlot`` is accepted and
-is the only behaviour) and ``--callAmbientRNAs`` (experimental upstream, vireo.py:79-81).
+host work.  ``--callAmbientRNAs`` (vireo.py:79-81) runs the per-cell ambient-RNA EM on the GPU
+and writes prop_ambient.tsv.  Not carried over: the genotype-distance figure (``--noPlot`` is
+accepted and is the only behaviour).
 """
 import os
 import sys
@@ -63,7 +64,8 @@ _MODEL_OPTIONS = [
     (("--randSeed",), "rand_seed", int, None, "seed of the restarts [default: %default]"),
     (("--cellRange",), "cell_range", "str", None, "cells to process, e.g. 0-10000 [default: all]"),
     (("--callAmbientRNAs",), "check_ambient", "flag", False,
-     "not available in vireo_amd (experimental upstream)"),
+     "if use, detect ambient RNAs in each cell (one EM per cell on the GPU; "
+     "writes prop_ambient.tsv)"),
     (("--nproc", "-p"), "nproc", int, 1,
      "accepted; the restarts run on the GPU [default: %default]"),
     (("--nGPU",), "n_gpu", int, 1,

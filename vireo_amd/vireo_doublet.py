@@ -1,13 +1,19 @@
-"""Doublet prediction with a fitted Vireo model, drop-in for
-vireoSNP/utils/vireo_doublet.py:11-136 (``predict_doublet`` and its two table builders).
+"""Doublet prediction and ambient-RNA estimation with a fitted Vireo model, drop-in for
+vireoSNP/utils/vireo_doublet.py:11-273 (``predict_doublet``, its two table builders and
+``predit_ambient``).
 
 The K + K(K-1)/2 column cell log-likelihood -- 3*6 transposed sparse products in the
 reference (:53-62) -- is one cell pass on the GPU (``vrx_problem_doublet``); the genotype
 table of the donor pairs (653 MB at N=100k, K=16 in the reference) is formed on the fly in
 the kernel, and the 6 pair thetas are host-side arithmetic on 3 numbers.  ``add_doublet_GT``
 is kept as a public helper (and for n_GT > 3).
+
+``predit_ambient`` (the reference's spelling) fits one small EM per cell; here every cell is fitted
+in one launch (``vrx_problem_ambient``, vireo_amd/csrc/vrx_ambient.h).
 """
+import ctypes as C
 import itertools
+import timeit
 
 import numpy as np
 from scipy.special import digamma
@@ -15,7 +21,10 @@ from scipy.special import digamma
 from . import _lib
 from ._lib import dptr, f64
 from .counts import device_counts
+from .variant_select import variant_ELBO_gain
 from .vireo_base import normalize
+
+LAST_AMBIENT = {}    # the split of the last predit_ambient call (read by tests/perf/ambient_bench.py)
 
 
 def add_doublet_theta(beta_mu, beta_sum):
@@ -92,3 +101,40 @@ def predict_doublet(vobj, AD, DP, update_GT=True, update_ID=True,
         else:
             print("For update_GT, please turn on update_ID.")
     return (ID_prob_both[:, vobj.n_donor:], ID_prob_both[:, :vobj.n_donor], logLik_ratio)
+
+
+def predit_ambient(vobj, AD, DP, nproc=10, min_ELBO_gain=None):
+    """-> (Psi_mat (n_cell, K), Psi_var (n_cell, K), Psi_logLik_ratio (n_cell,)): the fraction of
+    each donor's RNA in every cell, its Cramer-Rao variance and the log-likelihood ratio against
+    the cell's main donor alone (vireo_doublet.py:213-273).  Variants are selected by
+    ``variant_ELBO_gain >= min_ELBO_gain`` (default sqrt(n_cell) / 3); each cell's EM starts
+    from ``np.random.dirichlet`` draws of the global stream, cell after cell -- the reference's
+    ``nproc=1`` sequence.  ``nproc`` is accepted and ignored."""
+    start = timeit.default_timer()
+    counts = device_counts(AD, DP)
+    n_cell, K = counts.n_cell, vobj.GT_prob.shape[1]
+    theta_mat = f64(np.tensordot(vobj.GT_prob, vobj.beta_mu[0, :], axes=(2, 0)))
+    if min_ELBO_gain is None:
+        min_ELBO_gain = np.sqrt(n_cell) / 3.0
+    t0 = timeit.default_timer()
+    gain = variant_ELBO_gain(vobj.ID_prob, counts, None)
+    sel = gain >= min_ELBO_gain
+    print("[vireo] %d out %d SNPs selected for ambient RNA detection: "
+          "ELBO_gain > %.1f" % (sum(sel), len(sel), min_ELBO_gain))
+    t1 = timeit.default_timer()
+    psi0 = f64(np.random.dirichlet([1] * K, size=n_cell))
+    t2 = timeit.default_timer()
+    psi, var = np.empty((n_cell, K)), np.empty((n_cell, K))
+    llr, n_iter, ms = np.empty(n_cell), np.empty(n_cell, np.int32), np.zeros(3)
+    mask = np.ascontiguousarray(sel, dtype=np.uint8)
+    _lib.check(_lib.lib().vrx_problem_ambient(
+        counts.handle, K, dptr(theta_mat), mask.ctypes.data_as(C.POINTER(C.c_uint8)), dptr(psi0),
+        20, 200, 1e-3, dptr(psi), dptr(var), dptr(llr), n_iter.ctypes.data_as(C.POINTER(C.c_int32)),
+        dptr(ms)))
+    stop = timeit.default_timer()
+    LAST_AMBIENT.clear()
+    LAST_AMBIENT.update(gain_s=t1 - t0, draws_s=t2 - t1, compaction_ms=ms[0], em_ms=ms[1],
+                        download_ms=ms[2], call_s=stop - t2, total_s=stop - start,
+                        n_selected=int(sel.sum()), n_iter=n_iter)
+    print('[vireo] Ambient RNA time: %.1f sec' % (stop - start))
+    return psi, var, llr

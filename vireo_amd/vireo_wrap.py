@@ -1,5 +1,5 @@
 """``vireo_wrap``: multiple random restarts, model selection, optional extra-donor search /
-genotype-prior alignment, doublets -- drop-in for vireoSNP/utils/vireo_wrap.py:22-183.
+genotype-prior alignment, doublets, ambient RNA -- drop-in for vireoSNP/utils/vireo_wrap.py:22-183.
 
 Every fit runs on the GPU.  ``nproc`` is accepted for compatibility (the reference's
 multiprocessing.Pool, vireo_wrap.py:74-83) and ignored: restarts are instead sharded
@@ -23,7 +23,7 @@ from .dist import LocalComm, gather_restart_elbos, my_restarts
 from . import restarts as restarts_mod
 from .restarts import DeviceRestarts, LegacyStream, _phase
 from .vireo_base import donor_select, normalize, optimal_match
-from .vireo_doublet import predict_doublet
+from .vireo_doublet import predict_doublet, predit_ambient
 from .vireo_model import Vireo
 
 _INIT_KEYS = ("ID_prob_init", "GT_prob_init", "beta_mu_init", "beta_sum_init")
@@ -287,13 +287,14 @@ def _report(model):
     print("\t".join("%.0f" % s for s in sizes))
 
 
-def _result(model, ID_prob, doublet_prob, doublet_LLR, elbo_all):
+def _result(model, ID_prob, doublet_prob, doublet_LLR, elbo_all, ambient):
     """the reference's result dict (vireo_wrap.py:170-183)"""
     s1, s2 = model.beta_mu * model.beta_sum, (1 - model.beta_mu) * model.beta_sum
     return dict(ID_prob=ID_prob, GT_prob=model.GT_prob, doublet_LLR=doublet_LLR,
                 doublet_prob=doublet_prob, theta_shapes=np.append(s1, s2, axis=0),
-                theta_mean=model.beta_mu, theta_sum=model.beta_sum, ambient_Psi=None,
-                Psi_var=None, Psi_LLRatio=None, LB_list=elbo_all, LB_doublet=model.ELBO_[-1])
+                theta_mean=model.beta_mu, theta_sum=model.beta_sum, ambient_Psi=ambient[0],
+                Psi_var=ambient[1], Psi_LLRatio=ambient[2], LB_list=elbo_all,
+                LB_doublet=model.ELBO_[-1])
 
 
 def vireo_wrap(AD, DP, GT_prior=None, n_donor=None, learn_GT=True, n_init=20,
@@ -307,9 +308,6 @@ def vireo_wrap(AD, DP, GT_prior=None, n_donor=None, learn_GT=True, n_init=20,
     # every restart and the final fit run on ONE device problem (vireo_wrap.py:64-94): tell the builder how
     # many iterations that is, so that it can spend a one-off effort that pays back over them
     counts = device_counts(AD, DP, expected_iterations=-(-plan.n_init // comm.world) * max_iter_init + 200)
-    if check_ambient:
-        raise NotImplementedError("check_ambient (experimental in the reference, "
-                                  "vireo.py:79-81) is out of scope of vireo_amd")
     if random_seed is not None:                       # the ONLY seeding, vireo_wrap.py:53-54
         np.random.seed(random_seed)
 
@@ -332,4 +330,7 @@ def vireo_wrap(AD, DP, GT_prior=None, n_donor=None, learn_GT=True, n_init=20,
         n_cell, K = counts.shape[1], plan.n_donor
         ID_prob, doublet_LLR = model.ID_prob, np.zeros(n_cell)
         doublet_prob = np.zeros((n_cell, int(K * (K - 1) / 2)))
-    return _result(model, ID_prob, doublet_prob, doublet_LLR, elbo_all)
+    # vireo_wrap.py:161-168: on the final (doublet-updated) model; every rank runs it on its own
+    # device from the same global stream, and the kernels are deterministic, so the ranks agree
+    ambient = predit_ambient(model, counts, None, nproc=nproc) if check_ambient else (None, None, None)
+    return _result(model, ID_prob, doublet_prob, doublet_LLR, elbo_all, ambient)
