@@ -268,8 +268,7 @@ int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double* theta, co
  * words (padding included) per 1000 non-zeros; info[10]/[11] = extra row pieces (long rows are
  * cut into interleaved pieces); info[12] = form of the LDS-resident cell stream (0: (ad, dp)
  * pairs, 1: single-valued AD / BD entries); info[13] = form of the variant stream (0: pairs,
- * 2: AD entries then BD entries per round, 3: AD / BD entries as 2N single-accumulator virtual
- * rows -- the cell pass's kernel); info[14] = restarts in the model (n_batch); info[15]
+ * 3: AD / BD entries as 2N single-accumulator virtual rows -- the cell pass's kernel); info[14] = restarts in the model (n_batch); info[15]
  * = longest / mean wave stream of the tiled streams x 1000 (variant: low 16 bits, cell: high 16).  The forms follow
  * the depth of the data: AD/BD words unless a count needs so many of them (> 1.56 words per
  * entry, estimated at vrx_problem_create) that one pair word per entry is cheaper. */

@@ -418,23 +418,23 @@ def test_lds_resident_passes_vs_oracle(va, monkeypatch, fmt, blocks, sort):
         close(dev.GT_prob, ref.GT_prob)
 
 
-@pytest.mark.parametrize("top,var_form", [(2047, 0), (2048, 0), (7, 2), (2048, 2), (16383, 2),
-                                          (16384, 2), (90000, 2), (7, 3), (16384, 3), (90000, 3)])
+@pytest.mark.parametrize("top,var_form", [(2047, 0), (2048, 0), (7, 3), (2048, 3), (16383, 3),
+                                          (16384, 3), (90000, 3)])
 def test_lds_count_limit_and_tiny_shapes(va, monkeypatch, top, var_form):
-    """The single-valued AD / BD words (cell stream, FORM 1; variant stream, FORM 2: the
-    default) carry the top bits of the value's double and cut a count with more than three
-    significant bits into several entries, so the LDS-resident passes take any count (7 / 2048 /
-    16383 / 16384: chunk boundaries; 90000: data/mitoDNA-like depth).  The (ad, dp) pair words of
-    the older variant stream (VIREO_VAR_FORM=0) hold counts < 2048: at the limit that pass is
-    used, one above it silently stays on the global-gather kernel.  Shapes smaller than one
-    tile / one slab (N=70 variants, M=40 cells) and a single contracted range."""
+    """The single-valued AD / BD words (cell stream, FORM 1; variant stream over virtual rows,
+    VIREO_VAR_FORM=3: the default) carry the top bits of the value's double and cut a count with
+    more than three significant bits into several entries, so the LDS-resident passes take any
+    count (7 / 2048 / 16383 / 16384: chunk boundaries; 90000: data/mitoDNA-like depth).  The
+    (ad, dp) pair words of the variant stream (VIREO_VAR_FORM=0) hold counts < 2048: at the limit
+    that pass is used, one above it silently stays on the global-gather kernel.  Shapes smaller
+    than one tile / one slab (N=70 variants, M=40 cells) and a single contracted range."""
     from vireo_amd import _lib
     from vireo_amd.counts import DeviceCounts
     from vireo_amd.engine import DeviceModel
     monkeypatch.setenv("VIREO_LDS", "1")
     monkeypatch.setenv("VIREO_VAR_FORM", str(var_form))
     monkeypatch.setenv("VIREO_CELL_FORM", "1")     # (counts this deep would pick pair words)
-    expect_lds = var_form >= 2 or top < 2048
+    expect_lds = var_form == 3 or top < 2048
     rng = np.random.default_rng(5)
     dp = (rng.random((70, 40)) < 0.3) * rng.integers(1, 60, (70, 40))
     dp[3, 7] = top
@@ -454,6 +454,25 @@ def test_lds_count_limit_and_tiny_shapes(va, monkeypatch, top, var_form):
     close(dev.ELBO_, ref.ELBO_)
     close(dev.ID_prob, ref.ID_prob)
     close(dev.GT_prob, ref.GT_prob)
+
+
+@pytest.mark.parametrize("name,value", [("VIREO_VAR_FORM", "2"), ("VIREO_VAR_FORM", "1"),
+                                        ("VIREO_CELL_FORM", "2"), ("VIREO_CELL_FORM", "3")])
+@pytest.mark.parametrize("build", ["host", "device"])
+def test_unknown_stream_form_is_refused(va, monkeypatch, name, value, build):
+    """VIREO_CELL_FORM takes 0 / 1 and VIREO_VAR_FORM 0 / 3: any other value fails the problem's
+    creation, on either builder, with an error that names the switch (the cell stream of form 2
+    once reached the pair-word kernel as 128-B AD / BD words)"""
+    from vireo_amd import _lib
+    from vireo_amd.counts import DeviceCounts
+    monkeypatch.setenv("VIREO_LDS", "1")
+    monkeypatch.setenv("VIREO_BUILD", build)
+    monkeypatch.setenv(name, value)
+    rng = np.random.default_rng(6)
+    dp = (rng.random((70, 40)) < 0.3) * rng.integers(1, 60, (70, 40))
+    AD, DP = csc_matrix(rng.binomial(dp, 0.3)), csc_matrix(dp)
+    with pytest.raises(_lib.VrxError, match=name):
+        DeviceCounts(AD, DP)
 
 
 @pytest.mark.parametrize("N,M,K,top,fill", [(50, 40000, 5, 6, "1"), (50, 40000, 5, 6, "0"),

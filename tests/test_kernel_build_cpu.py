@@ -60,11 +60,12 @@ def _instances(report):
     return out
 
 
-def test_ad_bd_instances_do_not_spill(isa):
+def test_ad_bd_instances_are_the_cell_pass_and_do_not_spill(isa):
     _, report = isa
     inst = _instances(report)
-    hot = {k: v for k, v in inst.items() if v["form"] != 0}
-    assert len(hot) >= 9          # cell pass RW 96 / 32 and variant pass x flat / 16-B-unit / element-wise staging
+    hot = {(v["lpe"], v["mode"], v["rw"], v["padk"], v["split"], v["form"]) for v in inst.values() if v["form"] != 0}
+    # the AD/BD cell pass (cell stream and variant virtual rows): RW 96 / 32 x flat / element-wise / 16-B units
+    assert hot == {(4, 1, rw, padk, 1, 1) for rw in (96, 32) for padk in (0, 1, 2)}, sorted(hot)
     lines = ["%-8s %-5s %-4s %-5s %-5s  VGPRs spill scratch occupancy" % ("form", "mode", "RW", "PADK", "SPLIT")]
     for k, v in sorted(inst.items(), key=lambda kv: (-kv[1]["form"], kv[1]["mode"], kv[1]["rw"], kv[1]["padk"], kv[1]["split"])):
         lines.append("%-8d %-5d %-4d %-5d %-5d  %5d %5d %7d %9d" % (

@@ -293,7 +293,7 @@ struct TileRows {
     int64_t n_rows, n_contract, nnz;
     bool virt;
 };
-// The stream asked for: rows per wave, slab height, word form (0 pairs, 1 AD / BD words, 2 AD / BD phases),
+// The stream asked for: rows per wave, slab height, word form (0 pairs, 1 AD / BD words),
 // pass (0 variant, 1 cell), the padding guard (VIREO_LDS_MAX_PAD), balanced slabs (TiledStream::perm).
 struct TileShape {
     int RW, slab_rows, form, mode;
@@ -305,14 +305,12 @@ struct TileShape {
 // that slab + the staging of the slab, in trips -- so that every CU is busy for the whole launch
 // and a tile is cut into few pieces (tiles + n_wg pieces at most: the partial outputs the
 // consumers add up).  bnd = the per-wave (slab, round) offsets on the host.
-static int plan_items(TiledStream& t, const int32_t* bnd, int64_t n_wave, int nrv, int n_cu,
-                      const int32_t* rowmap, int mode, hipStream_t s) {
-    constexpr int UG = VRX_LDS_U * (64 / VRX_LDS_LPE);
-    const int64_t per_wave = (int64_t)t.n_slab * nrv + 1, visits = (int64_t)t.n_tile * t.n_slab;
-    const int want = env_int(mode == 1 ? "VIREO_LDS_BLOCKS_CELL" : "VIREO_LDS_BLOCKS_VAR",
-                             env_int("VIREO_LDS_BLOCKS", std::max(1, n_cu)));
-    const int n_wg = (int)std::max<int64_t>(1, std::min<int64_t>(want, visits));
-    const double stage = (double)env_int("VIREO_LDS_STAGE_TRIPS_X10", 100) / 10.0;
+static int plan_items(TiledStream& t, const int32_t* bnd, int n_cu, const int32_t* rowmap, hipStream_t s) {
+    constexpr int G = 64 / VRX_LDS_LPE, UG = VRX_LDS_U * G;
+    constexpr double stage = 10.0;  // staging a slab, in trips
+    const int nr = t.rw / G;
+    const int64_t per_wave = (int64_t)t.n_slab * nr + 1, visits = (int64_t)t.n_tile * t.n_slab;
+    const int n_wg = (int)std::max<int64_t>(1, std::min<int64_t>(env_int("VIREO_LDS_BLOCKS", std::max(1, n_cu)), visits));
     std::vector<double> cost((size_t)visits);
     parallel_chunks(t.n_tile, host_threads(), [&](int64_t t0, int64_t t1, int) {
         for (int64_t tl = t0; tl < t1; ++tl)
@@ -320,13 +318,12 @@ static int plan_items(TiledStream& t, const int32_t* bnd, int64_t n_wave, int nr
                 int32_t longest = 0;
                 for (int w = 0; w < VRX_LDS_WAVES; ++w) {
                     const int32_t* bw = bnd + (tl * VRX_LDS_WAVES + w) * per_wave;
-                    longest = std::max(longest, (bw[(int64_t)(sl + 1) * nrv] & ~(UG - 1)) -
-                                                    (bw[(int64_t)sl * nrv] & ~(UG - 1)));
+                    longest = std::max(longest, (bw[(int64_t)(sl + 1) * nr] & ~(UG - 1)) -
+                                                    (bw[(int64_t)sl * nr] & ~(UG - 1)));
                 }
                 cost[(size_t)(tl * t.n_slab + sl)] = (double)longest / UG + stage;
             }
     });
-    (void)n_wave;
     double total = 0.0;
     for (double c : cost) total += c;
     std::vector<int32_t> items, first((size_t)n_wg + 1, 0), pieces((size_t)t.n_tile, 0);
@@ -357,7 +354,7 @@ static int plan_items(TiledStream& t, const int32_t* bnd, int64_t n_wave, int nr
     // Workgroup b runs on XCD b % 8 (observed dispatch rule; used for speed only): the runs are
     // sorted by the slab they start at and dealt XCD by XCD, so that the ~32 workgroups of an
     // XCD walk neighbouring slabs together and every slab is fetched into that L2 about once.
-    if (env_int("VIREO_LDS_XCD_PHASE", 1) && n_wg > kXcd) {
+    if (n_wg > kXcd) {
         std::vector<int> run((size_t)n_wg);
         for (int b = 0; b < n_wg; ++b) run[(size_t)b] = b;
         auto phase = [&](int b) {
@@ -580,19 +577,14 @@ static VrxTileArgs tile_args(const TileRows& R, const TileShape& S, const TileLa
     A.n_slab = L.n_slab;
     A.slab_rows = L.slab_rows;
     A.form = S.form;
-    A.PH = S.form == 2 ? 2 : 1;  // phases of a round (form 2: AD entries, then BD entries)
     // the entry bit that selects the LDS bank half of a 128-B dense row: half (form 1), parity
     // of the slab-local index (variant pass); none for the 256-B rows of the (ad, dp) cell pass
     A.bit_shift = S.form != 0 ? 7 : (S.mode == 0 ? 22 : -1);
-    A.pairing = env_int("VIREO_LDS_PARITY", 1) != 0 ? 1 : 0;
     A.xor_partner = 24 / VRX_LDS_LPE;
     // form 1 words carry the LDS address of their half row: the slab starts behind the rings
     A.f1_base = (uint32_t)VRX_LDS_WAVES * VRX_RING * 4u;
     A.pad_word = S.form != 0 ? A.f1_base : 0u;
     A.n_wave = (int64_t)L.n_tile * VRX_LDS_WAVES;
-#ifdef VRX_CAP_PROBE
-    A.cap = R.virt ? env_int("VIREO_CAP_PROBE_VAR", 0) : env_int("VIREO_CAP_PROBE_CELL", 0);
-#endif
     return A;
 }
 
@@ -602,7 +594,7 @@ static VrxTileArgs tile_args(const TileRows& R, const TileShape& S, const TileLa
 static_assert(VRX_LDS_WAVES == 16 && VRX_LDS_PF <= 8,
               "balanced slabs: the perm path of vrx_spmm_lds assumes 16 waves and at most 8 prefetch registers");
 static bool balance_applies(const TileRows& R, const TileShape& S, const TileLayout& L) {
-    return VRX_LDS_PRECISE && S.balance && S.form == 1 && L.n_slab > 1 && R.n_contract < ((int64_t)1 << 24) &&
+    return S.balance && S.form == 1 && L.n_slab > 1 && R.n_contract < ((int64_t)1 << 24) &&
            L.n_vrows < ((int64_t)1 << 31) && (!L.split || env_int("VIREO_BALANCE_SPLIT", 1) != 0);
 }
 
@@ -891,7 +883,7 @@ static void push_value(std::vector<uint32_t>& out, int64_t v, uint32_t off) {
 static int64_t walk_wave(const TileRows& R, const TileLayout& L, const VrxTileArgs& A, int64_t w, int32_t* bw,
                          std::vector<uint32_t>& dst) {
     constexpr int G = 64 / VRX_LDS_LPE;
-    const int RW = A.RW, NR = A.NR, U = A.U, PH = A.PH, form = A.form, bit_shift = A.bit_shift;
+    const int RW = A.RW, NR = A.NR, U = A.U, form = A.form, bit_shift = A.bit_shift;
     const int64_t* ptr = R.ptr;
     const int32_t* idx = R.idx;
     const int2* val = R.val;
@@ -923,7 +915,6 @@ static int64_t walk_wave(const TileRows& R, const TileLayout& L, const VrxTileAr
                     s_hi[g] = hi;
                 }
             }
-            for (int ph = 0; ph < PH; ++ph) {
             int64_t longest = 0;
             for (int g = 0; g < G; ++g) {
                 std::vector<uint32_t>& sw = segw[g];
@@ -932,13 +923,10 @@ static int64_t walk_wave(const TileRows& R, const TileLayout& L, const VrxTileAr
                     if (form == 0) {
                         sw.push_back(((uint32_t)(idx[e] - base) << 22) |
                                      ((uint32_t)val[e].x << 11) | (uint32_t)val[e].y);
-                    } else if (form == 1) {
+                    } else {
                         const uint32_t at = A.f1_base + (uint32_t)(idx[e] - base) * 256u;
                         push_value(sw, val[e].x, at);
                         push_value(sw, (int64_t)val[e].y - val[e].x, at + 128u);
-                    } else {  // form 2: AD entries in phase 0, BD entries in phase 1
-                        const uint32_t at = A.f1_base + (uint32_t)(idx[e] - base) * 128u;
-                        push_value(sw, ph == 0 ? (int64_t)val[e].x : (int64_t)val[e].y - val[e].x, at);
                     }
                 }
                 longest = std::max<int64_t>(longest, (int64_t)sw.size());
@@ -953,7 +941,7 @@ static int64_t walk_wave(const TileRows& R, const TileLayout& L, const VrxTileAr
             // position z and its bit-1 entries after it, its partner Q the other way round.
             // z exists whenever the pair's bit-0 entries and its bit-1 entries each fit
             // into the round, i.e. almost always.
-            if (A.pairing && bit_shift >= 0) {
+            if (bit_shift >= 0) {
                 for (int g = 0; g < G; ++g) {
                     // the group that shares g's rotation inside g's service group holds
                     // lanes ^ 24 (ds_read_b128: {0-3,12-15,20-27}, {4-11,16-19,28-31}, +32)
@@ -987,18 +975,17 @@ static int64_t walk_wave(const TileRows& R, const TileLayout& L, const VrxTileAr
                 }
             }
             // offset | entries in the last trip (0 = full): the kernel skips the padding
-            bw[((int64_t)sl * NR + r) * PH + ph] = (int32_t)(rel | (longest % U));
+            bw[(int64_t)sl * NR + r] = (int32_t)(rel | (longest % U));
             longest = (longest + U - 1) / U * U;
             dst.resize((size_t)(rel + longest * G));
             for (int64_t j = 0; j < longest; ++j)
-                for (int g = 0; g < G; ++g)  // padding: value 0 (forms 1, 2: at the slab's first row)
+                for (int g = 0; g < G; ++g)  // padding: value 0 (form 1: at the slab's first row)
                     dst[(size_t)(rel + vrx_trip_slot(j, g, G, U, form))] =
                         j < (int64_t)segw[g].size() ? segw[g][(size_t)j] : A.pad_word;
             rel += longest * G;  // (a multiple of 64 words: streams stay 16-B aligned)
-            }
         }
     }
-    bw[(int64_t)A.n_slab * NR * PH] = (int32_t)rel;
+    bw[(int64_t)A.n_slab * NR] = (int32_t)rel;
     return rel;
 }
 
@@ -1039,7 +1026,7 @@ static int finish_stream(TiledStream& t, const TileShape& S, const TileLayout& L
         VRX_HIP(t.split_rows.upload(L.split_rows.data(), L.split_rows.size(), s));
     }
     VRX_HIP(hipStreamSynchronize(s));
-    rc = plan_items(t, bnd.data(), n_wave, A.NR * A.PH, n_cu, L.rowmap.data(), S.mode, s);
+    rc = plan_items(t, bnd.data(), n_cu, L.rowmap.data(), s);
     if (rc) return rc;
     t.ready = true;
     return VRX_OK;
@@ -1047,7 +1034,7 @@ static int finish_stream(TiledStream& t, const TileShape& S, const TileLayout& L
 
 static int stream_on_host(TiledStream& t, const TileRows& R, const TileShape& S, const TileLayout& L,
                           const VrxTileArgs& A, int n_cu, hipStream_t s) {
-    const int64_t n_wave = A.n_wave, per_wave = (int64_t)A.n_slab * A.NR * A.PH + 1;
+    const int64_t n_wave = A.n_wave, per_wave = (int64_t)A.n_slab * A.NR + 1;
     std::vector<int64_t> wave_len((size_t)n_wave, 0);
     std::vector<int32_t> bnd((size_t)(n_wave * per_wave));
     std::vector<std::vector<uint32_t>> wave_words((size_t)n_wave);
@@ -1106,7 +1093,7 @@ static int stream_on_device(TiledStream& t, const TileRows& R, const TileShape& 
         }
         t.perm = std::move(B.perm);
     }
-    const int64_t n_wave = A.n_wave, nsr = (int64_t)A.n_slab * A.NR * A.PH, per_wave = nsr + 1;
+    const int64_t n_wave = A.n_wave, nsr = (int64_t)A.n_slab * A.NR, per_wave = nsr + 1;
     const int64_t n_pos = n_wave * A.n_slab * A.RW;
     VRX_REQUIRE(n_pos < INT32_MAX * (int64_t)VRX_BLOCK, "tiled stream: too many segments");
     VRX_HIP(seg_lo.alloc((size_t)n_pos));
@@ -1186,25 +1173,21 @@ static int pick_rw_cell(int64_t n_var, int64_t n_cell, int n_cu, int cell_form) 
         const int64_t cus = std::max(1, n_cu);
         return (double)((tiles * n_slab_c + cus - 1) / cus) * rw;
     };
-    const int forced = env_int("VIREO_LDS_RW_CELL", 0);
-    return forced == VRX_LDS_RW_CELL_SHORT ||
-                   (forced == 0 && n_slab_c <= 2 && cost(VRX_LDS_RW_CELL_SHORT) < cost(tall))
-               ? VRX_LDS_RW_CELL_SHORT
-               : tall;
+    return n_slab_c <= 2 && cost(VRX_LDS_RW_CELL_SHORT) < cost(tall) ? VRX_LDS_RW_CELL_SHORT : tall;
 }
 
 // Which stream words the LDS-resident passes use.  Single-valued AD / BD words (cell form 1,
-// variant form 2) cost ~1.56x less per word than (ad, dp) pair words (c3: 0.39 vs 0.51 ms at
+// variant form 3) cost ~1.56x less per word than (ad, dp) pair words (c3: 0.39 vs 0.51 ms at
 // 1.2 words per entry) and hold any count, but a count with more than three significant bits
 // takes several words (45 = 40 + 5): deep data -- clone mode, DP ~ Poisson(50), 2.65 words per
 // entry -- is better served by one pair word per entry as long as the counts fit its 11 bits.
 // The words per entry are estimated from every 61st entry.  VIREO_CELL_FORM / VIREO_VAR_FORM
 // force a form.
 struct StreamForms {
-    int cell, var;   // cell pass: 1 AD/BD, 0 pairs; variant pass: 2 AD/BD phases, 0 pairs
+    int cell, var;   // cell pass: 1 AD/BD, 0 pairs; variant pass: 3 AD/BD virtual rows, 0 pairs
     bool auto_pair;  // pairs chosen by the estimate: fall back to AD/BD when a count is >= 2048
 };
-static StreamForms pick_forms(int64_t nnz, const int32_t* ad, const int32_t* dp) {
+static int pick_forms(int64_t nnz, const int32_t* ad, const int32_t* dp, StreamForms* out) {
     int64_t words = 0, seen = 0;
     for (int64_t e = 0; e < nnz; e += 61) {
         const int64_t a = ad[e], d = dp[e];
@@ -1218,7 +1201,16 @@ static StreamForms pick_forms(int64_t nnz, const int32_t* ad, const int32_t* dp)
     f.cell = env_int("VIREO_CELL_FORM", pairs ? 0 : 1);
     f.var = env_int("VIREO_VAR_FORM", pairs ? 0 : 3);
     f.auto_pair = pairs && !getenv("VIREO_CELL_FORM") && !getenv("VIREO_VAR_FORM");
-    return f;
+    if (f.cell != 0 && f.cell != 1) {
+        vrx_set_error("vrx_problem_create: VIREO_CELL_FORM=%d (0: pair words, 1: AD / BD words)", f.cell);
+        return VRX_ERR_ARG;
+    }
+    if (f.var != 0 && f.var != 3) {
+        vrx_set_error("vrx_problem_create: VIREO_VAR_FORM=%d (0: pair words, 3: AD / BD virtual rows)", f.var);
+        return VRX_ERR_ARG;
+    }
+    *out = f;
+    return VRX_OK;
 }
 
 // once the largest count is known: the estimate chose pair words but a count does not fit their 11 bits --
@@ -1254,7 +1246,7 @@ struct BuildPlan {
     StreamForms forms;
     int lds;
     int64_t min_nnz_cell, min_nnz_var;
-    int slab_cell, slab_var;
+    int slab_cell;
 };
 
 // The device builder's copy of the input: the merged CSC arrays, validated, and the variant-major rows
@@ -1483,7 +1475,7 @@ static int device_build(vrx_problem* p, const int64_t* colptr, const int32_t* ro
     const int var_form = forms.var, cell_form = forms.cell;
     const bool guard = plan.lds != 1;
     // (pair words hold 11-bit counts; a forced pair form leaves such data to the host builder)
-    if ((var_form < 2 || cell_form != 1) && max_count >= 2048) return VRX_OK;
+    if ((var_form == 0 || cell_form == 0) && max_count >= 2048) return VRX_OK;
     lap("upload + validate");
     if ((rc = transpose_pack(p, D, max_count))) return rc;
     lap("transposition");
@@ -1498,7 +1490,7 @@ static int device_build(vrx_problem* p, const int64_t* colptr, const int32_t* ro
         : TileRows{D.h_rptr.data(), nullptr, nullptr, {D.rptr.p, D.ridx.p, D.rval.p}, n_var, n_cell, nnz, false};
     const TileShape var_shape = var_form == 3
         ? TileShape{VRX_LDS_RW_CELL, VRX_LDS_SLAB_BYTES / 256, 1, 0, guard, p->want_balance}
-        : TileShape{VRX_LDS_RW_VARIANT, plan.slab_var, var_form == 2 ? 2 : 0, 0, guard, p->want_balance};
+        : TileShape{VRX_LDS_RW_VARIANT, VRX_LDS_SLAB_BYTES / 128, 0, 0, guard, p->want_balance};
     double balance_seconds = 0.0;
     if ((rc = build_both_streams(p, cell_rows, cell_shape, var_rows, var_shape, lap, &balance_seconds))) return rc;
     if (!p->by_cell.tiled.ready || !p->by_var.tiled.ready) {  // rejected by the padding guard
@@ -1551,6 +1543,9 @@ static int problem_create2(int device, int64_t n_var, int64_t n_cell, int64_t nn
     VRX_REQUIRE(n_var < INT32_MAX && n_cell < INT32_MAX, "vrx_problem_create: dimension >= 2^31");
     VRX_REQUIRE(colptr && (nnz == 0 || (rowidx && ad && dp)), "vrx_problem_create: null input");
     VRX_REQUIRE(colptr[0] == 0 && colptr[n_cell] == nnz, "vrx_problem_create: colptr/nnz mismatch");
+    BuildPlan plan;
+    int rc = pick_forms(nnz, ad, dp, &plan.forms);
+    if (rc) return rc;
     int ndev = 0;
     vrx_device_count(&ndev);
     if (device < 0 || device >= ndev) {
@@ -1574,17 +1569,13 @@ static int problem_create2(int device, int64_t n_var, int64_t n_cell, int64_t nn
     // on the device; VIREO_BUILD=host keeps the host builder (the specification the device
     // build is tested against), VIREO_BUILD=device takes the device path whenever VIREO_LDS
     // allows the streams.
-    BuildPlan plan;
-    plan.forms = pick_forms(nnz, ad, dp);
     plan.lds = env_int("VIREO_LDS", -1);
     plan.min_nnz_cell = env_int("VIREO_LDS_MIN_NNZ", 4000000);
     plan.min_nnz_var = env_int("VIREO_LDS_MIN_NNZ_VAR", 32000000);
     plan.slab_cell = std::min(VRX_LDS_SLAB_BYTES / 256, std::max(16, env_int("VIREO_LDS_SLAB_CELL", VRX_LDS_SLAB_BYTES / 256)));
-    plan.slab_var = std::min(VRX_LDS_SLAB_BYTES / 128, std::max(16, env_int("VIREO_LDS_SLAB_VAR", VRX_LDS_SLAB_BYTES / 128)));
     const char* bm = getenv("VIREO_BUILD");
     const bool force_dev = bm && !strcmp(bm, "device"), force_host = bm && !strcmp(bm, "host");
     const bool big = nnz >= plan.min_nnz_cell && nnz >= plan.min_nnz_var;
-    int rc;
     bool built = false;
     if (!force_host && plan.lds != 0 && (force_dev || big)) {
         if ((rc = device_build(p.get(), colptr, rowidx, ad, dp, plan, &built))) return rc;
@@ -1685,14 +1676,14 @@ static int host_build(vrx_problem* p, const int64_t* colptr, const int32_t* rowi
     // ties at 8-16 M and wins clearly at 100 M.
     const int lds = plan.lds;
     const StreamForms f = settle_forms(plan.forms, max_count);
-    const int cell_form = f.cell, var_form = f.var;  // cell 1: AD/BD stream; variant 3: AD/BD virtual rows,
-    const bool pairs_fit = max_count < 2048;         // 2: AD/BD phases (any counts); else pairs (11-bit counts)
+    const int cell_form = f.cell, var_form = f.var;  // cell 1: AD/BD stream; variant 3: AD/BD virtual rows;
+    const bool pairs_fit = max_count < 2048;         // else pairs (11-bit counts)
     if ((pairs_fit || cell_form == 1) && lds != 0) {
         // cell pass: slabs of 512 W rows (128 KiB at K = 16); variant pass: 1024 ID rows
         if (lds == 1 || nnz >= plan.min_nnz_cell) {
             const TileRows rows{colptr, rowidx, cval.data(), {}, n_cell, n_var, nnz, false};
-            const TileShape shape{pick_rw_cell(n_var, n_cell, p->n_cu, cell_form), plan.slab_cell, cell_form == 1 ? 1 : 0,
-                                  1, lds != 1, false};
+            const TileShape shape{pick_rw_cell(n_var, n_cell, p->n_cu, cell_form), plan.slab_cell, cell_form, 1,
+                                  lds != 1, false};
             if ((rc = build_tiled(p->by_cell, rows, shape, p->n_cu, p->stream))) return rc;
         }
         if (var_form == 3 && (lds == 1 || nnz >= plan.min_nnz_var)) {
@@ -1704,9 +1695,9 @@ static int host_build(vrx_problem* p, const int64_t* colptr, const int32_t* rowi
                                 (int64_t)vidx.size(), true};
             const TileShape shape{VRX_LDS_RW_CELL, VRX_LDS_SLAB_BYTES / 256, 1, 0, lds != 1, false};
             if ((rc = build_tiled(p->by_var, rows, shape, p->n_cu, p->stream))) return rc;
-        } else if ((var_form == 2 || pairs_fit) && (lds == 1 || nnz >= plan.min_nnz_var)) {
+        } else if (pairs_fit && (lds == 1 || nnz >= plan.min_nnz_var)) {
             const TileRows rows{rptr.data(), ridx.data(), rval.data(), {}, n_var, n_cell, nnz, false};
-            const TileShape shape{VRX_LDS_RW_VARIANT, plan.slab_var, var_form == 2 ? 2 : 0, 0, lds != 1, false};
+            const TileShape shape{VRX_LDS_RW_VARIANT, VRX_LDS_SLAB_BYTES / 128, 0, 0, lds != 1, false};
             if ((rc = build_tiled(p->by_var, rows, shape, p->n_cu, p->stream))) return rc;
         }
     }
@@ -2489,15 +2480,11 @@ static bool lds_eligible(const vrx_problem& p, int K) {
 // kernel instance for K: zero-padded rows when K % 4, 2 / 4 entries at once when K <= 8 / 4
 template <int LPE, int MODE, int RW>
 static auto lds_kernel_rw(int K, bool strided) {
-    const int split = std::min(LPE, K <= 4 ? 4 : K <= 8 ? 2 : 1);
+    const int split = K <= 4 ? 4 : K <= 8 ? 2 : 1;
     // (the element-wise slab copy handles row strides and rows that do not fill whole lanes)
     const bool pad = K % (16 / LPE) != 0 || strided;
-    if constexpr (LPE >= 4)
-        if (split == 4)
-            return pad ? vrx_spmm_lds<LPE, MODE, RW, 1, 4> : vrx_spmm_lds<LPE, MODE, RW, 0, 4>;
-    if constexpr (LPE >= 2)
-        if (split == 2)
-            return pad ? vrx_spmm_lds<LPE, MODE, RW, 1, 2> : vrx_spmm_lds<LPE, MODE, RW, 0, 2>;
+    if (split == 4) return pad ? vrx_spmm_lds<LPE, MODE, RW, 1, 4> : vrx_spmm_lds<LPE, MODE, RW, 0, 4>;
+    if (split == 2) return pad ? vrx_spmm_lds<LPE, MODE, RW, 1, 2> : vrx_spmm_lds<LPE, MODE, RW, 0, 2>;
     return pad ? vrx_spmm_lds<LPE, MODE, RW, 1, 1> : vrx_spmm_lds<LPE, MODE, RW, 0, 1>;
 }
 
@@ -2520,11 +2507,6 @@ static auto lds_kernel(int K, int ld, bool strided, int rw, int form) {
     if (MODE == 1 && form == 1) {
         return rw == VRX_LDS_RW_CELL_SHORT ? lds_kernel_form1<VRX_LDS_RW_CELL_SHORT>(pad)
                                            : lds_kernel_form1<VRX_LDS_RW_CELL>(pad);
-    }
-    if (MODE == 0 && form == 2) {
-        return pad == 0   ? vrx_spmm_lds<VRX_LDS_LPE, 0, VRX_LDS_RW_VARIANT, 0, 1, 2>
-               : pad == 1 ? vrx_spmm_lds<VRX_LDS_LPE, 0, VRX_LDS_RW_VARIANT, 1, 1, 2>
-                          : vrx_spmm_lds<VRX_LDS_LPE, 0, VRX_LDS_RW_VARIANT, 2, 1, 2>;
     }
     if (MODE == 1 && rw == VRX_LDS_RW_CELL_SHORT)
         return lds_kernel_rw<LPE, MODE, MODE == 1 ? VRX_LDS_RW_CELL_SHORT : VRX_LDS_RW_VARIANT>(K, strided);
@@ -2554,8 +2536,7 @@ static int launch_lds_one(const Orient& o, hipStream_t s, const double* X, int K
         const int kb = std::min(16, K - c0);
         const bool f1 = MODE == 1 && t.form == 1;  // planar operand, 256-B LDS rows
         constexpr int CPL = 16 / LPE;  // columns per lane: LDS rows hold whole lanes
-        const bool f2 = MODE == 0 && t.form == 2;  // 128-B LDS rows whatever K
-        const size_t lds = (size_t)t.slab_rows * (f1 ? 256 : f2 ? 128 : (kb + CPL - 1) / CPL * CPL * (MODE == 1 ? 16 : 8)) +
+        const size_t lds = (size_t)t.slab_rows * (f1 ? 256 : (kb + CPL - 1) / CPL * CPL * (MODE == 1 ? 16 : 8)) +
                            VRX_LDS_WAVES * VRX_RING * 4;
         auto kern = lds_kernel<LPE, MODE>(kb, K, K > 16, t.rw, t.form);
         VRX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -3209,23 +3190,6 @@ extern "C" int vrx_model_step(vrx_model* m, int32_t which, double* elbo_out) {
     VRX_HIP(hipStreamSynchronize(s));
     return prof_drain(m);
 }
-
-#ifdef VRX_PROBE_BUILD
-// scratch builds only (scratch/vrx_probe.h): read and clear the per-wave records of vrx_spmm_lds
-extern "C" int vrx_debug_probe_visits(unsigned long long* out) {
-    VRX_HIP(hipDeviceSynchronize());
-    VRX_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(vrx_probe_visit), sizeof(vrx_probe_visit)));
-    return VRX_OK;
-}
-extern "C" int vrx_debug_probe(unsigned long long* rec) {
-    VRX_HIP(hipDeviceSynchronize());
-    VRX_HIP(hipMemcpyFromSymbol(rec, HIP_SYMBOL(vrx_probe_rec), sizeof(vrx_probe_rec)));
-    void* dev = nullptr;
-    VRX_HIP(hipGetSymbolAddress(&dev, HIP_SYMBOL(vrx_probe_rec)));
-    VRX_HIP(hipMemset(dev, 0, sizeof(vrx_probe_rec)));
-    return VRX_OK;
-}
-#endif
 
 extern "C" int vrx_model_info(vrx_model* m, int32_t* info) {
     VRX_REQUIRE(m && info, "vrx_model_info: null argument");

@@ -466,32 +466,16 @@ __global__ __launch_bounds__(VRX_BLOCK) void vrx_spmm(
 typedef double vrx_d2 __attribute__((ext_vector_type(2)));
 typedef uint32_t vrx_u2 __attribute__((ext_vector_type(2)));
 typedef uint32_t vrx_u4 __attribute__((ext_vector_type(4)));
-#ifndef VRX_LDS_RING
-#define VRX_LDS_RING 512
-#endif
-constexpr int VRX_RING = VRX_LDS_RING;   // entries per wave
+#define VRX_LDS_WAVES 16  // waves per workgroup of the LDS-resident passes (one per CU)
+#define VRX_LDS_RING 512  // entries per wave
+constexpr int VRX_RING = VRX_LDS_RING;
 constexpr int VRX_CHUNK = 256;  // entries per refill (64 lanes x 16 B of one LDS-DMA load)
-#ifndef VRX_LDS_U_DEF
-#define VRX_LDS_U_DEF 4
-#endif
-// waves per workgroup of the LDS-resident passes (16: one 160-KiB workgroup per CU; 8: two
-// 80-KiB workgroups per CU whose barrier / staging phases overlap -- experimental builds)
-#ifndef VRX_LDS_WAVES
-#define VRX_LDS_WAVES 16
-#endif
-#ifndef VRX_LDS_PRECISE
-#define VRX_LDS_PRECISE 1
-#endif
 // LDS of a pass = one 2-KiB entry ring per wave + the slab; a slab is staged through PF 16-B
 // registers per thread: 16 waves: 32 KiB + 8 x 16 KiB = 160 KiB
-#ifdef VRX_LDS_PF_DEF
-constexpr int VRX_LDS_PF = VRX_LDS_PF_DEF;
-#else
 constexpr int VRX_LDS_PF = (160 * 1024 - VRX_LDS_WAVES * VRX_RING * 4) / (VRX_LDS_WAVES * 64 * 16);
-#endif
 constexpr int VRX_LDS_SLAB_BYTES = VRX_LDS_PF * VRX_LDS_WAVES * 64 * 16;
 // Word order inside a trip (U entries for each of the G lane groups).  Pair words (FORM 0):
-// entry-major, word j of group g at j * G + g.  AD/BD words (FORM 1, 2): group-major, the U
+// entry-major, word j of group g at j * G + g.  AD/BD words (FORM 1): group-major, the U
 // words of a group adjacent (g * U + u), so that a lane takes its trip with ONE ds_read_b128
 // instead of two ds_read2_b32.  Both builders place the words with vrx_trip_slot.
 // stream position, relative to the round's base, of entry n (0, 1, ...) of lane group g
@@ -500,20 +484,15 @@ __host__ __device__ inline int64_t vrx_trip_slot(int64_t n, int g, int G, int U,
     return n * G + g;
 }
 // output rows per wave (tile = 16 x this), per pass: the tallest tile the 128 registers of a
-// 1024-thread workgroup hold without spilling (accumulators: RW / 2 registers in the AD/BD cell
-// pass, RW in the AD/BD variant pass and the pair-word cell pass) -- every slab is staged once
+// 1024-thread workgroup hold without spilling (accumulators: RW / 2 registers in the AD/BD
+// pass, RW in the pair-word passes) -- every slab is staged once
 // per tile, so a taller tile means less staging per entry (c3 cell pass: 0.389 / 0.362 / 0.349 /
 // 0.341 ms at 48 / 64 / 80 / 96 rows)
-#ifndef VRX_LDS_LPE_DEF
-#define VRX_LDS_LPE_DEF 4
-#define VRX_LDS_RWV_DEF 32
-#define VRX_LDS_RWC_DEF 96
-#endif
-constexpr int VRX_LDS_RW_VARIANT = VRX_LDS_RWV_DEF, VRX_LDS_RW_CELL = VRX_LDS_RWC_DEF;
-constexpr int VRX_LDS_RW_CELL_PAIR = 64;  // cell pass on (ad, dp) pair words (FORM 0): twice the accumulators
-constexpr int VRX_LDS_RW_CELL_SHORT = VRX_LDS_LPE_DEF == 1 ? 64 : 32;  // cell pass with one or two slabs, see vrx_problem_create
-constexpr int VRX_LDS_LPE = VRX_LDS_LPE_DEF;  // lanes per output row (16 / this columns per lane)
-constexpr int VRX_LDS_U = VRX_LDS_U_DEF;    // entries per trip and group; rows are padded to it
+constexpr int VRX_LDS_RW_VARIANT = 32, VRX_LDS_RW_CELL = 96;
+constexpr int VRX_LDS_RW_CELL_PAIR = 64;   // cell pass on (ad, dp) pair words (FORM 0): twice the accumulators
+constexpr int VRX_LDS_RW_CELL_SHORT = 32;  // cell pass with one or two slabs, see pick_rw_cell
+constexpr int VRX_LDS_LPE = 4;  // lanes per output row (16 / this columns per lane)
+constexpr int VRX_LDS_U = 4;    // entries per trip and group; rows are padded to it
 
 // PADK: K is not a multiple of 4 (the slab is staged element-wise into zero-padded rows).
 // SPLIT: with K <= 8 (<= 4) a row needs only 2 (1) of the group's 4 lanes, so the group's lanes
@@ -532,23 +511,9 @@ constexpr int VRX_LDS_U = VRX_LDS_U_DEF;    // entries per trip and group; rows 
 // conversion (high dword = word & 0xfffc0000, low dword 0) and the LDS address of a slice is
 // one v_and_or_b32.  The two lane groups of a ds_read_b128 service
 // group that share a slice rotation read different halves whenever one walks AD entries and the
-// other BD entries, which the stream builder arranges (AD-first / BD-first segments).
+// other BD entries, which the stream builder arranges (AD-first / BD-first segments).  The
+// variant pass takes FORM 1 too, over virtual rows (vrx_build.h), or pair words (FORM 0).
 //
-// FORM 2 (variant pass): the same single-valued words against the 128-B rows of ID_prob, in
-// two PHASES per round -- first the AD entries of the round's rows, accumulated into S1 = AD @ ID,
-// then their BD entries, accumulated into S2 = BD @ ID (SS = S1 + S2 at the store); each phase is
-// padded to its own longest row.  ~22 % more slots than the (ad, dp) pair words, but 7 instead of
-// ~15 vector instructions per slot, no conversions, and counts of any size.
-// Probe hooks: the product build defines them away.  A scratch build with -DVRX_PROBE_BUILD includes
-// scratch/vrx_probe.h, which times the bracketed statements with s_memtime (DESIGN_HISTORY.md 4.2).
-#ifdef VRX_PROBE_BUILD
-#include "../../scratch/vrx_probe.h"
-#else
-#define VRX_PROBE_BEGIN
-#define VRX_PROBE(var, stmt) stmt;
-#define VRX_PROBE_TRIP
-#define VRX_PROBE_END
-#endif
 // PADK: 0 = rows of exactly 16 contiguous columns (flat slab copy); 1 = any K / row stride
 // (element-wise staging into zero-padded rows, masked stores); 2 = AD/BD forms with even K and
 // even row stride (column blocks of wider operands, restart batches, K = 2 ... 14): as 1, but
@@ -575,16 +540,14 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
     constexpr int PF = VRX_LDS_PF;         // 16-B prefetch registers per thread (a slab / the workgroup)
     constexpr int NV = MODE == 0 ? 2 : 1;  // accumulated values per column
     constexpr int U = VRX_LDS_U;           // entries per trip and group
+    static_assert(LPE == 4, "lanes per row");
     static_assert(RW % G == 0 && 2 * (RW / G) < 63, "rows per wave");
-    static_assert(FORM == 0 || (SPLIT == 1 && ((MODE == 1 && FORM == 1) || (MODE == 0 && FORM == 2))),
-                  "AD/BD forms");
-    constexpr int PH = FORM == 2 ? 2 : 1;  // phases of a round (FORM 2: AD entries, then BD entries)
-    constexpr int NRV = NR * PH;           // (round, phase) pairs per slab
+    static_assert(FORM == 0 || (SPLIT == 1 && MODE == 1 && FORM == 1), "AD/BD form");
     // AD/BD forms staged in whole 16-B units: the slab prefetch is exactly PF vector loads per
     // thread, every one of them unconditional (lanes outside the slab re-read a valid unit; the
     // rows / columns they fill are never referenced by a word resp. never stored), so the walk
     // can leave the prefetch in flight while it waits for a chunk of its stream
-    constexpr bool PRECISE = FORM != 0 && VRX_LDS_PRECISE;
+    constexpr bool PRECISE = FORM != 0;
     // (element-wise: 2 loads per unit) + the bnd words of the next slab (+ AD/BD instances: the rows the wave
     //  stages for the slab behind it, TiledStream::perm -- issued whether or not the stream is balanced)
     constexpr bool GATHER = PRECISE;
@@ -602,7 +565,6 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
     // One persistent workgroup per CU walks its work items (TiledStream::items): a contiguous run
     // of one tile's slabs each, whose sums go to partial array `slot`.
     const int item_end = wg_first[blockIdx.x + 1];
-    VRX_PROBE_BEGIN
     for (int item = wg_first[blockIdx.x]; item < item_end; ++item) {
     const int tile = __builtin_amdgcn_readfirstlane(items[4 * item]);
     const int s_lo = __builtin_amdgcn_readfirstlane(items[4 * item + 1]);
@@ -615,7 +577,7 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
     const int g = lane / LPE, sub = (lane % LPE) / LPR, kl = lane % LPR;
     const bool kok = kl * CP < K;  // a lane's 4 columns may start (or run) past K
     const int64_t wid = (int64_t)tile * VRX_LDS_WAVES + wave;
-    const int32_t* bw = bnd + wid * ((int64_t)n_slab * NRV + 1);
+    const int32_t* bw = bnd + wid * ((int64_t)n_slab * NR + 1);
     const uint32_t* stream = ent + wave_start[wid];
     // byte offset, inside a dense row, of the q-th 16-B slice this lane reads (rotated by g)
     uint32_t qoff[NQ];
@@ -805,8 +767,8 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
     // vmcnt waits only become stricter.  The walk's wait is exact where the instruction count
     // of the slab prefetch is fixed (PRECISE): the prefetch of the next slab, issued after the
     // chunk, stays in flight (s_waitcnt vmcnt(NPF)) instead of being drained with it.
-    const int stream_lo = __builtin_amdgcn_readfirstlane(bw[(int64_t)s_lo * NRV]) & ~(U * G - 1);
-    const int stream_end = __builtin_amdgcn_readfirstlane(bw[(int64_t)s_hi * NRV]) & ~(U * G - 1);
+    const int stream_lo = __builtin_amdgcn_readfirstlane(bw[(int64_t)s_lo * NR]) & ~(U * G - 1);
+    const int stream_end = __builtin_amdgcn_readfirstlane(bw[(int64_t)s_hi * NR]) & ~(U * G - 1);
     const int base0 = stream_lo & ~(VRX_CHUNK - 1);
     const int clamp_last = max(stream_end - 4, 0);  // lanes past the range re-read its last 16 B
     const uint32_t ring_lds = (uint32_t)(wave * VRX_RING * 4);  // (dynamic LDS starts at 0)
@@ -869,17 +831,17 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
     };
 
     // bnd words of a slab: stream offset (a multiple of U*G) | entries in the round's last trip
-    // (0 = a full trip) for each (round, phase), then the first word of the next slab: lane i
+    // (0 = a full trip) for each round, then the first word of the next slab: lane i
     // holds word i, ONE vector load a slab ahead (it is part of the prefetch the walk counts)
-    // the record of a slab: lanes 0 .. NRV its bnd words; balanced slabs: lanes 32 .. 63 the contracted rows
+    // the record of a slab: lanes 0 .. NR its bnd words; balanced slabs: lanes 32 .. 63 the contracted rows
     // this wave stages for the slab BEHIND it (they are needed a slab earlier, by the prefetch)
     // (scalar bases + 32-bit lane offsets formed from an opaque copy of the lane index: per-lane 64-bit
     //  pointers kept across the walk would cost registers it has not got)
     auto bnd_load = [&](int s_b) {
         int lane_o = threadIdx.x & 63;
         asm volatile("" : "+v"(lane_o));
-        const int32_t* a = bw + (int64_t)s_b * NRV;
-        return a[(uint32_t)min(lane_o, NRV)];
+        const int32_t* a = bw + (int64_t)s_b * NR;
+        return a[(uint32_t)min(lane_o, NR)];
     };
     // balanced slabs: lane 32 + 4 i + q holds the contracted row of slab-local row 4 * wave + 64 i + q of slab
     // s_p -- the 32 rows this wave stages.  A load of its own (loaded a slab before the prefetch that uses it,
@@ -899,43 +861,35 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
     slab_fetch(s_lo, rvec);
     if (GATHER) rvec = rows_load(s_lo + 1);
     for (int s = s_lo; s < s_hi; ++s) {
-#ifndef VRX_PROBE_NOBAR    // TIMING PROBES ONLY (scratch builds): barriers / slab staging compiled out (racy, wrong results)
-        VRX_PROBE(tm_bar1, __syncthreads())  // every wave is done reading the previous slab
-#endif
+        __syncthreads();  // every wave is done reading the previous slab
         // The slab's bnd words go to scalar registers BEFORE the next slab's prefetch is issued: the
         // compiler guards the readlanes with a full `s_waitcnt vmcnt(0)` (it cannot count across the loop),
         // which up to round 5 sat BEHIND the prefetch and drained it on the spot -- one exposed memory round
         // trip per visit, the 10-14 % a pass spent "staging" (profiles/r06_pass_structure_probes.txt).  Here
         // it only meets loads of the previous visit, which landed long ago.
-        int bcur[NRV + 1];
+        int bcur[NR + 1];
 #pragma unroll
-        for (int i = 0; i <= NRV; ++i) bcur[i] = __builtin_amdgcn_readlane(bvec, i);
-#ifndef VRX_PROBE_NOSTAGE
-        VRX_PROBE(tm_stage, slab_store())
+        for (int i = 0; i <= NR; ++i) bcur[i] = __builtin_amdgcn_readlane(bvec, i);
+        slab_store();
         if (s + 1 < s_hi) {  // (with the two loads below: NPF vector loads)
             slab_fetch(s + 1, rvec);
             since_fetch = 0;
         }
-#endif
         if (s + 1 < s_hi) {
             bvec = bnd_load(s + 1);
             if (GATHER) rvec = rows_load(s + 2);
         }
-#ifndef VRX_PROBE_NOBAR
-        VRX_PROBE(tm_bar2, __syncthreads())
-#endif
+        __syncthreads();
 #pragma unroll
-        for (int rv = 0; rv < NRV; ++rv) {
-            const int r = rv / PH;
+        for (int r = 0; r < NR; ++r) {
             // the round's entries are stored trip-major; the zero words that pad the round's
             // last trip are not executed
-            const int braw = bcur[rv];
+            const int braw = bcur[r];
             const int base = braw & ~(U * G - 1), tail = braw & (U - 1);
-            const int end = bcur[rv + 1] & ~(U * G - 1);
+            const int end = bcur[r + 1] & ~(U * G - 1);
             const int full_end = tail ? end - U * G : end;
             if (FORM != 0) {
-                // FORM 2: the AD entries of the round's rows feed S1 (acc), the BD entries S2 (acc2)
-                double (&ac)[NQ][2] = FORM == 2 && (rv & 1) ? acc2[r] : acc[r];
+                double (&ac)[NQ][2] = acc[r];
                 // A trip of NE <= U entries: every slice is requested (ds_read_b128, integer
                 // addresses: word offset bits | lane offset, the slab base is part of the word)
                 // before the first FMA; the FMAs of the first half wait for their four reads
@@ -944,64 +898,14 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
                 auto trip = [&](int at, auto ne_tag) {
                     constexpr int NE = decltype(ne_tag)::value;
                     uint32_t w[NE];
-                    VRX_PROBE_TRIP
                     {
-#ifndef VRX_PROBE_NODMA   // TIMING PROBE ONLY (scratch builds): the stream's LDS-DMA and its waits compiled out
-                        if (at >= ring_evt) VRX_PROBE(tm_dma, ring_event())
-#endif
+                        if (at >= ring_evt) ring_event();
                         // the group's U words are adjacent (padding words fill a short last trip)
-#ifdef VRX_PROBE_NORING   // TIMING PROBE ONLY: no ring read -- every word is the slab's first half row, value 0
-                        uint32_t pw = (uint32_t)VRX_LDS_WAVES * VRX_RING * 4u + ((uint32_t)at & 0x380u);
-                        asm volatile("" : "+v"(pw));
-                        const uint4 q4 = make_uint4(pw, pw ^ 128u, pw, pw ^ 128u);
-#else
                         const uint4 q4 = *reinterpret_cast<const uint4*>(ring + (at & (VRX_RING - 1)) + g * U);
-#endif
                         const uint32_t qq[4] = {q4.x, q4.y, q4.z, q4.w};
 #pragma unroll
                         for (int u = 0; u < NE; ++u) w[u] = qq[u];
                     }
-                    if constexpr (NQ == 1) {
-                        // EXPERIMENT BUILDS ONLY (-DVRX_LDS_LPE_DEF=8: rounds of 8 rows, 8 lanes and 2
-                        // columns each, DESIGN_HISTORY.md 4.2 r4): one 16-B slice per word and lane
-                        vrx_d2 y[NE];
-                        if (NE == 4) asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[NE - 1]));
-                        if (NE == 3) asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[NE - 1]));
-                        if (NE == 2) asm volatile("" : "+v"(w[0]), "+v"(w[NE - 1]));
-                        uint32_t b0, b1;
-#define VRX_R1(X0, W, A) "v_and_or_b32 " A ", " W ", %[msk], %[q0]\n\tds_read_b128 " X0 ", " A "\n\t"
-                        if constexpr (NE == 4)
-                            asm volatile(VRX_R1("%[x0]", "%[w0]", "%[a0]") VRX_R1("%[x1]", "%[w1]", "%[a1]")
-                                         VRX_R1("%[x2]", "%[w2]", "%[a0]") VRX_R1("%[x3]", "%[w3]", "%[a1]")
-                                         : [x0] "=&v"(y[0]), [x1] "=&v"(y[1]), [x2] "=&v"(y[2]), [x3] "=&v"(y[NE - 1]),
-                                           [a0] "=&v"(b0), [a1] "=&v"(b1)
-                                         : [w0] "v"(w[0]), [w1] "v"(w[1]), [w2] "v"(w[2]), [w3] "v"(w[NE - 1]),
-                                           [msk] "s"(0x3ff80u), [q0] "v"(qoff[0])
-                                         : "memory");
-                        else {
-#pragma unroll
-                            for (int u = 0; u < NE; ++u)
-                                asm volatile(VRX_R1("%[x0]", "%[w0]", "%[a0]")
-                                             : [x0] "=&v"(y[u]), [a0] "=&v"(b0)
-                                             : [w0] "v"(w[u]), [msk] "s"(0x3ff80u), [q0] "v"(qoff[0])
-                                             : "memory");
-                        }
-#undef VRX_R1
-                        if (NE == 4) {
-                            asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(y[0]), "+v"(y[1]));
-                        } else {
-#pragma unroll
-                            for (int u = 0; u < NE; ++u) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(y[u]));
-                        }
-#pragma unroll
-                        for (int u = 0; u < NE; ++u) {
-                            if (NE == 4 && u == 2)
-                                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(y[2]), "+v"(y[NE - 1]), "+v"(ac[0][0]), "+v"(ac[0][1]));
-                            const double v = __builtin_bit_cast(double, vrx_u2{0u, w[u] & 0xfffc0000u});
-                            ac[0][0] = fma(v, y[u][0], ac[0][0]);
-                            ac[0][1] = fma(v, y[u][1], ac[0][1]);
-                        }
-                    } else {
                     vrx_d2 x[NE][2];
                     // (all words have landed before the first slice is requested: the compiler's
                     //  own waits do not count the reads issued from inline assembly)
@@ -1079,7 +983,6 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
                             ac[q][1] = fma(v, x[u][q][1], ac[q][1]);
                         }
                     }
-                    }  // NQ == 2
                 };
                 for (int at = base; at < full_end; at += U * G) trip(at, std::integral_constant<int, 4>());
                 if (tail == 1) trip(full_end, std::integral_constant<int, 1>());
@@ -1113,7 +1016,6 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
     // (every issued chunk has been awaited by the walk; this only guards the invariant that no
     //  LDS-DMA write is in flight when the workgroup's LDS is released)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    VRX_PROBE_END
     // ---- every group holds the complete sums of its rows: store them ------------------------
     if (SPLIT > 1) {  // partial sums of the SPLIT entry streams: butterfly over the lanes
 #pragma unroll
@@ -1148,12 +1050,6 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
                     const int slice = kl * NQ + (q + g) % NQ;  // 16-B slice of the dense row
                     if (FORM == 1) {  // columns 2*slice, 2*slice + 1 of logLik_ID
                         double* o = dst + row * ld + 2 * slice;
-#ifdef VRX_PROBE_WT_PARTIALS  // TIMING PROBE ONLY (scratch builds): the partial planes written through
-                        if (!PADK) {  //  to memory (sc0 sc1), as a cross-XCD fold inside the pass would need
-                            const vrx_d2 v2 = {acc[r][q][0], acc[r][q][1]};
-                            asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(o), "v"(v2) : "memory");
-                        } else
-#endif
                         if (!PADK)
                             *reinterpret_cast<double2*>(o) = make_double2(acc[r][q][0], acc[r][q][1]);
                         else if (PADK == 2) {  // even K and stride: the pair is whole or absent
@@ -1166,10 +1062,6 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
                     } else if (MODE == 1) {
                         if (!PADK || slice < K) dst[row * ld + slice] = acc[r][q][0];
                     } else {  // columns 2*slice, 2*slice+1; S[row][k] = (s1, ss)
-                        if (FORM == 2) {  // acc2 holds S2 = BD @ ID_prob: ss = s1 + s2
-                            acc2[r][q][0] += acc[r][q][0];
-                            acc2[r][q][1] += acc[r][q][1];
-                        }
                         double2* o = reinterpret_cast<double2*>(dst) + row * ld + 2 * slice;
                         if (!PADK || 2 * slice < K)
                             o[0] = make_double2(acc[r][q][0], acc2[r][q][0]);
@@ -1686,11 +1578,7 @@ __global__ __launch_bounds__(VRX_BLOCK) void vrx_theta_partial(
                 const int np = vptr ? vptr[vr + 1] - (int)v : 1;
                 double t = 0.0;
                 if (np == 1) {
-#ifdef VRX_PROBE_ONE_PLANE  // TIMING PROBE ONLY (scratch builds): as if the pass had left ONE plane per tile
-                    const int nr = 1;
-#else
                     const int nr = npiece[v];
-#endif
                     const double* src = P + v * B.Kt + col;
                     for (int r0 = 0; r0 < nr; r0 += 8) {
                         double x[8];
@@ -2175,11 +2063,7 @@ __global__ __launch_bounds__(VRX_BLOCK) void vrx_cell_softmax(
     const int np = live && npiece ? (vptr ? vptr[cell + 1] - (int)pv0 : 1) : 0;
     const int64_t col0 = (int64_t)rb * K;
     if (np == 1) {
-#ifdef VRX_PROBE_ONE_PLANE  // TIMING PROBE ONLY (scratch builds)
-        const int n_range = 1;
-#else
         const int n_range = npiece[pv0];
-#endif
         for (int k = kl; k < K; k += KP) {
             // the loads of 8 ranges are issued together (one memory round trip instead of 8);
             // the additions keep the range order
