@@ -253,6 +253,30 @@ int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double* theta, co
                         double epsilon, double* psi /* n_cell x n_donor */, double* var /* n_cell x n_donor */,
                         double* llr /* n_cell */, int32_t* n_iter /* n_cell */, double* ms3);
 
+/* ---- bulk donor abundance (vrx_bulk.h) ---------------------------------------------------
+ * A bulk sample's per-variant counts and the donors' genotype probabilities, resident on the
+ * device: the operands of VireoBulk.fit (vireoSNP/utils/vireo_bulk.py:44-108) and LikRatio_test
+ * (:120-167).  GT_prob is n_var x n_donor x n_gt, AD / DP are n_var doubles ("BD = DP - AD",
+ * :72 and :151, is formed on the way in).  n_donor >= 1, n_gt >= 2. */
+typedef struct vrx_bulk vrx_bulk;
+int vrx_bulk_create(int device, int64_t n_var, int64_t n_donor, int64_t n_gt, const double* GT_prob,
+                    const double* AD, const double* DP, vrx_bulk** out);
+void vrx_bulk_destroy(vrx_bulk* b);
+/* another sample on the same genotypes (GT_prob stays where it is) */
+int vrx_bulk_set_counts(vrx_bulk* b, const double* AD, const double* DP);
+/* The EM loop of VireoBulk.fit (vireo_bulk.py:75-105) from psi_io / theta_io, which receive the
+ * fitted values.  One pass over GT_prob per iteration plus one: pass p yields logLik[p - 1] and
+ * the sums of update p; the stop rule (:97-105, same order of comparisons) runs on the device.
+ * logLik_trace[0 .. last_it] are the reference's logLik[0 .. it]; last_it is its loop index at
+ * exit.  ms_out (may be NULL): device milliseconds from the first pass to the last. */
+int vrx_bulk_fit(vrx_bulk* b, double* psi_io /* n_donor */, double* theta_io /* n_gt */, int32_t max_iter,
+                 int32_t min_iter, double epsilon, int32_t learn_theta, int32_t delay_fit_theta,
+                 double* logLik_trace /* max_iter */, int32_t* last_it, double* ms_out);
+/* sum_n AD log(t) + BD log(1 - t), t = GT_prob . theta . psi (vireo_bulk.py:94-96, :152-158), for
+ * n_psi vectors at once (eight per pass over GT_prob). */
+int vrx_bulk_loglik(vrx_bulk* b, int64_t n_psi, const double* psi /* n_psi x n_donor */,
+                    const double* theta /* n_gt */, double* out /* n_psi */);
+
 /* ---- timing (bench.py roofline leg) ---------------------------------------------------
  * When enabled, every launch of a pass kernel is bracketed by hipEvents on the model's
  * stream; totals are read back after a sync.  Kernel ids: */

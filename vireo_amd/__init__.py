@@ -1,7 +1,7 @@
 """vireo_amd -- MI355X-native implementation of vireoSNP's variational-EM hot path.
 
 Same names as the reference package surface (vireoSNP/__init__.py:7-15) for the path
-that is in scope: ``Vireo``, ``BinomMixtureVB``, ``vireo_wrap`` and the helpers they use.
+that is in scope: ``Vireo``, ``BinomMixtureVB``, ``vireo_wrap``, ``VireoBulk`` / ``LikRatio_test`` and the helpers they use.
 Host code is plain Python/NumPy; all per-iteration arithmetic runs in hand-written HIP
 kernels for gfx950 behind a ctypes C ABI (include/vireo_hip.h).  There is no CPU
 fallback and no PyTorch in the compute path.
@@ -21,9 +21,10 @@ from .bmm_model import BinomMixtureVB
 from .vireo_doublet import predict_doublet, add_doublet_GT, add_doublet_theta, predit_ambient
 from .variant_select import variant_ELBO_gain
 from .vireo_wrap import vireo_wrap
+from .vireo_bulk import VireoBulk, LikRatio_test, BulkData, device_bulk
 
 __all__ = ["__version__", "Vireo", "BinomMixtureVB", "vireo_wrap", "predict_doublet",
-           "predit_ambient", "variant_ELBO_gain",
+           "predit_ambient", "variant_ELBO_gain", "VireoBulk", "LikRatio_test", "BulkData", "device_bulk",
            "DeviceCounts", "device_counts", "load_VCF", "match_SNPs", "read_cellSNP",
            "read_vartrix", "normalize", "tensor_normalize", "loglik_amplify", "get_binom_coeff",
            "binom_coeff_sum", "beta_entropy", "match", "optimal_match", "donor_select",

@@ -16,6 +16,7 @@
 #include "vrx_kernels.h"
 #include "vrx_build.h"
 #include "vrx_ambient.h"
+#include "vrx_bulk.h"
 
 // (vrx_set_error / vrx_last_error: vrx_host.cpp, so that the host-only translation unit links on
 //  its own for the sanitizer build of tests/test_host_sanitizers_cpu.py)
@@ -3499,5 +3500,195 @@ extern "C" int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double
             ms3[i] = t;
         }
     }
+    return VRX_OK;
+}
+
+// ---- bulk donor abundance (vrx_bulk.h) --------------------------------------------------------
+struct vrx_bulk {
+    int device = 0, n_cu = 0;
+    int64_t N = 0;
+    int K = 0, G = 0;
+    int T = 0, n_wg = 0;       // the fit pass: variants per tile, workgroups
+    int T_ll = 0, n_wg_ll = 0; // the log-likelihood pass
+    size_t lds = 0, lds_ll = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    DevBuf<double> P;
+    DevBuf<double2> AB;  // (AD, BD) per variant
+    DevBuf<double> par;     // psi[K] | theta[G]
+    DevBuf<double> part;    // per-workgroup partials of either pass
+    DevBuf<double> trace;   // logLik, max_iter of the largest fit so far
+    DevBuf<double> psis, out;  // VRX_BULK_Q x K, VRX_BULK_Q
+    DevBuf<int32_t> ctl;
+};
+
+// variants per tile: even, <= 256 (a lane per variant), inside the LDS budget; at least 2
+static int bulk_tile(int64_t N, int K, int G, bool fit) {
+    const VrxBulkShape h0 = vrx_bulk_shape(K, G, 0);
+    const size_t fixed = (fit ? vrx_bulk_lds_doubles(h0) : vrx_bulk_ll_lds_doubles(h0)) * sizeof(double);
+    const size_t per = (size_t)(fit ? h0.S + h0.SK + 2 : h0.S) * sizeof(double);
+    const size_t budget = VRX_BULK_LDS_TILE;
+    int64_t T = budget > fixed ? (int64_t)((budget - fixed) / per) : 0;
+    T = std::min<int64_t>(T, VRX_BULK_BLOCK);
+    T = std::min<int64_t>(T, N + (N & 1));
+    T &= ~(int64_t)1;
+    return (int)std::max<int64_t>(T, 2);
+}
+
+static int bulk_upload_counts(vrx_bulk* b, const double* AD, const double* DP) {
+    std::vector<double2> ab((size_t)b->N);
+    for (int64_t n = 0; n < b->N; ++n) ab[(size_t)n] = make_double2(AD[n], DP[n] - AD[n]);
+    VRX_HIP(b->AB.upload(ab.data(), (size_t)b->N, b->stream));
+    VRX_HIP(hipStreamSynchronize(b->stream));  // (ab dies at return)
+    return VRX_OK;
+}
+
+extern "C" void vrx_bulk_destroy(vrx_bulk* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    if (b->t0) (void)hipEventDestroy(b->t0);
+    if (b->t1) (void)hipEventDestroy(b->t1);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    delete b;
+}
+
+extern "C" int vrx_bulk_create(int device, int64_t n_var, int64_t n_donor, int64_t n_gt, const double* GT_prob,
+                               const double* AD, const double* DP, vrx_bulk** out) {
+    VRX_REQUIRE(GT_prob && AD && DP && out, "vrx_bulk_create: null argument");
+    VRX_REQUIRE(n_var >= 1 && n_var < ((int64_t)1 << 31) - 512 && n_donor >= 1 && n_gt >= 2,
+                "vrx_bulk_create: 1 <= n_var < 2^31 - 512, n_donor >= 1, n_gt >= 2");
+    VRX_REQUIRE(n_donor * n_gt <= (1 << 20), "vrx_bulk_create: n_donor x n_gt too large");
+    int ndev = 0;
+    vrx_device_count(&ndev);
+    if (device < 0 || device >= ndev) {
+        vrx_set_error("vrx_bulk_create: device %d not available (%d HIP devices visible)", device, ndev);
+        return VRX_ERR_HIP;
+    }
+    VRX_HIP(hipSetDevice(device));
+    struct Del {
+        void operator()(vrx_bulk* b) const { vrx_bulk_destroy(b); }
+    };
+    std::unique_ptr<vrx_bulk, Del> b(new vrx_bulk());
+    b->device = device;
+    b->N = n_var;
+    b->K = (int)n_donor;
+    b->G = (int)n_gt;
+    hipDeviceProp_t prop;
+    VRX_HIP(hipGetDeviceProperties(&prop, device));
+    b->n_cu = prop.multiProcessorCount;
+    // what a launch may ask for without the opt-in attribute (the device property may say more)
+    const size_t lds_max = std::min<size_t>(prop.sharedMemPerBlock, 64 * 1024);
+    b->T = bulk_tile(n_var, b->K, b->G, true);
+    b->T_ll = bulk_tile(n_var, b->K, b->G, false);
+    b->lds = vrx_bulk_lds_doubles(vrx_bulk_shape(b->K, b->G, b->T)) * sizeof(double);
+    b->lds_ll = vrx_bulk_ll_lds_doubles(vrx_bulk_shape(b->K, b->G, b->T_ll)) * sizeof(double);
+    VRX_REQUIRE(b->lds <= lds_max && b->lds_ll <= lds_max && (size_t)(b->K + 2 * b->G + 2) * sizeof(double) <= lds_max,
+                "vrx_bulk_create: n_donor x n_gt = %lld x %lld needs %zu bytes of LDS per workgroup (limit %zu)",
+                (long long)n_donor, (long long)n_gt, std::max(b->lds, b->lds_ll), lds_max);
+    // workgroups: as many as stay resident (LDS-bound, at most 4 per CU), each walking tiles grid-stride
+    auto grid = [&](int T, size_t lds) {
+        const int64_t n_tile = (n_var + T - 1) / T;
+        const int per_cu = (int)std::min<size_t>(4, std::max<size_t>(1, (size_t)(160 * 1024) / lds));
+        return (int)std::min<int64_t>(n_tile, (int64_t)b->n_cu * per_cu);
+    };
+    b->n_wg = grid(b->T, b->lds);
+    b->n_wg_ll = grid(b->T_ll, b->lds_ll);
+    VRX_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    VRX_HIP(hipEventCreate(&b->t0));
+    VRX_HIP(hipEventCreate(&b->t1));
+    VRX_HIP(b->P.upload(GT_prob, (size_t)(n_var * n_donor * n_gt), b->stream));
+    int rc = bulk_upload_counts(b.get(), AD, DP);
+    if (rc) return rc;
+    VRX_HIP(b->par.alloc((size_t)(b->K + b->G)));
+    VRX_HIP(b->part.alloc(std::max((size_t)b->n_wg * (b->K + 2 * b->G + 1), (size_t)b->n_wg_ll * VRX_BULK_Q)));
+    VRX_HIP(b->psis.alloc((size_t)VRX_BULK_Q * b->K));
+    VRX_HIP(b->out.alloc(VRX_BULK_Q));
+    VRX_HIP(b->ctl.alloc(VRX_BULK_CTL_WORDS));
+    *out = b.release();
+    return VRX_OK;
+}
+
+extern "C" int vrx_bulk_set_counts(vrx_bulk* b, const double* AD, const double* DP) {
+    VRX_REQUIRE(b && AD && DP, "vrx_bulk_set_counts: null argument");
+    VRX_HIP(hipSetDevice(b->device));
+    return bulk_upload_counts(b, AD, DP);
+}
+
+extern "C" int vrx_bulk_fit(vrx_bulk* b, double* psi_io, double* theta_io, int32_t max_iter, int32_t min_iter,
+                            double epsilon, int32_t learn_theta, int32_t delay_fit_theta, double* logLik_trace,
+                            int32_t* last_it, double* ms_out) {
+    VRX_REQUIRE(b && psi_io && theta_io && logLik_trace && last_it, "vrx_bulk_fit: null argument");
+    VRX_REQUIRE(max_iter >= 1, "vrx_bulk_fit: max_iter must be >= 1");
+    VRX_HIP(hipSetDevice(b->device));
+    hipStream_t s = b->stream;
+    const int K = b->K, G = b->G, W = K + 2 * G + 1;
+    if (b->trace.n < (size_t)max_iter) VRX_HIP(b->trace.alloc((size_t)max_iter));
+    VRX_HIP(hipMemcpyAsync(b->par.p, psi_io, (size_t)K * sizeof(double), hipMemcpyHostToDevice, s));
+    VRX_HIP(hipMemcpyAsync(b->par.p + K, theta_io, (size_t)G * sizeof(double), hipMemcpyHostToDevice, s));
+    VRX_HIP(hipMemsetAsync(b->ctl.p, 0, VRX_BULK_CTL_WORDS * sizeof(int32_t), s));
+    // As in vrx_model_fit: the stop rule runs on the device (vrx_bulk_finish); the host enqueues a
+    // batch of passes, then reads the control words.  The first batch reaches the first pass the
+    // rule can fire after; a kernel launched behind the stop returns at once.
+    const int batch = VRX_BULK_BATCH;
+    const int64_t n_pass = (int64_t)max_iter + 1;  // pass p closes iteration p - 1
+    int64_t next = 0;
+    int32_t hctl[VRX_BULK_CTL_WORDS] = {};
+    VRX_HIP(hipEventRecord(b->t0, s));
+    while (next < n_pass && !hctl[VRX_BULK_STOP]) {
+        const int64_t first = std::max<int64_t>((int64_t)std::max(min_iter, 0) + 3, batch);
+        const int64_t upto = std::min(n_pass, next == 0 ? first : next + batch);
+        for (; next < upto; ++next) {
+            if (G == 3)
+                vrx_bulk_pass<3><<<b->n_wg, VRX_BULK_BLOCK, b->lds, s>>>((int)b->N, K, G, b->T, b->P.p, b->AB.p,
+                                                                         b->par.p, b->ctl.p, b->part.p);
+            else
+                vrx_bulk_pass<0><<<b->n_wg, VRX_BULK_BLOCK, b->lds, s>>>((int)b->N, K, G, b->T, b->P.p, b->AB.p,
+                                                                         b->par.p, b->ctl.p, b->part.p);
+            vrx_bulk_finish<<<1, 1024, (size_t)(W + 1) * sizeof(double), s>>>(
+                b->n_wg, K, G, b->part.p, b->par.p, b->trace.p, b->ctl.p, min_iter, max_iter, epsilon, learn_theta,
+                delay_fit_theta);
+        }
+        VRX_HIP(hipGetLastError());
+        VRX_HIP(hipEventRecord(b->t1, s));
+        VRX_HIP(hipMemcpyAsync(hctl, b->ctl.p, sizeof hctl, hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipStreamSynchronize(s));
+    }
+    VRX_REQUIRE(hctl[VRX_BULK_STOP], "vrx_bulk_fit: the loop ended without its last iteration");
+    const int it = hctl[VRX_BULK_IT];
+    *last_it = it;
+    VRX_HIP(hipMemcpyAsync(logLik_trace, b->trace.p, (size_t)(it + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(psi_io, b->par.p, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(theta_io, b->par.p + K, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    if (ms_out) {
+        float ms = 0.f;
+        VRX_HIP(hipEventElapsedTime(&ms, b->t0, b->t1));
+        *ms_out = ms;
+    }
+    return VRX_OK;
+}
+
+extern "C" int vrx_bulk_loglik(vrx_bulk* b, int64_t n_psi, const double* psi, const double* theta, double* out) {
+    VRX_REQUIRE(b && psi && theta && out, "vrx_bulk_loglik: null argument");
+    VRX_REQUIRE(n_psi >= 1, "vrx_bulk_loglik: n_psi must be >= 1");
+    VRX_HIP(hipSetDevice(b->device));
+    hipStream_t s = b->stream;
+    const int K = b->K, G = b->G;
+    VRX_HIP(hipMemcpyAsync(b->par.p + K, theta, (size_t)G * sizeof(double), hipMemcpyHostToDevice, s));
+    for (int64_t q0 = 0; q0 < n_psi; q0 += VRX_BULK_Q) {
+        const int nq = (int)std::min<int64_t>(VRX_BULK_Q, n_psi - q0);
+        VRX_HIP(hipMemcpyAsync(b->psis.p, psi + q0 * K, (size_t)nq * K * sizeof(double), hipMemcpyHostToDevice, s));
+        if (G == 3)
+            vrx_bulk_ll<3><<<b->n_wg_ll, VRX_BULK_BLOCK, b->lds_ll, s>>>((int)b->N, K, G, b->T_ll, nq, b->P.p, b->AB.p,
+                                                                         b->psis.p, b->par.p + K, b->part.p);
+        else
+            vrx_bulk_ll<0><<<b->n_wg_ll, VRX_BULK_BLOCK, b->lds_ll, s>>>((int)b->N, K, G, b->T_ll, nq, b->P.p, b->AB.p,
+                                                                         b->psis.p, b->par.p + K, b->part.p);
+        vrx_bulk_ll_sum<<<1, 1024, 0, s>>>(b->n_wg_ll, nq, b->part.p, b->out.p);
+        VRX_HIP(hipGetLastError());
+        VRX_HIP(hipMemcpyAsync(out + q0, b->out.p, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    VRX_HIP(hipStreamSynchronize(s));
     return VRX_OK;
 }
