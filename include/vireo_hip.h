@@ -75,6 +75,9 @@ int vrx_problem_create2(int device, int64_t n_var, int64_t n_cell, int64_t nnz,
 /* info4 = { variant stream balanced (0 | 1), cell stream balanced, seconds the balancing added to the build,
  * built on the device (0 | 1) } */
 int vrx_problem_build_info(vrx_problem* p, double* info4);
+/* fmt2 = { entry format of the variant orientation, of the cell orientation }: 0 = 4 B, 1 = 8 B, 2 = 12 B per
+ * entry; the narrowest that holds the counts and the index, or the wider one VIREO_ENTRY_FMT asked for */
+int vrx_problem_entry_format(vrx_problem* p, int32_t* fmt2);
 void vrx_problem_destroy(vrx_problem* p);
 
 /* sum over entries with dp>0 of float32(min(log C(dp,ad), 700)), accumulated in float64.
@@ -205,7 +208,8 @@ int vrx_model_get_elbo_parts(vrx_model* m, double* parts4);
  * (add_doublet_GT, :105-136) is formed on the fly inside the kernel that builds the cell
  * pass's W tables; logLik / prob_out are (n_cell x C), C = K + K(K-1)/2 (singlets first,
  * pairs in itertools.combinations order).  psi*: digammas of the T + T(T-1)/2 class thetas
- * of add_doublet_theta (:85-102), (psi_rows x G).  n_gt <= 3. */
+ * of add_doublet_theta (:85-102), (psi_rows x G).  n_donor >= 2; every n_gt a model can have
+ * (1 .. 8, so G <= 36): the classes are formed one at a time, never as a table. */
 int vrx_problem_doublet(vrx_problem* p, int64_t n_donor, int64_t n_gt,
                         const double* GT_prob /* n_var x n_donor x n_gt */,
                         const double* psi1, const double* psi2, const double* psis,
@@ -222,7 +226,9 @@ int vrx_problem_donor_reads(vrx_problem* p, int64_t n_col, const double* ID_prob
 /* One-shot cell log-likelihood against caller-supplied genotype/theta tables:
  *   logLik[m,c] = sum_n sum_g GT[n,c,g] * (AD[n,m] psi1[g] + BD[n,m] psi2[g] - DP[n,m] psis[g])
  * with psi*(n_rows_psi x G): the 3*G transposed products of predict_doublet
- * (vireoSNP/utils/vireo_doublet.py:53-62), C = K + K(K-1)/2 columns, G = 6 classes.
+ * (vireoSNP/utils/vireo_doublet.py:53-62); any n_col >= 1 and n_class <= 8 (the class limit of the
+ * dense kernels: an explicit doublet table fits for n_GT <= 3 only, G = T + T(T-1)/2 = 6 classes --
+ * predict_doublet uses vrx_problem_doublet, which has no such limit).
  * If prob_out is non-NULL it receives softmax_c(logLik + log ID_prior)
  * (vireo_doublet.py:67-68; ID_prior rows as in vrx_model_set_prior). */
 int vrx_problem_cell_loglik(vrx_problem* p, int64_t n_col, int64_t n_class,

@@ -23,17 +23,19 @@ def theta_of(GT_prob, beta_mu):
     return np.tensordot(GT_prob, beta_mu[0, :], axes=(2, 0))
 
 
-def fit_cell(a, b, th, psi0, min_iter=20, max_iter=200, eps=1e-3):
+def fit_cell(a, b, th, psi0, min_iter=20, max_iter=200, eps=1e-3, dtype=float):
     """one cell: a, b (n_e,) counts of its selected entries, th (n_e, K) their theta rows.
-    -> psi, var, llr, it (the loop index at exit, as in the reference)"""
-    a = np.asarray(a, float)
-    b = np.asarray(b, float)
+    -> psi, var, llr, it (the loop index at exit, as in the reference).  ``dtype=np.longdouble``
+    runs the same statements in extended precision (is a cell's exit decided by rounding?)"""
+    a = np.asarray(a, dtype)
+    b = np.asarray(b, dtype)
+    th = np.asarray(th, dtype)
     K = th.shape[1]
     if a.sum() + b.sum() == 0:           # 0 / 0 in the reference: NaN, the loop never breaks
         nan = np.full(K, np.nan)
         return nan, nan.copy(), np.nan, max_iter - 1
-    psi = np.array(psi0, float)
-    ll = np.zeros(max_iter)
+    psi = np.array(psi0, dtype)
+    ll = np.zeros(max_iter, dtype)
     for it in range(max_iter):
         t1 = th @ psi
         t0 = (1 - th) @ psi

@@ -184,6 +184,34 @@ def main():
              doublet_prob=dbl, singlet_prob=sing, doublet_LLR=llr,
              GT_prob_after_doublet=mm_.GT_prob)
 
+    doublet_cases()
+
+
+# the doublet step at other genotype-class counts and in ASE mode: (tag, n_GT, K, ASE_mode, fit iterations)
+DOUBLET_CASES = [("t2k3", 2, 3, False, 5), ("t4k3", 4, 3, False, 6), ("t5k2", 5, 2, False, 4),
+                 ("t4k5_ase", 4, 5, True, 5), ("t3k4_ase", 3, 4, True, 3)]
+DOUBLET_SHAPE = (300, 200, 0.05)
+
+
+def doublet_cases():
+    """synth_dbl_*: a short fit and predict_doublet of the reference on small synthetic counts
+    (`python tests/golden/make_golden.py doublet` writes these alone)"""
+    n, mm, dens = DOUBLET_SHAPE
+    for tag, n_gt, k, ase, iters in DOUBLET_CASES:
+        sAD, sDP = synth_donor(n, mm, k, dens, seed=0)
+        np.random.seed(1)
+        m = Vireo(n_var=n, n_cell=mm, n_donor=k, n_GT=n_gt, ASE_mode=ase)
+        init = state(m, "init_")
+        quiet(m.fit, sAD, sDP, min_iter=2, max_iter=iters, delay_fit_theta=1, verbose=False)
+        end = state(m, "end_")
+        dbl, sing, llr = quiet(predict_doublet, m, sAD, sDP)
+        save("synth_dbl_" + tag, **pack(sAD, sDP), ELBO_=m.ELBO_, **init, **end,
+             doublet_prob=dbl, singlet_prob=sing, doublet_LLR=llr,
+             GT_prob_after_doublet=m.GT_prob)
+
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["doublet"]:
+        doublet_cases()
+    else:
+        main()

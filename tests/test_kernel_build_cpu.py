@@ -137,3 +137,14 @@ def test_balance_greedy_column_loop_waits_for_no_memory(isa):
     head = body[heads[0]:nxt]
     assert not any("s_waitcnt vmcnt" in l for l in head), [l for l in head if "waitcnt" in l]
     assert any("ds_bpermute_b32" in l for l in body) and any("row_mirror" in l for l in body)
+
+
+def test_doublet_table_kernel_keeps_its_registers(isa):
+    """vrx_doublet_w forms the T + T(T-1)/2 classes of a donor pair one at a time (no per-thread table),
+    so every n_GT up to VRX_MAXT runs in registers: no VGPR / SGPR spill, no scratch."""
+    _, report = isa
+    block = [b for b in re.split(r"remark: [^\n]*Function Name: ", report)[1:] if "vrx_doublet_w" in b.split()[0]]
+    assert len(block) == 1, [b.split()[0] for b in block]
+    get = lambda key: int(re.search(key + r": (\d+)", block[0]).group(1))      # noqa: E731
+    r = dict(vgpr_spill=get("VGPRs Spill"), sgpr_spill=get("SGPRs Spill"), scratch=get(r"ScratchSize \[bytes/lane\]"))
+    assert r == dict(vgpr_spill=0, sgpr_spill=0, scratch=0), r

@@ -172,6 +172,31 @@ def test_synthetic_generator_and_fit(tag, shape):
     eq(st.GT_prob, g["GT_prob_after_doublet"])
 
 
+@pytest.mark.parametrize("tag,n_gt,k,ase,iters", [("t2k3", 2, 3, False, 5), ("t4k3", 4, 3, False, 6),
+                                                  ("t5k2", 5, 2, False, 4), ("t4k5_ase", 4, 5, True, 5),
+                                                  ("t3k4_ase", 3, 4, True, 3)])
+def test_doublet_other_class_counts_and_ase_mode(tag, n_gt, k, ase, iters):
+    """the oracle's doublet step at n_GT = 2, 4, 5 and in ASE mode (theta per variant), bit for bit the
+    reference's predict_doublet: the yardstick of tests/test_gpu_postfit_sweep.py"""
+    g = gold.load("synth_dbl_" + tag)
+    AD, DP = O.synth_donor(300, 200, k, 0.05, seed=0)
+    gAD, gDP = gold.unpack(g)
+    assert (AD != gAD).nnz == 0 and (DP != gDP).nnz == 0
+    np.random.seed(1)
+    st = O.vireo_new(200, 300, k, n_GT=n_gt, ASE_mode=ase)
+    _check_state(st, g, "init_")
+    O.vireo_fit(st, AD, DP, min_iter=2, max_iter=iters, delay_fit_theta=1)
+    eq(st.ELBO_, g["ELBO_"])
+    _check_state(st, g, "end_")
+    assert st.GT_prob.shape == (300, k, n_gt) and st.beta_mu.shape == (300 if ase else 1, n_gt)
+    dbl, sing, llr = O.vireo_doublet(st, AD, DP)
+    assert dbl.shape == (200, k * (k - 1) // 2)
+    eq(dbl, g["doublet_prob"])
+    eq(sing, g["singlet_prob"])
+    eq(llr, g["doublet_LLR"])
+    eq(st.GT_prob, g["GT_prob_after_doublet"])
+
+
 def test_fuzz_arbiter_fixture_is_the_oracles_problem():
     """tests/golden/fuzz_arbiter.npz (80-bit end states of the sweep's deviation cases,
     make_bmm_arbiter.py) against the oracle on two of its smaller cases: same problem, same

@@ -46,6 +46,7 @@ SIGNATURES = {
     "vrx_problem_create2": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, _I64, _I32, _I32,
                                       _I32, C.c_int32, C.POINTER(_P)]),
     "vrx_problem_build_info": (C.c_int, [_P, _D]),
+    "vrx_problem_entry_format": (C.c_int, [_P, _I32]),
     "vrx_problem_destroy": (None, [_P]),
     "vrx_problem_binom_const": (C.c_int, [_P, _D]),
     "vrx_problem_n_vars": (C.c_int, [_P, _I32]),

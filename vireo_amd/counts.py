@@ -151,6 +151,12 @@ class DeviceCounts:
         return dict(balanced_variant=bool(a[0]), balanced_cell=bool(a[1]), balance_seconds=float(a[2]),
                     device_built=bool(a[3]))
 
+    def entry_format(self):
+        """(variant orientation, cell orientation): 0 / 1 / 2 = 4 / 8 / 12 bytes per entry (VIREO_ENTRY_FMT)"""
+        a = np.zeros(2, dtype=np.int32)
+        _lib.check(_lib.lib().vrx_problem_entry_format(self._h, a.ctypes.data_as(C.POINTER(C.c_int32))))
+        return int(a[0]), int(a[1])
+
     @property
     def handle(self):
         return self._h

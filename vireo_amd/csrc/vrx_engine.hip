@@ -1822,6 +1822,13 @@ extern "C" int vrx_problem_build_info(vrx_problem* p, double* info4) {
     return VRX_OK;
 }
 
+extern "C" int vrx_problem_entry_format(vrx_problem* p, int32_t* fmt2) {
+    VRX_REQUIRE(p && fmt2, "vrx_problem_entry_format: null argument");
+    fmt2[0] = p->by_var.fmt;
+    fmt2[1] = p->by_cell.fmt;
+    return VRX_OK;
+}
+
 extern "C" int vrx_problem_n_vars(vrx_problem* p, int32_t* out) {
     VRX_REQUIRE(p && out, "vrx_problem_n_vars: null argument");
     std::memcpy(out, p->n_vars.data(), p->n_vars.size() * sizeof(int32_t));
@@ -3278,8 +3285,8 @@ extern "C" int vrx_problem_doublet(vrx_problem* p, int64_t n_donor, int64_t n_gt
                                    const double* psis, int64_t psi_rows, const double* ID_prior,
                                    int64_t id_rows, double* logLik, double* prob_out) {
     VRX_REQUIRE(p && GT_prob && psi1 && psi2 && psis && logLik, "vrx_problem_doublet: null argument");
-    VRX_REQUIRE(n_donor >= 2 && n_gt >= 1 && n_gt <= 3,
-                "vrx_problem_doublet: needs n_donor >= 2 and n_GT <= 3");
+    VRX_REQUIRE(n_donor >= 2 && n_gt >= 1 && n_gt <= VRX_MAXT,
+                "vrx_problem_doublet: needs n_donor >= 2 and 1 <= n_GT <= %d", VRX_MAXT);
     VRX_REQUIRE(psi_rows == 1 || psi_rows == p->n_var, "vrx_problem_doublet: psi rows must be 1 or n_var");
     const int64_t C = n_donor + n_donor * (n_donor - 1) / 2;
     const int G = (int)(n_gt + n_gt * (n_gt - 1) / 2);

@@ -1872,9 +1872,13 @@ __global__ __launch_bounds__(VRX_BLOCK) void vrx_gt_update(
 //   both[t]       = p_t q_t                                   (same genotype)
 //   both[T + m]   = p_{g1} q_{g2} + p_{g2} q_{g1}             (m-th genotype pair g1 < g2)
 // normalised over the classes.  The N x C x (T + T(T-1)/2) tensor the reference
-// materialises (653 MB at N=100k, K=16) never exists: each thread forms its classes in
-// registers and writes W[n][c] = (sum_g both_g (psi1_g - psi2_g), sum_g both_g (psi2_g - psis_g)).
-// psi*: [rows][G] with G = T + T(T-1)/2 classes (rows = N in ASE mode, else 1).  T <= 3.
+// materialises (653 MB at N=100k, K=16) never exists: each thread forms its classes one at a
+// time and writes W[n][c] = (sum_g both_g (psi1_g - psi2_g), sum_g both_g (psi2_g - psis_g)).
+// A pair column walks its classes twice: first for the normaliser, then for raw_g / sum times
+// the weights -- the reference's order (normalise, then weight), the same operations in the
+// same sequence as a table of normalised classes would give, and no per-thread array, so any
+// T <= VRX_MAXT (G <= 36) keeps its registers.
+// psi*: [rows][G] with G = T + T(T-1)/2 classes (rows = N in ASE mode, else 1).
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(VRX_BLOCK) void vrx_doublet_w(
     int64_t N, int K, int T, int C, int ase, const double* __restrict__ GT,
@@ -1891,34 +1895,28 @@ __global__ __launch_bounds__(VRX_BLOCK) void vrx_doublet_w(
     const double* p1 = psi1 + pr * G;
     const double* p2 = psi2 + pr * G;
     const double* ps = psis + pr * G;
-    double both[6];
-#pragma unroll
-    for (int g = 0; g < 6; ++g) both[g] = 0.0;
+    double w1 = 0.0, w2 = 0.0, wa = 0.0;
+    auto add = [&](int g, double both) {
+        w1 += both * (p1[g] - p2[g]);
+        w2 += both * (p2[g] - ps[g]);
+        wa += both * (p1[g] - ps[g]);
+    };
     if (c < K) {
-        for (int t = 0; t < T; ++t) both[t] = GT[(n * K + c) * T + t];
+        const double* p = GT + (n * K + c) * T;
+        for (int t = 0; t < T; ++t) add(t, p[t]);
+        for (int g = T; g < G; ++g) add(g, 0.0);  // (the zero mixed classes of a single donor)
     } else {
         const int2 ab = pair[c - K];
         const double* p = GT + (n * K + ab.x) * T;
         const double* q = GT + (n * K + ab.y) * T;
         double sum = 0.0;
-        for (int t = 0; t < T; ++t) {
-            both[t] = p[t] * q[t];
-            sum += both[t];
-        }
+        for (int t = 0; t < T; ++t) sum += p[t] * q[t];
+        for (int g1 = 0; g1 < T; ++g1)
+            for (int g2 = g1 + 1; g2 < T; ++g2) sum += p[g1] * q[g2] + p[g2] * q[g1];
+        for (int t = 0; t < T; ++t) add(t, p[t] * q[t] / sum);
         int m = T;
         for (int g1 = 0; g1 < T; ++g1)
-            for (int g2 = g1 + 1; g2 < T; ++g2) {
-                both[m] = p[g1] * q[g2] + p[g2] * q[g1];
-                sum += both[m];
-                ++m;
-            }
-        for (int g = 0; g < G; ++g) both[g] = both[g] / sum;
-    }
-    double w1 = 0.0, w2 = 0.0, wa = 0.0;
-    for (int g = 0; g < G; ++g) {
-        w1 += both[g] * (p1[g] - p2[g]);
-        w2 += both[g] * (p2[g] - ps[g]);
-        wa += both[g] * (p1[g] - ps[g]);
+            for (int g2 = g1 + 1; g2 < T; ++g2) add(m++, (p[g1] * q[g2] + p[g2] * q[g1]) / sum);
     }
     vrx_store_w(W, wform, n, c, C, w1, w2, wa);
 }

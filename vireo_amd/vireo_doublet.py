@@ -5,8 +5,8 @@ vireoSNP/utils/vireo_doublet.py:11-273 (``predict_doublet``, its two table build
 The K + K(K-1)/2 column cell log-likelihood -- 3*6 transposed sparse products in the
 reference (:53-62) -- is one cell pass on the GPU (``vrx_problem_doublet``); the genotype
 table of the donor pairs (653 MB at N=100k, K=16 in the reference) is formed on the fly in
-the kernel, and the 6 pair thetas are host-side arithmetic on 3 numbers.  ``add_doublet_GT``
-is kept as a public helper (and for n_GT > 3).
+the kernel for every n_GT a model can have, and the T + T(T-1)/2 class thetas are host-side
+arithmetic on T numbers.  ``add_doublet_GT`` is kept as a public helper; nothing here calls it.
 
 ``predit_ambient`` (the reference's spelling) fits one small EM per cell; here every cell is fitted
 in one launch (``vrx_problem_ambient``, vireo_amd/csrc/vrx_ambient.h).
@@ -62,6 +62,8 @@ def predict_doublet(vobj, AD, DP, update_GT=True, update_ID=True,
     (ID_prob <- un-renormalised singlet block, then update_GT_prob)."""
     counts = device_counts(AD, DP)
     K, T = vobj.GT_prob.shape[1], vobj.GT_prob.shape[2]
+    if K < 2:
+        raise ValueError("predict_doublet needs n_donor >= 2 (a doublet is a pair of donors), got %d" % K)
     n_pair = K * (K - 1) // 2
     C_ = K + n_pair
     beta_mu_both, beta_sum_both = add_doublet_theta(vobj.beta_mu, vobj.beta_sum)
@@ -78,18 +80,11 @@ def predict_doublet(vobj, AD, DP, update_GT=True, update_ID=True,
     logLik_ID = np.empty((counts.n_cell, C_))
     ID_prob_both = np.empty((counts.n_cell, C_))
     prior = f64(ID_prior_both)
-    if T <= 3 and K >= 2:
-        # the pair genotype table (add_doublet_GT) is formed inside the kernel, never in memory
-        GT = f64(vobj.GT_prob)
-        _lib.check(_lib.lib().vrx_problem_doublet(
-            counts.handle, K, T, dptr(GT), dptr(psi1), dptr(psi2), dptr(psis), psi1.shape[0],
-            dptr(prior), prior.shape[0], dptr(logLik_ID), dptr(ID_prob_both)))
-    else:   # unusual n_GT: explicit table, same cell pass
-        GT_both = f64(add_doublet_GT(vobj.GT_prob))
-        _lib.check(_lib.lib().vrx_problem_cell_loglik(
-            counts.handle, C_, GT_both.shape[2], dptr(GT_both), dptr(psi1), dptr(psi2),
-            dptr(psis), psi1.shape[0], dptr(prior), prior.shape[0], dptr(logLik_ID),
-            dptr(ID_prob_both)))
+    # the pair genotype table (add_doublet_GT) is formed inside the kernel, never in memory
+    GT = f64(vobj.GT_prob)
+    _lib.check(_lib.lib().vrx_problem_doublet(
+        counts.handle, K, T, dptr(GT), dptr(psi1), dptr(psi2), dptr(psis), psi1.shape[0],
+        dptr(prior), prior.shape[0], dptr(logLik_ID), dptr(ID_prob_both)))
 
     logLik_ratio = (logLik_ID[:, vobj.n_donor:].max(1) -
                     logLik_ID[:, :vobj.n_donor].max(1))
