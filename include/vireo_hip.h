@@ -283,6 +283,24 @@ int vrx_bulk_fit(vrx_bulk* b, double* psi_io /* n_donor */, double* theta_io /* 
 int vrx_bulk_loglik(vrx_bulk* b, int64_t n_psi, const double* psi /* n_psi x n_donor */,
                     const double* theta /* n_gt */, double* out /* n_psi */);
 
+/* ---- donor matching (vrx_match.h) -----------------------------------------------------------
+ * The genotype distance between every donor of X and every donor of Z,
+ *   D[i][j] = mean over (n, t) of |X[n][i][t] - Z[n][j][t]|,
+ * in one streaming pass over both tensors: the matrix that optimal_match fills pair by pair with
+ * np.mean(np.abs(...)) (vireoSNP/utils/vireo_base.py:197-201; called by match_VCF_samples,
+ * vcf_utils.py:404-405) and, with Z = X, the one of donor_select (vireo_base.py:230-234).
+ * The operands stay on the host: the call walks them in slabs of block_vars variants (default: the
+ * most that keep each operand's slab at or below 256 MiB), uploads a slab of each, adds the slab's
+ * partial sums and reduces chunks and slabs in order -- no atomics, so two calls with the same
+ * block_vars on the same device are bitwise identical.  A NaN reaches exactly the cells of the donor
+ * that carries it.  n_var, k1, k2, n_gt >= 1; VRX_ERR_UNSUPPORTED when one variant of a 4 x 4 donor
+ * tile does not fit the kernel's LDS (n_gt in the hundreds). */
+int vrx_geno_dist(int device, int64_t n_var, int64_t k1, int64_t k2, int64_t n_gt,
+                  const double* X /* host, n_var x k1 x n_gt */,
+                  const double* Z /* host, n_var x k2 x n_gt; NULL: Z = X, k2 = k1 */,
+                  int64_t block_vars /* variants per upload slab; 0: default */,
+                  double* D /* host, k1 x k2 */, double* ms_out /* kernel ms, may be NULL */);
+
 /* ---- timing (bench.py roofline leg) ---------------------------------------------------
  * When enabled, every launch of a pass kernel is bracketed by hipEvents on the model's
  * stream; totals are read back after a sync.  Kernel ids: */

@@ -1,0 +1,47 @@
+"""Build-time check of the donor-matching kernels (vrx_match.h; no GPU: hipcc cross-compiles gfx950):
+every instance keeps its registers -- no VGPR / SGPR spill, no scratch."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "vireo_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+@pytest.fixture(scope="module")
+def report(tmp_path_factory):
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc")
+    d = tmp_path_factory.mktemp("isa_match")
+    rep = str(d / "usage.txt")
+    with open(rep, "w") as err:
+        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
+                        "--cuda-device-only", "-S", "-o", str(d / "engine.s"), "vrx_engine.hip",
+                        "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, stderr=err, check=True)
+    return open(rep).read()
+
+
+def test_geno_kernels_do_not_spill(report):
+    found = {}
+    for block in re.split(r"remark: [^\n]*Function Name: ", report)[1:]:
+        name = block.split()[0]
+        if "vrx_geno_" not in name:
+            continue
+        get = lambda key: int(re.search(key + r": (\d+)", block).group(1))      # noqa: E731
+        found[name] = dict(vgpr_spill=get("VGPRs Spill"), sgpr_spill=get("SGPRs Spill"),
+                           scratch=get(r"ScratchSize \[bytes/lane\]"))
+    for kernel in ("vrx_geno_pass", "vrx_geno_sum"):
+        assert any(kernel in n for n in found), (kernel, sorted(found))
+    # the n_GT = 3 instance and the generic one of the pass
+    assert len([n for n in found if "vrx_geno_passILi" in n]) == 2
+    for name, r in found.items():
+        assert r == dict(vgpr_spill=0, sgpr_spill=0, scratch=0), (name, r)
+
+
+def test_headers_list_rebuilds_on_the_kernel_header():
+    import __graft_entry__ as g
+    assert "vrx_match.h" in g.HEADERS
+    assert os.path.exists(os.path.join(CSRC, "vrx_match.h"))

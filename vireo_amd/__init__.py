@@ -12,10 +12,11 @@ from . import vcf_utils as vcf
 from . import vireo_base as base
 from . import vireo_model as model
 from .counts import DeviceCounts, device_counts
-from .vcf_utils import load_VCF, match_SNPs
+from .vcf_utils import load_VCF, match_SNPs, match_VCF_samples
 from .io_utils import read_cellSNP, read_vartrix
 from .vireo_base import (normalize, tensor_normalize, loglik_amplify, get_binom_coeff,
-                         binom_coeff_sum, beta_entropy, match, optimal_match, donor_select)
+                         binom_coeff_sum, beta_entropy, match, optimal_match, donor_select,
+                         genotype_distance, donor_match)
 from .vireo_model import Vireo
 from .bmm_model import BinomMixtureVB
 from .vireo_doublet import predict_doublet, add_doublet_GT, add_doublet_theta, predit_ambient
@@ -28,4 +29,5 @@ __all__ = ["__version__", "Vireo", "BinomMixtureVB", "vireo_wrap", "predict_doub
            "DeviceCounts", "device_counts", "load_VCF", "match_SNPs", "read_cellSNP",
            "read_vartrix", "normalize", "tensor_normalize", "loglik_amplify", "get_binom_coeff",
            "binom_coeff_sum", "beta_entropy", "match", "optimal_match", "donor_select",
+           "genotype_distance", "donor_match", "match_VCF_samples",
            "vcf", "base", "model"]

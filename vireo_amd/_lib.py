@@ -82,6 +82,7 @@ SIGNATURES = {
     "vrx_bulk_fit": (C.c_int, [_P, _D, _D, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, _D, _I32,
                                _D]),
     "vrx_bulk_loglik": (C.c_int, [_P, C.c_int64, _D, _D, _D]),
+    "vrx_geno_dist": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _D, _D, C.c_int64, _D, _D]),
     "vrx_model_info": (C.c_int, [_P, _I32]),
     "vrx_model_profile": (C.c_int, [_P, C.c_int32]),
     "vrx_model_profile_read": (C.c_int, [_P, _D, _I64]),

@@ -16,7 +16,7 @@ import numpy as np
 from scipy.sparse import csr_matrix
 
 from . import _lib
-from .vireo_base import match
+from .vireo_base import donor_match, match
 
 _MISSING = (".", "./.", ".|.")
 
@@ -199,6 +199,39 @@ def match_SNPs(SNP_ids1, SNPs_ids2):
     if np.mean(idx == None) == 1:                                  # noqa: E711
         idx = match(SNP_ids1, ["chr" + x for x in SNPs_ids2])
     return idx
+
+
+def match_VCF_samples(VCF_file1, VCF_file2, GT_tag1, GT_tag2):
+    """Align the donors of two VCF files by their genotype probabilities (vcf_utils.py:353-420): the
+    biallelic variants both files hold (with or without the ``chr`` prefix), the distance between every
+    donor of the first and every donor of the second from one pass on the GPU (``donor_match``), and the
+    Hungarian assignment.  GT_tag1 / GT_tag2: GT, GP or PL.  Prints the reference's lines and returns its
+    dict: matched_GPb_diff, matched_donors1, matched_donors2, full_GPb_diff, full_donors1, full_donors2,
+    matched_n_var."""
+    dat1 = load_VCF(VCF_file1, biallelic_only=True, sparse=False, format_list=[GT_tag1])
+    var_ids1 = np.array(dat1['variants'])
+    donors1 = np.array(dat1['samples'])
+    GPb1 = parse_donor_GPb(dat1['GenoINFO'][GT_tag1], GT_tag1)
+    print('Shape for Geno Prob in VCF1:', GPb1.shape)
+
+    dat2 = load_VCF(VCF_file2, biallelic_only=True, sparse=False, format_list=[GT_tag2])
+    var_ids2 = np.array(dat2['variants'])
+    donors2 = np.array(dat2['samples'])
+    GPb2 = parse_donor_GPb(dat2['GenoINFO'][GT_tag2], GT_tag2)
+    print('Shape for Geno Prob in VCF2:', GPb2.shape)
+
+    found = match_SNPs(var_ids2, var_ids1)
+    use2 = np.where(found != None)[0]                              # noqa: E711
+    use1 = found[use2].astype(int)
+    print("n_variants in VCF1, VCF2 and matched: %d, %d, %d" % (var_ids1.shape[0], var_ids2.shape[0], len(use2)))
+
+    idx1, idx2, diff = donor_match(GPb1[use1], GPb2[use2], axis=1, return_delta=True)
+    print("aligned donors:")
+    print(donors1[idx1])
+    print(donors2[idx2])
+    return dict(matched_GPb_diff=diff[idx1, :][:, idx2], matched_donors1=donors1[idx1],
+                matched_donors2=donors2[idx2], full_GPb_diff=diff, full_donors1=donors1,
+                full_donors2=donors2, matched_n_var=len(use1))
 
 
 class _GenoArrays(dict):

@@ -4,9 +4,12 @@ Only what the host needs to prepare the initial state and priors lives here; the
 per-iteration normalisation / amplification / Beta-KL arithmetic of the reference runs
 inside the HIP kernels (vireo_amd/csrc/vrx_kernels.h).
 """
+import ctypes as C
+
 import numpy as np
 
-from .counts import device_counts
+from . import _lib
+from .counts import default_device, device_counts
 
 
 def normalize(X, axis=-1):
@@ -102,6 +105,75 @@ def optimal_match(X, Z, axis=1, return_delta=False):
         xi = np.take(X, i, axis=axis)
         for j in range(nz):
             delta[i, j] = np.mean(np.abs(xi - np.take(Z, j, axis=axis)))
+    idx0, idx1 = linear_sum_assignment(delta)
+    return (idx0, idx1, delta) if return_delta else (idx0, idx1)
+
+
+MAX_GT_MATCH = 64      # genotype classes per donor that genotype_distance accepts
+
+
+def _canonical_genotypes(A, axis, name):
+    """(n_var, K, n_gt) float64 C-contiguous view of a 2-D or 3-D array whose donors lie along ``axis``
+    (no copy when it already is one); ValueError otherwise"""
+    A = np.asarray(A)
+    if A.dtype.kind not in "iufb":
+        raise ValueError("%s has unsupported dtype %s" % (name, A.dtype))
+    if A.ndim not in (2, 3):
+        raise ValueError("%s must be 2-D or 3-D, got shape %s" % (name, A.shape))
+    if not -A.ndim <= axis < A.ndim:
+        raise ValueError("axis %d is out of range for %s of shape %s" % (axis, name, A.shape))
+    A = np.moveaxis(A, axis, 1)
+    if A.ndim == 2:
+        A = A[:, :, None]
+    return np.ascontiguousarray(A, dtype=np.float64)
+
+
+def genotype_distance(X, Z=None, axis=1, block_vars=None):
+    """(K1, K2) matrix of the mean absolute difference between every slice of X and every slice of Z along
+    ``axis`` -- the ``diff_mat`` that optimal_match fills pair by pair (vireo_base.py:197-201) -- in one
+    streaming pass on the GPU (``vrx_geno_dist``).  ``Z=None`` compares X with itself (the matrix of
+    donor_select, :230-234).  X and Z are 2-D or 3-D and agree on every axis but ``axis``; float64
+    C-contiguous (n_var, K, n_gt) inputs are used as they are, anything else is moved and copied once on
+    the host.  ``block_vars``: variants per upload slab (default: 256 MiB per operand).  No variants at
+    all: all NaN, like np.mean of an empty array.  There is no CPU fallback."""
+    Xc = _canonical_genotypes(X, axis, "X")
+    Zc = None if Z is None else _canonical_genotypes(Z, axis, "Z")
+    n_var, k1, n_gt = Xc.shape
+    k2 = k1
+    if Zc is not None:
+        if Zc.shape[0] != n_var or Zc.shape[2] != n_gt:
+            raise ValueError("X %s and Z %s differ off axis %d" % (np.shape(X), np.shape(Z), axis))
+        k2 = Zc.shape[1]
+    if k1 < 1 or k2 < 1 or n_gt < 1:
+        raise ValueError("X %s and Z %s need at least one slice along axis %d and one genotype"
+                         % (np.shape(X), np.shape(Z) if Z is not None else None, axis))
+    if n_gt > MAX_GT_MATCH:
+        raise ValueError("%d genotype classes per donor (at most %d)" % (n_gt, MAX_GT_MATCH))
+    block_vars = 0 if block_vars is None else int(block_vars)
+    if block_vars < 0:
+        raise ValueError("block_vars must be positive (or None / 0 for the default)")
+    if n_var == 0:
+        return np.full((k1, k2), np.nan)
+    return _geno_dist(Xc, Zc, block_vars)[0]
+
+
+def _geno_dist(Xc, Zc, block_vars=0):
+    """-> (D, kernel ms) of canonical operands (n_var, K, n_gt), float64 C-contiguous; Zc None: Xc itself"""
+    _lib.require_gpu()
+    n_var, k1, n_gt = Xc.shape
+    k2 = k1 if Zc is None else Zc.shape[1]
+    D = np.empty((k1, k2))
+    ms = C.c_double(0.0)
+    _lib.check(_lib.lib().vrx_geno_dist(default_device(), n_var, k1, k2, n_gt, _lib.dptr(Xc), _lib.dptr(Zc),
+                                        block_vars, _lib.dptr(D), C.byref(ms)))
+    return D, ms.value
+
+
+def donor_match(X, Z, axis=1, return_delta=False):
+    """optimal_match with the distance matrix from the GPU: Hungarian alignment of the slices of Z to those
+    of X along ``axis`` by ``genotype_distance``; the same return values as optimal_match."""
+    from scipy.optimize import linear_sum_assignment
+    delta = genotype_distance(X, Z, axis=axis)
     idx0, idx1 = linear_sum_assignment(delta)
     return (idx0, idx1, delta) if return_delta else (idx0, idx1)
 
