@@ -301,6 +301,36 @@ int vrx_geno_dist(int device, int64_t n_var, int64_t k1, int64_t k2, int64_t n_g
                   int64_t block_vars /* variants per upload slab; 0: default */,
                   double* D /* host, k1 x k2 */, double* ms_out /* kernel ms, may be NULL */);
 
+/* ---- barcode selection (vrx_barcode.h) -----------------------------------------------------
+ * The greedy rounds of variant_select (vireoSNP/utils/variant_select.py:22-62).  A handle keeps the
+ * categorical genotypes (values 0..9, n_donor <= 128) and the optional var_count on the device; the
+ * host keeps only a class rank per donor (donors with equal barcodes so far share a class, classes
+ * in the string order of their barcodes).
+ * vrx_barcode_create: GT is DONOR-major, n_donor x n_var bytes; var_count n_var doubles or NULL.
+ * vrx_barcode_round replaces the loop over all variants with barcode_entropy (:42-44, :5-19) and the
+ * tie set, median filter and count of :45-52: every variant's entropy is the reference's double,
+ * bit for bit -- the terms in np.unique's order, both sums by np.sum's rule, and entr() read from
+ * `table`, (2 H + 1) x (n_donor + 1) doubles the host filled with scipy.special.entr:
+ * table[j + H][c] = entr((c / n_donor) / s_j), s_j the double with the bit pattern of 1.0 plus j.
+ * `order`: the donors sorted by class; `bnd`: n_class + 1 boundaries of the classes in it; `log2`:
+ * np.log(2).  Out: the maximal entropy and counts3 = variants tied at it (by value), those of them
+ * with var_count >= np.median of the tied counts (all of them without var_count), variants whose
+ * normalising sum lies more than H ulp from 1.  If the last is not 0 the call fails with
+ * VRX_ERR_UNSUPPORTED: no entropy is ever evaluated approximately.  ms2 (may be NULL): milliseconds of
+ * the entropy kernel and of the kernels after it.
+ * vrx_barcode_pick: `idx[np.random.randint(len(idx))]` (:53) once the host has drawn r: the r-th
+ * survivor in ascending variant index, and its entropy (:57).
+ * vrx_barcode_entropies: the last round's per-variant entropies (n_var doubles); for the tests. */
+typedef struct vrx_barcode vrx_barcode;
+int vrx_barcode_create(int device, int64_t n_var, int64_t n_donor, int64_t n_cat /* 1 + largest value */,
+                       const uint8_t* GT, const double* var_count, vrx_barcode** out);
+void vrx_barcode_destroy(vrx_barcode* b);
+int vrx_barcode_round(vrx_barcode* b, const int32_t* order /* n_donor */, const int32_t* bnd /* n_class + 1 */,
+                      int32_t n_class, const double* table, int32_t half_width /* H */, double log2,
+                      double* max_out, int64_t* counts3, double* ms2);
+int vrx_barcode_pick(vrx_barcode* b, int64_t r, int64_t* index_out, double* entropy_out);
+int vrx_barcode_entropies(vrx_barcode* b, double* out /* n_var */);
+
 /* ---- timing (bench.py roofline leg) ---------------------------------------------------
  * When enabled, every launch of a pass kernel is bracketed by hipEvents on the model's
  * stream; totals are read back after a sync.  Kernel ids: */

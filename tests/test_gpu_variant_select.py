@@ -1,0 +1,158 @@
+"""Barcode selection on the GPU: the device pass (csrc/vrx_barcode.h) against the NumPy restatement and
+the real reference's fixture.  Everything is compared for EQUALITY -- entropies on their bit patterns --
+because variant_select decides by float equality: a last-bit difference changes the tie sets and with
+them the chosen variants."""
+import contextlib
+import io
+import os
+
+import numpy as np
+import pytest
+
+from tests import gold
+from tests import variant_select_np as V
+
+pytestmark = pytest.mark.gpu
+
+N_VARS = [1, 2, 63, 64, 65, 255, 257, 4097]
+DONORS = [1, 2, 7, 8, 9, 16, 17, 127, 128]
+CATEGORIES = [1, 2, 3, 10]
+CHOSEN = [0, 1, 3]
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    return gold.load("c1_barcode")
+
+
+def bits(a):
+    return np.asarray(a, dtype=np.float64).view(np.int64)
+
+
+@pytest.mark.parametrize("n_cat", CATEGORIES)
+@pytest.mark.parametrize("K", DONORS)
+def test_entropies_of_a_round_bit_for_bit(K, n_cat):
+    from vireo_amd.variant_select import BarcodeRounds
+    for n_var in N_VARS:
+        for n_chosen in CHOSEN:
+            rs = np.random.RandomState(100000 * n_cat + 1000 * K + 10 * (n_var % 97) + n_chosen)
+            GT = rs.randint(0, n_cat, (n_var, K))
+            picks = rs.randint(0, n_var, n_chosen)
+            dev = BarcodeRounds(GT)
+            rank = np.zeros(K, dtype=np.int64)
+            for i in picks:
+                rank = V.dense_rank(rank, GT[i])
+                dev.choose(GT[i])
+            assert np.array_equal(dev.rank, rank)
+            want, _ = V.entropies(GT, rank)
+            top, n_tied, n_kept = dev.round()
+            got = dev.entropies()
+            dev.close()
+            where = (K, n_cat, n_var, n_chosen)
+            assert np.array_equal(bits(got), bits(want)), (where, np.flatnonzero(bits(got) != bits(want))[:8])
+            assert top == np.max(want) and n_tied == n_kept == int(np.sum(want == np.max(want))), where
+
+
+@pytest.mark.parametrize("name", list(V.CASES))
+def test_selection_equals_the_reference(fixture, name):
+    from vireo_amd import variant_select
+    c = V.fixture_case(fixture, name)
+    GT, vc = V.case_input(name)
+    runs = []
+    for _ in range(2):
+        np.random.seed(12345)                       # (the call must seed for itself)
+        out = io.StringIO()
+        with contextlib.redirect_stdout(out):
+            rv = variant_select(GT, vc, rand_seed=0)
+        runs.append((rv, out.getvalue(), np.random.get_state()))
+    (final, barcodes, chosen), printed, state = runs[0]
+    assert [int(i) for i in chosen] == list(c["chosen"])
+    assert np.array_equal(bits(final), bits(c["final"]))
+    assert barcodes == list(c["barcodes"])
+    assert printed.splitlines() == list(c["lines"]) and (printed == "" or printed.endswith("\n"))
+    assert state[0] == "MT19937" and np.array_equal(state[1], c["rng_key"]) and state[2] == int(c["rng_pos"])
+    # the types of the reference: a list of numpy integers, a list of str, a numpy float (or the int 0)
+    assert isinstance(chosen, list) and all(isinstance(i, np.integer) for i in chosen)
+    assert isinstance(barcodes, list) and all(type(b) is str for b in barcodes)
+    assert isinstance(final, np.float64) if len(chosen) else (type(final) is int and final == 0)
+    (final2, barcodes2, chosen2), printed2, state2 = runs[1]
+    assert bits(final2) == bits(final) and barcodes2 == barcodes and chosen2 == chosen and printed2 == printed
+    assert np.array_equal(state2[1], state[1]) and state2[2] == state[2]
+
+
+@pytest.mark.parametrize("name", ["k10_s2_vc", "k17", "sparse", "cat10"])
+def test_rounds_equal_the_reference(fixture, name):
+    """every round's entropies and both tie counts, walking the reference's choices"""
+    from vireo_amd.variant_select import BarcodeRounds
+    c = V.fixture_case(fixture, name)
+    GT, vc = V.case_input(name)
+    dev = BarcodeRounds(GT, vc)
+    for k, ent in enumerate(c["ent"]):
+        top, n_tied, n_kept = dev.round()
+        assert np.array_equal(bits(dev.entropies()), bits(ent)), (name, k)
+        assert top == np.max(ent)
+        if k < len(c["chosen"]):
+            assert (n_tied, n_kept) == (int(c["tied"][k]), int(c["kept"][k])), (name, k)
+            tied = np.flatnonzero(ent == np.max(ent))
+            kept = tied[vc[tied] >= np.median(vc[tied])]
+            for r in sorted({0, len(kept) // 2, len(kept) - 1}):
+                idx, e = dev.pick(r)
+                assert idx == kept[r] and bits(e) == bits(ent[idx])
+            dev.choose(GT[c["chosen"][k]])
+    dev.close()
+
+
+@pytest.mark.parametrize("counts,n_kept", [
+    ([5.0, 1.0, 3.0], 2),                     # odd: the middle one, 3
+    ([5.0, 1.0, 3.0, 4.0], 2),                # even: (3 + 4) / 2 = 3.5
+    ([2.0, 1.0, 2.0, 3.0], 3),                # even, the two middle ones equal
+    ([7.0] * 6, 6), ([7.0] * 5, 5),           # all equal: every one is >= the median
+    ([1e308, 1e308, 1.0, 2.0], 2),            # (a + b) / 2 of 2 and 1e308
+    ([-3.0, -1.0, -2.0, 0.5, 0.25], 3),       # negative counts sort as numbers
+])
+def test_median_filter(counts, n_kept):
+    from vireo_amd.variant_select import BarcodeRounds
+    n = len(counts)
+    # n identical splitting variants (all tied) between variants that split nothing
+    GT = np.zeros((2 * n + 1, 4), dtype=np.int64)
+    GT[1::2] = [0, 1, 0, 1]
+    vc = np.full(2 * n + 1, 1e6)
+    vc[1::2] = counts
+    assert n_kept == int(np.sum(np.array(counts) >= np.median(counts)))
+    dev = BarcodeRounds(GT, vc)
+    top, tied, kept = dev.round()
+    assert (top, tied, kept) == (V.entropies(GT, np.zeros(4, dtype=np.int64))[0].max(), n, n_kept)
+    want = [2 * i + 1 for i in range(n) if counts[i] >= np.median(counts)]
+    assert [int(dev.pick(r)[0]) for r in range(kept)] == want
+    from vireo_amd import _lib
+    with pytest.raises(_lib.VrxError):
+        dev.pick(kept)
+    dev.close()
+
+
+def test_a_sum_outside_the_table_is_an_error_not_an_estimate():
+    from vireo_amd import _lib
+    from vireo_amd.variant_select import BarcodeRounds
+    GT, vc = V.case_input("k10_s2_vc")
+    _, j = V.entropies(GT, np.zeros(10, dtype=np.int64))
+    assert np.any(j != 0)                               # some normalising sum is not exactly 1
+    dev = BarcodeRounds(GT, vc)
+    with pytest.raises(_lib.VrxError, match="%d variants.*outside the entropy table" % int(np.sum(j != 0))):
+        dev.round(half_width=0)
+    with pytest.raises(_lib.VrxError, match="no finished round"):
+        dev.entropies()
+    top, _, _ = dev.round(half_width=int(np.abs(j).max()))     # the narrowest table that holds them all
+    assert top == np.max(V.entropies(GT, np.zeros(10, dtype=np.int64))[0])
+    dev.close()
+
+
+@pytest.mark.parametrize("run", list(V.BARCODE_RUNS))
+def test_GTbarcode_command(run, tmp_path):
+    from vireo_amd import GTbarcode
+    tsv = str(tmp_path / "GTbarcode.tsv")
+    out = io.StringIO()
+    with contextlib.redirect_stdout(out):
+        GTbarcode.main(["-i", V.BARCODE_VCF, "-o", tsv, "--noPlot"] + V.BARCODE_RUNS[run])
+    d = V.barcode_run_dir(run)
+    assert open(tsv, "rb").read() == open(os.path.join(d, "GTbarcode.tsv"), "rb").read()
+    assert out.getvalue().encode() == open(os.path.join(d, "stdout.txt"), "rb").read()

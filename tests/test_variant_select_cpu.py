@@ -1,0 +1,202 @@
+"""Barcode selection without a GPU: the NumPy restatement (tests/variant_select_np.py) against the real
+reference's fixture, bit for bit; its sum rule against np.sum; the entropy table against scipy; the
+argument limits that hold before any device call; the GTbarcode option table and filter; and the error a
+selection gives when there is no GPU."""
+import contextlib
+import io
+
+import numpy as np
+import pytest
+from scipy.special import entr
+
+from tests import gold
+from tests import variant_select_np as V
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    return gold.load("c1_barcode")
+
+
+def bits(a):
+    return np.asarray(a, dtype=np.float64).view(np.int64)
+
+
+@pytest.fixture(scope="module")
+def restated():
+    """every case once: name -> the restatement's record and the generator state after it"""
+    out = {}
+    for name in V.CASES:
+        GT, vc = V.case_input(name)
+        rec = V.select(GT, vc, rand_seed=0)
+        rec["state"] = np.random.get_state()
+        out[name] = rec
+    return out
+
+
+def test_fixture_was_made_with_these_libraries_rules(fixture):
+    assert str(fixture["numpy_version"]) and str(fixture["scipy_version"])
+    assert float(np.log(2)) == float(np.float64(0.6931471805599453))
+
+
+@pytest.mark.parametrize("name", list(V.CASES))
+def test_restatement_equals_the_reference(fixture, restated, name):
+    c, r = V.fixture_case(fixture, name), restated[name]
+    assert r["ent"].shape == c["ent"].shape
+    assert np.array_equal(bits(r["ent"]), bits(c["ent"]))                 # every round, every variant
+    assert r["tied"] == list(c["tied"]) and r["kept"] == list(c["kept"])
+    assert r["chosen"] == list(c["chosen"])
+    assert np.array_equal(bits(r["final"]), bits(c["final"]))
+    assert r["barcodes"] == list(c["barcodes"])
+    assert r["lines"] == list(c["lines"])
+    assert np.array_equal(r["state"][1], c["rng_key"]) and r["state"][2] == int(c["rng_pos"])
+
+
+def test_fixture_tells_an_order_blind_entropy_apart(fixture):
+    """at least three cases change a tie count or a choice when the class sizes are summed in sorted order"""
+    telling = []
+    for name in V.CASES:
+        GT, vc = V.case_input(name)
+        c = V.fixture_case(fixture, name)
+        blind = V.select(GT, vc, rand_seed=0, order_blind=True)
+        if (blind["tied"], blind["kept"], blind["chosen"]) != (list(c["tied"]), list(c["kept"]), list(c["chosen"])):
+            telling.append(name)
+    assert len(telling) >= 3 and set(telling) & set(V.ORDER_SENSITIVE), telling
+
+
+def test_special_cases_are_what_they_claim(fixture):
+    mono = V.fixture_case(fixture, "monomorphic")
+    assert len(mono["chosen"]) == 0 and mono["final"] == 0 and list(mono["barcodes"]) == ["#"] * 5
+    assert list(mono["lines"]) == ["Warning: variant_select can't distinguish all samples."]
+    twins = V.fixture_case(fixture, "twins")
+    assert twins["barcodes"][1] == twins["barcodes"][4] and len(set(twins["barcodes"])) == 5
+    assert twins["lines"][-1].startswith("Warning")
+    assert len(V.fixture_case(fixture, "sparse")["chosen"]) >= 6
+    assert len(V.fixture_case(fixture, "k1")["chosen"]) == 0
+
+
+def test_sum_rule_is_np_sum():
+    rs = np.random.RandomState(0)
+    for n in range(1, 129):
+        A = rs.rand(40, n)
+        A[:8] = rs.randint(1, 130, (8, n)) / 129.0
+        want = np.array([np.sum(np.ascontiguousarray(row)) for row in A])
+        assert np.array_equal(bits(V.np_sum_rule(A, n)), bits(want)), n
+    assert bits(V.np_sum_rule(np.array([[-0.0]]), 1)[0]) == bits(np.sum(np.array([-0.0])))      # +0.0
+
+
+def test_table_entries_are_scipy_entr():
+    from vireo_amd.variant_select import entr_table, HALF_WIDTH
+    assert HALF_WIDTH == 32
+    for K in (1, 2, 10, 127, 128):
+        T = entr_table(K, 32)
+        assert T.shape == (65, K + 1) and T.flags.c_contiguous
+        assert np.array_equal(bits(T), bits(V.entr_table(K, 32)))
+        for j in (-32, -1, 0, 1, 32):
+            s = (np.float64(1.0).view(np.int64) + j).view(np.float64)
+            for c in (0, 1, K // 2, K):
+                assert bits(T[j + 32, c]) == bits(entr((np.float64(c) / np.float64(K)) / s))
+    assert entr_table(10, 0).shape == (1, 11)
+
+
+def test_normalising_sums_stay_inside_the_table(restated):
+    for name, r in restated.items():
+        assert -32 <= r["j_lo"] <= r["j_hi"] <= 32, (name, r["j_lo"], r["j_hi"])
+    assert min(r["j_lo"] for r in restated.values()) < 0 < max(r["j_hi"] for r in restated.values())
+
+
+def test_host_barcode_entropy(fixture):
+    from vireo_amd import barcode_entropy
+    c = V.fixture_case(fixture, "k10_s2")
+    GT, _ = V.case_input("k10_s2")
+    for i in (0, 7, 150, 299):
+        e, codes = barcode_entropy(["#"] * 10, GT[i])
+        assert bits(e) == bits(c["ent"][0, i]) and codes == ["#%d" % g for g in GT[i]]
+    e, codes = barcode_entropy([3, 1, 3])
+    assert codes == ["3", "1", "3"] and bits(e) == bits(V.entropies(np.array([[0, 1, 0]]), np.zeros(3, int))[0][0])
+    out = io.StringIO()
+    with contextlib.redirect_stdout(out):
+        assert barcode_entropy([1, 2], [1]) == (None, None)
+    assert out.getvalue() == "Error: X and y have different length in barcode_entropy.\n"
+
+
+def test_argument_limits_hold_before_any_device_call(monkeypatch):
+    from vireo_amd import _lib, variant_select
+
+    def no_device(*a, **k):
+        raise AssertionError("the library was touched")
+    monkeypatch.setattr(_lib, "lib", no_device)
+    monkeypatch.setattr(_lib, "require_gpu", no_device)
+    GT = np.random.RandomState(0).randint(0, 3, (20, 4))
+    bad = [
+        dict(GT=GT + 0.5),                                  # not integer-valued
+        dict(GT=np.where(GT == 0, np.nan, GT)),
+        dict(GT=GT.astype(str)),
+        dict(GT=GT - 1),                                    # below 0
+        dict(GT=GT + 8),                                    # above 9
+        dict(GT=np.zeros((5, 129), int)),                   # more than 128 samples
+        dict(GT=np.zeros((0, 4), int)),                     # no variants
+        dict(GT=GT[0]),                                     # 1-D
+        dict(GT=GT, var_count=np.ones(19)),                 # wrong length
+        dict(GT=GT, var_count=np.ones((20, 1))),
+        dict(GT=GT, var_count=np.where(np.arange(20) == 3, np.nan, 1.0)),
+        dict(GT=GT, var_count=np.where(np.arange(20) == 3, np.inf, 1.0)),
+    ]
+    for kw in bad:
+        with pytest.raises(ValueError):
+            variant_select(**kw)
+    with pytest.raises(AssertionError, match="touched"):    # a valid call does go to the device
+        variant_select(GT, np.ones(20))
+
+
+def test_no_gpu_no_fallback():
+    from vireo_amd import _lib, variant_select
+    if _lib.device_count() > 0:
+        pytest.skip("a GPU is visible here")
+    GT, vc = V.case_input("k10_s2")
+    with pytest.raises(_lib.VrxError):
+        variant_select(GT, vc)
+
+
+def test_package_surface():
+    import vireo_amd
+    from vireo_amd import _lib
+    for name in ("variant_select", "barcode_entropy", "variant_ELBO_gain"):
+        assert hasattr(vireo_amd, name) and name in vireo_amd.__all__
+    for name in ("create", "destroy", "round", "pick", "entropies"):
+        assert "vrx_barcode_" + name in _lib.SIGNATURES
+
+
+def test_gtbarcode_options():
+    from vireo_amd import GTbarcode
+    p = GTbarcode.build_parser()
+    o, _ = p.parse_args([])
+    assert (o.vcf_file, o.out_file, o.geno_tag, o.no_homo_alt, o.no_plot, o.fig_size, o.fig_format, o.rand_seed) == (
+        None, None, "GT", False, False, "4,2", "png", None)
+    o, _ = p.parse_args(["-i", "a.vcf", "-o", "b.tsv", "-t", "PL", "--noHomoAlt", "--noPlot", "--figSize", "3,1",
+                         "--figFormat", "pdf", "--randSeed", "7"])
+    assert (o.vcf_file, o.out_file, o.geno_tag, o.no_homo_alt, o.no_plot, o.fig_size, o.fig_format, o.rand_seed) == (
+        "a.vcf", "b.tsv", "PL", True, True, "3,1", "pdf", 7)
+    o, _ = p.parse_args(["--vcfFile", "a", "--outFile", "b", "--genoTag", "GP"])
+    assert (o.vcf_file, o.out_file, o.geno_tag) == ("a", "b", "GP")
+    for argv, text in (([], "Welcome to GT barcode generator; Vireo v"), (["--noPlot"], "Error: need genotype data")):
+        out = io.StringIO()
+        with contextlib.redirect_stdout(out), pytest.raises(SystemExit) as e:
+            GTbarcode.main(argv)
+        assert e.value.code == 1 and out.getvalue().startswith(text)
+
+
+def test_gtbarcode_filter_mask():
+    from vireo_amd.GTbarcode import info_value, variant_mask
+    assert info_value("AD=3;DP=25;OTH=1", "DP=") == 25.0 and info_value("AD=3", "DP=") == 0
+    assert info_value("DP=30;XDP=7;DP=9", "DP=") == 30.0        # the first occurrence, up to ';'
+    assert info_value("DP=41", "DP=") == 41.0
+    INFO = ["AD=5;DP=21;OTH=1", "AD=5;DP=20;OTH=0", "AD=1;DP=100;OTH=5", "AD=1;DP=100;OTH=4", "AD=2;DP=50",
+            "DP=60;OTH=0"]
+    GT = np.array([[0, 1], [0, 1], [0, 1], [0, 2], [1, 1], [2, 0]])
+    keep, AD, DP, OTH = variant_mask(INFO, GT)
+    assert keep.tolist() == [True, False, False, True, True, True]        # 1/21 < 0.05, 20 is not > 20, 5 % is not < 5 %
+    assert DP.tolist() == [21, 20, 100, 100, 50, 60] and OTH.tolist() == [1, 0, 5, 4, 0, 0]
+    assert AD.tolist() == [5, 5, 1, 1, 2, 0]
+    keep, _, _, _ = variant_mask(INFO, GT, no_homo_alt=True)
+    assert keep.tolist() == [True, False, False, False, True, False]
