@@ -282,6 +282,28 @@ int vrx_bulk_fit(vrx_bulk* b, double* psi_io /* n_donor */, double* theta_io /* 
  * n_psi vectors at once (eight per pass over GT_prob). */
 int vrx_bulk_loglik(vrx_bulk* b, int64_t n_psi, const double* psi /* n_psi x n_donor */,
                     const double* theta /* n_gt */, double* out /* n_psi */);
+/* A cohort: n_sample bulk samples genotyped against the same donors, the loop over samples that
+ * users of VireoBulk write around :44-108 (one fit per sample on the same GT_prob).  AD / DP are
+ * n_sample x n_var doubles ("BD = DP - AD", :72, formed on the way in).  Replaces any earlier
+ * cohort; the handle's single-sample counts, vrx_bulk_fit and vrx_bulk_loglik are untouched by it.
+ * Fails with the LDS message where n_donor x n_gt is too large for a chunk's accumulators. */
+int vrx_bulk_set_cohort(vrx_bulk* b, int64_t n_sample, const double* AD /* n_sample x n_var */,
+                        const double* DP /* n_sample x n_var */);
+/* samples that share one read of a GT_prob tile (a compile-time constant) */
+int32_t vrx_bulk_cohort_chunk(void);
+/* The EM loop of VireoBulk.fit (vireo_bulk.py:75-105) for every sample of the cohort at once, each
+ * from its own row of psi_io / theta_io, which receive the fitted values.  The stop rule (:97-105)
+ * runs per sample on the device; a sample that has stopped is frozen while the others go on.
+ * logLik_trace row s holds that sample's logLik[0 .. last_it[s]] and zeros behind it.  A sample's
+ * results do not depend on the other samples of the cohort nor on its position among them. */
+int vrx_bulk_fit_cohort(vrx_bulk* b, double* psi_io /* n_sample x n_donor */, double* theta_io /* n_sample x n_gt */,
+                        int32_t max_iter, int32_t min_iter, double epsilon, int32_t learn_theta,
+                        int32_t delay_fit_theta, double* logLik_trace /* n_sample x max_iter */,
+                        int32_t* last_it /* n_sample */, double* ms_out);
+/* The log-likelihood of vireo_bulk.py:94-96 / :152-158 for n_psi vectors per sample, each sample under
+ * its own theta and counts (LikRatio_test for a whole cohort in one pass per eight vectors). */
+int vrx_bulk_loglik_cohort(vrx_bulk* b, int64_t n_psi, const double* psi /* n_sample x n_psi x n_donor */,
+                           const double* theta /* n_sample x n_gt */, double* out /* n_sample x n_psi */);
 
 /* ---- donor matching (vrx_match.h) -----------------------------------------------------------
  * The genotype distance between every donor of X and every donor of Z,

@@ -3529,14 +3529,27 @@ struct vrx_bulk {
     DevBuf<double> trace;   // logLik, max_iter of the largest fit so far
     DevBuf<double> psis, out;  // VRX_BULK_Q x K, VRX_BULK_Q
     DevBuf<int32_t> ctl;
+    // the cohort (vrx_bulk_set_cohort): n_sample count vectors on the same GT_prob
+    int64_t n_sample = 0;
+    int T_co = 0, n_wg_co = 0;        // the cohort fit pass; functions of (N, K, G) alone
+    int T_co_ll = 0, n_wg_co_ll = 0;  // the cohort log-likelihood pass
+    size_t lds_co = 0, lds_co_ll = 0, lds_max = 0;
+    DevBuf<double2> AB_co;     // [n_sample][N]
+    DevBuf<double> par_co;     // [n_sample][K + G]
+    DevBuf<double> part_co;    // [chunk][workgroup][slot][.] of either cohort pass
+    DevBuf<double> trace_co;   // [n_sample][max_iter]
+    DevBuf<double> psis_co, out_co;  // [n_sample][n_psi][K], [n_sample][n_psi]
+    DevBuf<int32_t> ctl_co;    // [n_sample][VRX_BULK_CTL_WORDS]
 };
 
 // variants per tile: even, <= 256 (a lane per variant), inside the LDS budget; at least 2
-static int bulk_tile(int64_t N, int K, int G, bool fit) {
+static int bulk_tile(int64_t N, int K, int G, bool fit, bool cohort = false) {
     const VrxBulkShape h0 = vrx_bulk_shape(K, G, 0);
-    const size_t fixed = (fit ? vrx_bulk_lds_doubles(h0) : vrx_bulk_ll_lds_doubles(h0)) * sizeof(double);
+    const size_t fixed = (cohort ? (fit ? vrx_bulk_cohort_lds_doubles(h0) : vrx_bulk_cohort_ll_lds_doubles(h0))
+                                 : (fit ? vrx_bulk_lds_doubles(h0) : vrx_bulk_ll_lds_doubles(h0))) *
+                         sizeof(double);
     const size_t per = (size_t)(fit ? h0.S + h0.SK + 2 : h0.S) * sizeof(double);
-    const size_t budget = VRX_BULK_LDS_TILE;
+    const size_t budget = cohort ? VRX_BULK_COHORT_LDS : VRX_BULK_LDS_TILE;
     int64_t T = budget > fixed ? (int64_t)((budget - fixed) / per) : 0;
     T = std::min<int64_t>(T, VRX_BULK_BLOCK);
     T = std::min<int64_t>(T, N + (N & 1));
@@ -3603,6 +3616,15 @@ extern "C" int vrx_bulk_create(int device, int64_t n_var, int64_t n_donor, int64
     };
     b->n_wg = grid(b->T, b->lds);
     b->n_wg_ll = grid(b->T_ll, b->lds_ll);
+    // the cohort passes: shapes now (of N, K, G alone), the LDS check when a cohort is set -- a donor
+    // count the single-sample passes take may be too large for VRX_BULK_COHORT sets of accumulators
+    b->lds_max = lds_max;
+    b->T_co = bulk_tile(n_var, b->K, b->G, true, true);
+    b->T_co_ll = bulk_tile(n_var, b->K, b->G, false, true);
+    b->lds_co = vrx_bulk_cohort_lds_doubles(vrx_bulk_shape(b->K, b->G, b->T_co)) * sizeof(double);
+    b->lds_co_ll = vrx_bulk_cohort_ll_lds_doubles(vrx_bulk_shape(b->K, b->G, b->T_co_ll)) * sizeof(double);
+    b->n_wg_co = grid(b->T_co, b->lds_co);
+    b->n_wg_co_ll = grid(b->T_co_ll, b->lds_co_ll);
     VRX_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
     VRX_HIP(hipEventCreate(&b->t0));
     VRX_HIP(hipEventCreate(&b->t1));
@@ -3698,6 +3720,137 @@ extern "C" int vrx_bulk_loglik(vrx_bulk* b, int64_t n_psi, const double* psi, co
         VRX_HIP(hipGetLastError());
         VRX_HIP(hipMemcpyAsync(out + q0, b->out.p, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, s));
     }
+    VRX_HIP(hipStreamSynchronize(s));
+    return VRX_OK;
+}
+
+extern "C" int32_t vrx_bulk_cohort_chunk(void) { return VRX_BULK_COHORT; }
+
+extern "C" int vrx_bulk_set_cohort(vrx_bulk* b, int64_t n_sample, const double* AD, const double* DP) {
+    VRX_REQUIRE(b && AD && DP, "vrx_bulk_set_cohort: null argument");
+    VRX_REQUIRE(n_sample >= 1 && n_sample <= (1 << 16), "vrx_bulk_set_cohort: 1 <= n_sample <= 65536");
+    VRX_REQUIRE(b->lds_co <= b->lds_max && b->lds_co_ll <= b->lds_max,
+                "vrx_bulk_set_cohort: n_donor x n_gt = %d x %d needs %zu bytes of LDS per workgroup for a chunk of "
+                "%d samples (limit %zu)",
+                b->K, b->G, std::max(b->lds_co, b->lds_co_ll), VRX_BULK_COHORT, b->lds_max);
+    VRX_HIP(hipSetDevice(b->device));
+    const size_t S = (size_t)n_sample, N = (size_t)b->N;
+    const size_t n_chunk = (S + VRX_BULK_COHORT - 1) / VRX_BULK_COHORT;
+    b->n_sample = 0;  // (no cohort while this one is half built)
+    {
+        std::vector<double2> ab(S * N);
+        for (size_t i = 0; i < S * N; ++i) ab[i] = make_double2(AD[i], DP[i] - AD[i]);
+        VRX_HIP(b->AB_co.upload(ab.data(), S * N, b->stream));
+        VRX_HIP(hipStreamSynchronize(b->stream));  // (ab dies here)
+    }
+    VRX_HIP(b->par_co.alloc(S * (size_t)(b->K + b->G)));
+    VRX_HIP(b->ctl_co.alloc(S * VRX_BULK_CTL_WORDS));
+    VRX_HIP(b->part_co.alloc(n_chunk * VRX_BULK_COHORT *
+                             std::max((size_t)b->n_wg_co * (b->K + 2 * b->G + 1), (size_t)b->n_wg_co_ll * VRX_BULK_Q)));
+    b->n_sample = n_sample;
+    return VRX_OK;
+}
+
+extern "C" int vrx_bulk_fit_cohort(vrx_bulk* b, double* psi_io, double* theta_io, int32_t max_iter, int32_t min_iter,
+                                   double epsilon, int32_t learn_theta, int32_t delay_fit_theta, double* logLik_trace,
+                                   int32_t* last_it, double* ms_out) {
+    VRX_REQUIRE(b && psi_io && theta_io && logLik_trace && last_it, "vrx_bulk_fit_cohort: null argument");
+    VRX_REQUIRE(b->n_sample >= 1, "vrx_bulk_fit_cohort: no cohort set (vrx_bulk_set_cohort)");
+    VRX_REQUIRE(max_iter >= 1, "vrx_bulk_fit_cohort: max_iter must be >= 1");
+    VRX_HIP(hipSetDevice(b->device));
+    hipStream_t s = b->stream;
+    const int K = b->K, G = b->G, S = (int)b->n_sample;
+    const int n_chunk = (S + VRX_BULK_COHORT - 1) / VRX_BULK_COHORT;
+    const size_t n_trace = (size_t)S * max_iter;
+    if (b->trace_co.n < n_trace) VRX_HIP(b->trace_co.alloc(n_trace));
+    std::vector<double> par((size_t)S * (K + G));
+    for (int i = 0; i < S; ++i) {
+        std::copy(psi_io + (size_t)i * K, psi_io + (size_t)(i + 1) * K, par.begin() + (size_t)i * (K + G));
+        std::copy(theta_io + (size_t)i * G, theta_io + (size_t)(i + 1) * G, par.begin() + (size_t)i * (K + G) + K);
+    }
+    VRX_HIP(hipMemcpyAsync(b->par_co.p, par.data(), par.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    VRX_HIP(hipMemsetAsync(b->ctl_co.p, 0, (size_t)S * VRX_BULK_CTL_WORDS * sizeof(int32_t), s));
+    VRX_HIP(hipMemsetAsync(b->trace_co.p, 0, n_trace * sizeof(double), s));
+    // The schedule of vrx_bulk_fit with a stop word per sample: a batch of passes, then the control
+    // words of every sample; the loop ends when all have stopped.  A stopped sample does no work in
+    // the passes behind its stop and its state is not written again.
+    const int batch = VRX_BULK_BATCH;
+    const int64_t n_pass = (int64_t)max_iter + 1;
+    int64_t next = 0;
+    std::vector<int32_t> hctl((size_t)S * VRX_BULK_CTL_WORDS, 0);
+    bool all = false;
+    const dim3 grid((unsigned)b->n_wg_co, (unsigned)n_chunk);
+    VRX_HIP(hipEventRecord(b->t0, s));
+    while (next < n_pass && !all) {
+        const int64_t first = std::max<int64_t>((int64_t)std::max(min_iter, 0) + 3, batch);
+        const int64_t upto = std::min(n_pass, next == 0 ? first : next + batch);
+        for (; next < upto; ++next) {
+            if (G == 3)
+                vrx_bulk_cohort_pass<3><<<grid, VRX_BULK_BLOCK, b->lds_co, s>>>(
+                    (int)b->N, K, G, b->T_co, S, b->P.p, b->AB_co.p, b->par_co.p, b->ctl_co.p, b->part_co.p);
+            else
+                vrx_bulk_cohort_pass<0><<<grid, VRX_BULK_BLOCK, b->lds_co, s>>>(
+                    (int)b->N, K, G, b->T_co, S, b->P.p, b->AB_co.p, b->par_co.p, b->ctl_co.p, b->part_co.p);
+            vrx_bulk_cohort_finish<<<S, 1024, (size_t)(K + 2 * G + 2) * sizeof(double), s>>>(
+                b->n_wg_co, K, G, b->part_co.p, b->par_co.p, b->trace_co.p, b->ctl_co.p, min_iter, max_iter, epsilon,
+                learn_theta, delay_fit_theta);
+        }
+        VRX_HIP(hipGetLastError());
+        VRX_HIP(hipEventRecord(b->t1, s));
+        VRX_HIP(hipMemcpyAsync(hctl.data(), b->ctl_co.p, hctl.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipStreamSynchronize(s));
+        all = true;
+        for (int i = 0; i < S; ++i) all = all && hctl[(size_t)i * VRX_BULK_CTL_WORDS + VRX_BULK_STOP];
+    }
+    VRX_REQUIRE(all, "vrx_bulk_fit_cohort: the loop ended without every sample's last iteration");
+    for (int i = 0; i < S; ++i) last_it[i] = hctl[(size_t)i * VRX_BULK_CTL_WORDS + VRX_BULK_IT];
+    // (the whole trace: entries behind a sample's last iteration are the zeros it started with)
+    VRX_HIP(hipMemcpyAsync(logLik_trace, b->trace_co.p, n_trace * sizeof(double), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(par.data(), b->par_co.p, par.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < S; ++i) {
+        const double* src = par.data() + (size_t)i * (K + G);
+        std::copy(src, src + K, psi_io + (size_t)i * K);
+        std::copy(src + K, src + K + G, theta_io + (size_t)i * G);
+    }
+    if (ms_out) {
+        float ms = 0.f;
+        VRX_HIP(hipEventElapsedTime(&ms, b->t0, b->t1));
+        *ms_out = ms;
+    }
+    return VRX_OK;
+}
+
+extern "C" int vrx_bulk_loglik_cohort(vrx_bulk* b, int64_t n_psi, const double* psi, const double* theta,
+                                      double* out) {
+    VRX_REQUIRE(b && psi && theta && out, "vrx_bulk_loglik_cohort: null argument");
+    VRX_REQUIRE(b->n_sample >= 1, "vrx_bulk_loglik_cohort: no cohort set (vrx_bulk_set_cohort)");
+    VRX_REQUIRE(n_psi >= 1 && n_psi <= (1 << 20), "vrx_bulk_loglik_cohort: 1 <= n_psi <= 2^20");
+    VRX_HIP(hipSetDevice(b->device));
+    hipStream_t s = b->stream;
+    const int K = b->K, G = b->G, S = (int)b->n_sample;
+    const int n_chunk = (S + VRX_BULK_COHORT - 1) / VRX_BULK_COHORT;
+    const size_t n_in = (size_t)S * n_psi * K, n_out = (size_t)S * n_psi;
+    if (b->psis_co.n < n_in) VRX_HIP(b->psis_co.alloc(n_in));
+    if (b->out_co.n < n_out) VRX_HIP(b->out_co.alloc(n_out));
+    VRX_HIP(hipMemcpyAsync(b->psis_co.p, psi, n_in * sizeof(double), hipMemcpyHostToDevice, s));
+    // (theta rides in par_co's first n_sample x G doubles: no fit is in flight on this stream)
+    VRX_HIP(hipMemcpyAsync(b->par_co.p, theta, (size_t)S * G * sizeof(double), hipMemcpyHostToDevice, s));
+    const dim3 grid((unsigned)b->n_wg_co_ll, (unsigned)n_chunk);
+    for (int64_t q0 = 0; q0 < n_psi; q0 += VRX_BULK_Q) {
+        const int nq = (int)std::min<int64_t>(VRX_BULK_Q, n_psi - q0);
+        if (G == 3)
+            vrx_bulk_cohort_ll<3><<<grid, VRX_BULK_BLOCK, b->lds_co_ll, s>>>((int)b->N, K, G, b->T_co_ll, S, (int)n_psi,
+                                                                             (int)q0, nq, b->P.p, b->AB_co.p,
+                                                                             b->psis_co.p, b->par_co.p, b->part_co.p);
+        else
+            vrx_bulk_cohort_ll<0><<<grid, VRX_BULK_BLOCK, b->lds_co_ll, s>>>((int)b->N, K, G, b->T_co_ll, S, (int)n_psi,
+                                                                             (int)q0, nq, b->P.p, b->AB_co.p,
+                                                                             b->psis_co.p, b->par_co.p, b->part_co.p);
+        vrx_bulk_cohort_ll_sum<<<S, 1024, 0, s>>>(b->n_wg_co_ll, (int)n_psi, (int)q0, nq, b->part_co.p, b->out_co.p);
+        VRX_HIP(hipGetLastError());
+    }
+    VRX_HIP(hipMemcpyAsync(out, b->out_co.p, n_out * sizeof(double), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
     return VRX_OK;
 }
