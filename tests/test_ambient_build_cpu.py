@@ -1,27 +1,15 @@
 """Build-time check of the ambient-RNA kernels (vrx_ambient.h; no GPU: hipcc cross-compiles gfx950):
 every one of them keeps its registers -- no VGPR / SGPR spill, no scratch."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vireo_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from tests.device_isa import compile_unit
 
 
 @pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    d = tmp_path_factory.mktemp("isa_ambient")
-    rep = str(d / "usage.txt")
-    with open(rep, "w") as err:
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                        "--cuda-device-only", "-S", "-o", str(d / "engine.s"), "vrx_engine.hip",
-                        "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, stderr=err, check=True)
-    return open(rep).read()
+def report():
+    return compile_unit("vrx_engine.hip")[1]
 
 
 def test_ambient_kernels_do_not_spill(report):

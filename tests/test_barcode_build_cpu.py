@@ -1,30 +1,19 @@
 """Build-time check of the barcode-selection kernels (vrx_barcode.h; no GPU: hipcc cross-compiles gfx950):
 every instance keeps its registers -- no VGPR / SGPR spill, no scratch (the class counters and the eight
 accumulators of the sum rule are arrays in the source and must stay registers)."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vireo_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from tests.device_isa import compile_unit
+
 KERNELS = ("vrx_barcode_entropy", "vrx_barcode_max", "vrx_barcode_max2", "vrx_barcode_flag", "vrx_barcode_gather",
            "vrx_barcode_median", "vrx_barcode_flag_ge")
 
 
 @pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    d = tmp_path_factory.mktemp("isa_barcode")
-    rep = str(d / "usage.txt")
-    with open(rep, "w") as err:
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                        "--cuda-device-only", "-S", "-o", str(d / "engine.s"), "vrx_engine.hip",
-                        "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, stderr=err, check=True)
-    return open(rep).read()
+def report():
+    return compile_unit("vrx_barcode.hip")[1]
 
 
 def test_barcode_kernels_do_not_spill(report):
@@ -45,10 +34,3 @@ def test_barcode_kernels_do_not_spill(report):
     assert len(found) == len(KERNELS) + 1
     for name, r in found.items():
         assert r == dict(vgpr_spill=0, sgpr_spill=0, scratch=0), (name, r)
-
-
-def test_headers_list_rebuilds_on_the_kernel_header():
-    import __graft_entry__ as g
-    assert "vrx_barcode.h" in g.HEADERS
-    assert os.path.exists(os.path.join(CSRC, "vrx_barcode.h"))
-    assert '#include "vrx_barcode.h"' in open(os.path.join(CSRC, "vrx_engine.hip")).read()

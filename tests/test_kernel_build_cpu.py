@@ -10,13 +10,14 @@
 """
 import os
 import re
-import subprocess
+import shutil
 
 import pytest
 
+from tests.device_isa import compile_unit
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vireo_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def _pf_from_header():
@@ -33,16 +34,8 @@ PF = _pf_from_header()      # 8 at 16 waves: (160 KiB - 32 KiB of rings) / (1024
 
 
 @pytest.fixture(scope="module")
-def isa(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    d = tmp_path_factory.mktemp("isa")
-    asm, rep = str(d / "engine.s"), str(d / "usage.txt")
-    with open(rep, "w") as err:
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                        "--cuda-device-only", "-S", "-o", asm, "vrx_engine.hip",
-                        "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, stderr=err, check=True)
-    return open(asm).read(), open(rep).read()
+def isa():
+    return compile_unit("vrx_engine.hip")
 
 
 def _instances(report):
@@ -148,3 +141,31 @@ def test_doublet_table_kernel_keeps_its_registers(isa):
     get = lambda key: int(re.search(key + r": (\d+)", block[0]).group(1))      # noqa: E731
     r = dict(vgpr_spill=get("VGPRs Spill"), sgpr_spill=get("SGPRs Spill"), scratch=get(r"ScratchSize \[bytes/lane\]"))
     assert r == dict(vgpr_spill=0, sgpr_spill=0, scratch=0), r
+
+
+def test_build_goes_stale_on_every_file_of_csrc(tmp_path, monkeypatch):
+    """build() recompiles when any source or header is newer than the library: _stale() lists csrc/, so a
+    new unit or header is covered without an entry anywhere; every unit the build names exists."""
+    import __graft_entry__ as g
+    for f in g.SOURCES:
+        assert os.path.isfile(os.path.join(CSRC, f)), f
+    csrc = tmp_path / "vireo_amd" / "csrc"
+    shutil.copytree(CSRC, csrc)
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
+    lib = tmp_path / "vireo_amd" / "libvireo_hip.so"
+    monkeypatch.setattr(g, "CSRC", str(csrc))
+    monkeypatch.setattr(g, "LIB", str(lib))
+    assert g._stale()                                  # no library yet
+    lib.write_bytes(b"")
+    files = sorted(csrc.iterdir()) + [tmp_path / "include" / "vireo_hip.h"]
+    assert {p.name for p in files} >= set(g.SOURCES) | {"vrx_common.h", "vrx_kernels.h", "vrx_bulk.h", "vireo_hip.h"}
+    old, mid, new = 1_000_000_000, 1_000_000_100, 1_000_000_200
+    for p in files:
+        os.utime(p, (old, old))
+    os.utime(lib, (mid, mid))
+    assert not g._stale()
+    for p in files:
+        os.utime(p, (new, new))
+        assert g._stale(), p.name
+        os.utime(p, (old, old))
+    assert not g._stale()

@@ -1,27 +1,15 @@
 """Build-time check of the donor-matching kernels (vrx_match.h; no GPU: hipcc cross-compiles gfx950):
 every instance keeps its registers -- no VGPR / SGPR spill, no scratch."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vireo_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+from tests.device_isa import compile_unit
 
 
 @pytest.fixture(scope="module")
-def report(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("no hipcc")
-    d = tmp_path_factory.mktemp("isa_match")
-    rep = str(d / "usage.txt")
-    with open(rep, "w") as err:
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                        "--cuda-device-only", "-S", "-o", str(d / "engine.s"), "vrx_engine.hip",
-                        "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, stderr=err, check=True)
-    return open(rep).read()
+def report():
+    return compile_unit("vrx_match.hip")[1]
 
 
 def test_geno_kernels_do_not_spill(report):
@@ -39,9 +27,3 @@ def test_geno_kernels_do_not_spill(report):
     assert len([n for n in found if "vrx_geno_passILi" in n]) == 2
     for name, r in found.items():
         assert r == dict(vgpr_spill=0, sgpr_spill=0, scratch=0), (name, r)
-
-
-def test_headers_list_rebuilds_on_the_kernel_header():
-    import __graft_entry__ as g
-    assert "vrx_match.h" in g.HEADERS
-    assert os.path.exists(os.path.join(CSRC, "vrx_match.h"))

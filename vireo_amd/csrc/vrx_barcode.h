@@ -1,7 +1,7 @@
 // Barcode selection (vrx_barcode_*): one greedy round of variant_select (vireoSNP/utils/variant_select.py:22-62)
 // -- the entropy of every variant's candidate barcodes (barcode_entropy, :5-19), the tie set of the
 // maximum, the median filter on var_count and the r-th survivor -- on the device.  Included by
-// vrx_engine.hip only.
+// vrx_barcode.hip only.
 //
 // The reference decides by float equality, so every variant's entropy is the reference's double, bit for
 // bit.  What that takes:

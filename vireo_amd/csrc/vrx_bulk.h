@@ -1,5 +1,5 @@
 // Bulk donor abundance (vrx_bulk_*): the device form of VireoBulk.fit and LikRatio_test
-// (vireoSNP/utils/vireo_bulk.py:44-108, :120-167).  Included by vrx_engine.hip only.
+// (vireoSNP/utils/vireo_bulk.py:44-108, :120-167).  Included by vrx_bulk.hip only.
 //
 //   vrx_bulk_pass     one streaming pass over GT_prob [n][k][g] with the current (psi, theta): per
 //                     workgroup the partial sums psi_raw[K] | theta_s1[G] | theta_s2[G] | logLik

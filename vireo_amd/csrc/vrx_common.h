@@ -14,6 +14,10 @@
 
 void vrx_set_error(const char* fmt, ...);
 
+// Makes `device` current for the calling thread after checking it against vrx_device_count: VRX_OK, or
+// VRX_ERR_HIP with "<who>: device <d> not available (<n> HIP devices visible)" set.  Not part of the C ABI.
+__attribute__((visibility("hidden"))) int vrx_use_device(const char* who, int device);
+
 #define VRX_HIP(expr)                                                                   \
     do {                                                                                \
         hipError_t e__ = (expr);                                                        \

@@ -16,9 +16,6 @@
 #include "vrx_kernels.h"
 #include "vrx_build.h"
 #include "vrx_ambient.h"
-#include "vrx_bulk.h"
-#include "vrx_match.h"
-#include "vrx_barcode.h"
 
 // (vrx_set_error / vrx_last_error: vrx_host.cpp, so that the host-only translation unit links on
 //  its own for the sanitizer build of tests/test_host_sanitizers_cpu.py)
@@ -32,6 +29,17 @@ extern "C" int vrx_device_count(int* n) {
         c = 0;
     }
     *n = c;
+    return VRX_OK;
+}
+
+int vrx_use_device(const char* who, int device) {
+    int ndev = 0;
+    vrx_device_count(&ndev);
+    if (device < 0 || device >= ndev) {
+        vrx_set_error("%s: device %d not available (%d HIP devices visible)", who, device, ndev);
+        return VRX_ERR_HIP;
+    }
+    VRX_HIP(hipSetDevice(device));
     return VRX_OK;
 }
 
@@ -1549,14 +1557,7 @@ static int problem_create2(int device, int64_t n_var, int64_t n_cell, int64_t nn
     BuildPlan plan;
     int rc = pick_forms(nnz, ad, dp, &plan.forms);
     if (rc) return rc;
-    int ndev = 0;
-    vrx_device_count(&ndev);
-    if (device < 0 || device >= ndev) {
-        vrx_set_error("vrx_problem_create: device %d not available (%d HIP devices visible)",
-                      device, ndev);
-        return VRX_ERR_HIP;
-    }
-    VRX_HIP(hipSetDevice(device));
+    if (int e = vrx_use_device("vrx_problem_create", device)) return e;
     std::unique_ptr<vrx_problem> p(new vrx_problem());
     p->device = device;
     p->n_var = n_var;
@@ -3509,672 +3510,5 @@ extern "C" int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double
             ms3[i] = t;
         }
     }
-    return VRX_OK;
-}
-
-// ---- bulk donor abundance (vrx_bulk.h) --------------------------------------------------------
-struct vrx_bulk {
-    int device = 0, n_cu = 0;
-    int64_t N = 0;
-    int K = 0, G = 0;
-    int T = 0, n_wg = 0;       // the fit pass: variants per tile, workgroups
-    int T_ll = 0, n_wg_ll = 0; // the log-likelihood pass
-    size_t lds = 0, lds_ll = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    DevBuf<double> P;
-    DevBuf<double2> AB;  // (AD, BD) per variant
-    DevBuf<double> par;     // psi[K] | theta[G]
-    DevBuf<double> part;    // per-workgroup partials of either pass
-    DevBuf<double> trace;   // logLik, max_iter of the largest fit so far
-    DevBuf<double> psis, out;  // VRX_BULK_Q x K, VRX_BULK_Q
-    DevBuf<int32_t> ctl;
-    // the cohort (vrx_bulk_set_cohort): n_sample count vectors on the same GT_prob
-    int64_t n_sample = 0;
-    int T_co = 0, n_wg_co = 0;        // the cohort fit pass; functions of (N, K, G) alone
-    int T_co_ll = 0, n_wg_co_ll = 0;  // the cohort log-likelihood pass
-    size_t lds_co = 0, lds_co_ll = 0, lds_max = 0;
-    DevBuf<double2> AB_co;     // [n_sample][N]
-    DevBuf<double> par_co;     // [n_sample][K + G]
-    DevBuf<double> part_co;    // [chunk][workgroup][slot][.] of either cohort pass
-    DevBuf<double> trace_co;   // [n_sample][max_iter]
-    DevBuf<double> psis_co, out_co;  // [n_sample][n_psi][K], [n_sample][n_psi]
-    DevBuf<int32_t> ctl_co;    // [n_sample][VRX_BULK_CTL_WORDS]
-};
-
-// variants per tile: even, <= 256 (a lane per variant), inside the LDS budget; at least 2
-static int bulk_tile(int64_t N, int K, int G, bool fit, bool cohort = false) {
-    const VrxBulkShape h0 = vrx_bulk_shape(K, G, 0);
-    const size_t fixed = (cohort ? (fit ? vrx_bulk_cohort_lds_doubles(h0) : vrx_bulk_cohort_ll_lds_doubles(h0))
-                                 : (fit ? vrx_bulk_lds_doubles(h0) : vrx_bulk_ll_lds_doubles(h0))) *
-                         sizeof(double);
-    const size_t per = (size_t)(fit ? h0.S + h0.SK + 2 : h0.S) * sizeof(double);
-    const size_t budget = cohort ? VRX_BULK_COHORT_LDS : VRX_BULK_LDS_TILE;
-    int64_t T = budget > fixed ? (int64_t)((budget - fixed) / per) : 0;
-    T = std::min<int64_t>(T, VRX_BULK_BLOCK);
-    T = std::min<int64_t>(T, N + (N & 1));
-    T &= ~(int64_t)1;
-    return (int)std::max<int64_t>(T, 2);
-}
-
-static int bulk_upload_counts(vrx_bulk* b, const double* AD, const double* DP) {
-    std::vector<double2> ab((size_t)b->N);
-    for (int64_t n = 0; n < b->N; ++n) ab[(size_t)n] = make_double2(AD[n], DP[n] - AD[n]);
-    VRX_HIP(b->AB.upload(ab.data(), (size_t)b->N, b->stream));
-    VRX_HIP(hipStreamSynchronize(b->stream));  // (ab dies at return)
-    return VRX_OK;
-}
-
-extern "C" void vrx_bulk_destroy(vrx_bulk* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    if (b->t0) (void)hipEventDestroy(b->t0);
-    if (b->t1) (void)hipEventDestroy(b->t1);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
-    delete b;
-}
-
-extern "C" int vrx_bulk_create(int device, int64_t n_var, int64_t n_donor, int64_t n_gt, const double* GT_prob,
-                               const double* AD, const double* DP, vrx_bulk** out) {
-    VRX_REQUIRE(GT_prob && AD && DP && out, "vrx_bulk_create: null argument");
-    VRX_REQUIRE(n_var >= 1 && n_var < ((int64_t)1 << 31) - 512 && n_donor >= 1 && n_gt >= 2,
-                "vrx_bulk_create: 1 <= n_var < 2^31 - 512, n_donor >= 1, n_gt >= 2");
-    VRX_REQUIRE(n_donor * n_gt <= (1 << 20), "vrx_bulk_create: n_donor x n_gt too large");
-    int ndev = 0;
-    vrx_device_count(&ndev);
-    if (device < 0 || device >= ndev) {
-        vrx_set_error("vrx_bulk_create: device %d not available (%d HIP devices visible)", device, ndev);
-        return VRX_ERR_HIP;
-    }
-    VRX_HIP(hipSetDevice(device));
-    struct Del {
-        void operator()(vrx_bulk* b) const { vrx_bulk_destroy(b); }
-    };
-    std::unique_ptr<vrx_bulk, Del> b(new vrx_bulk());
-    b->device = device;
-    b->N = n_var;
-    b->K = (int)n_donor;
-    b->G = (int)n_gt;
-    hipDeviceProp_t prop;
-    VRX_HIP(hipGetDeviceProperties(&prop, device));
-    b->n_cu = prop.multiProcessorCount;
-    // what a launch may ask for without the opt-in attribute (the device property may say more)
-    const size_t lds_max = std::min<size_t>(prop.sharedMemPerBlock, 64 * 1024);
-    b->T = bulk_tile(n_var, b->K, b->G, true);
-    b->T_ll = bulk_tile(n_var, b->K, b->G, false);
-    b->lds = vrx_bulk_lds_doubles(vrx_bulk_shape(b->K, b->G, b->T)) * sizeof(double);
-    b->lds_ll = vrx_bulk_ll_lds_doubles(vrx_bulk_shape(b->K, b->G, b->T_ll)) * sizeof(double);
-    VRX_REQUIRE(b->lds <= lds_max && b->lds_ll <= lds_max && (size_t)(b->K + 2 * b->G + 2) * sizeof(double) <= lds_max,
-                "vrx_bulk_create: n_donor x n_gt = %lld x %lld needs %zu bytes of LDS per workgroup (limit %zu)",
-                (long long)n_donor, (long long)n_gt, std::max(b->lds, b->lds_ll), lds_max);
-    // workgroups: as many as stay resident (LDS-bound, at most 4 per CU), each walking tiles grid-stride
-    auto grid = [&](int T, size_t lds) {
-        const int64_t n_tile = (n_var + T - 1) / T;
-        const int per_cu = (int)std::min<size_t>(4, std::max<size_t>(1, (size_t)(160 * 1024) / lds));
-        return (int)std::min<int64_t>(n_tile, (int64_t)b->n_cu * per_cu);
-    };
-    b->n_wg = grid(b->T, b->lds);
-    b->n_wg_ll = grid(b->T_ll, b->lds_ll);
-    // the cohort passes: shapes now (of N, K, G alone), the LDS check when a cohort is set -- a donor
-    // count the single-sample passes take may be too large for VRX_BULK_COHORT sets of accumulators
-    b->lds_max = lds_max;
-    b->T_co = bulk_tile(n_var, b->K, b->G, true, true);
-    b->T_co_ll = bulk_tile(n_var, b->K, b->G, false, true);
-    b->lds_co = vrx_bulk_cohort_lds_doubles(vrx_bulk_shape(b->K, b->G, b->T_co)) * sizeof(double);
-    b->lds_co_ll = vrx_bulk_cohort_ll_lds_doubles(vrx_bulk_shape(b->K, b->G, b->T_co_ll)) * sizeof(double);
-    b->n_wg_co = grid(b->T_co, b->lds_co);
-    b->n_wg_co_ll = grid(b->T_co_ll, b->lds_co_ll);
-    VRX_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    VRX_HIP(hipEventCreate(&b->t0));
-    VRX_HIP(hipEventCreate(&b->t1));
-    VRX_HIP(b->P.upload(GT_prob, (size_t)(n_var * n_donor * n_gt), b->stream));
-    int rc = bulk_upload_counts(b.get(), AD, DP);
-    if (rc) return rc;
-    VRX_HIP(b->par.alloc((size_t)(b->K + b->G)));
-    VRX_HIP(b->part.alloc(std::max((size_t)b->n_wg * (b->K + 2 * b->G + 1), (size_t)b->n_wg_ll * VRX_BULK_Q)));
-    VRX_HIP(b->psis.alloc((size_t)VRX_BULK_Q * b->K));
-    VRX_HIP(b->out.alloc(VRX_BULK_Q));
-    VRX_HIP(b->ctl.alloc(VRX_BULK_CTL_WORDS));
-    *out = b.release();
-    return VRX_OK;
-}
-
-extern "C" int vrx_bulk_set_counts(vrx_bulk* b, const double* AD, const double* DP) {
-    VRX_REQUIRE(b && AD && DP, "vrx_bulk_set_counts: null argument");
-    VRX_HIP(hipSetDevice(b->device));
-    return bulk_upload_counts(b, AD, DP);
-}
-
-extern "C" int vrx_bulk_fit(vrx_bulk* b, double* psi_io, double* theta_io, int32_t max_iter, int32_t min_iter,
-                            double epsilon, int32_t learn_theta, int32_t delay_fit_theta, double* logLik_trace,
-                            int32_t* last_it, double* ms_out) {
-    VRX_REQUIRE(b && psi_io && theta_io && logLik_trace && last_it, "vrx_bulk_fit: null argument");
-    VRX_REQUIRE(max_iter >= 1, "vrx_bulk_fit: max_iter must be >= 1");
-    VRX_HIP(hipSetDevice(b->device));
-    hipStream_t s = b->stream;
-    const int K = b->K, G = b->G, W = K + 2 * G + 1;
-    if (b->trace.n < (size_t)max_iter) VRX_HIP(b->trace.alloc((size_t)max_iter));
-    VRX_HIP(hipMemcpyAsync(b->par.p, psi_io, (size_t)K * sizeof(double), hipMemcpyHostToDevice, s));
-    VRX_HIP(hipMemcpyAsync(b->par.p + K, theta_io, (size_t)G * sizeof(double), hipMemcpyHostToDevice, s));
-    VRX_HIP(hipMemsetAsync(b->ctl.p, 0, VRX_BULK_CTL_WORDS * sizeof(int32_t), s));
-    // As in vrx_model_fit: the stop rule runs on the device (vrx_bulk_finish); the host enqueues a
-    // batch of passes, then reads the control words.  The first batch reaches the first pass the
-    // rule can fire after; a kernel launched behind the stop returns at once.
-    const int batch = VRX_BULK_BATCH;
-    const int64_t n_pass = (int64_t)max_iter + 1;  // pass p closes iteration p - 1
-    int64_t next = 0;
-    int32_t hctl[VRX_BULK_CTL_WORDS] = {};
-    VRX_HIP(hipEventRecord(b->t0, s));
-    while (next < n_pass && !hctl[VRX_BULK_STOP]) {
-        const int64_t first = std::max<int64_t>((int64_t)std::max(min_iter, 0) + 3, batch);
-        const int64_t upto = std::min(n_pass, next == 0 ? first : next + batch);
-        for (; next < upto; ++next) {
-            if (G == 3)
-                vrx_bulk_pass<3><<<b->n_wg, VRX_BULK_BLOCK, b->lds, s>>>((int)b->N, K, G, b->T, b->P.p, b->AB.p,
-                                                                         b->par.p, b->ctl.p, b->part.p);
-            else
-                vrx_bulk_pass<0><<<b->n_wg, VRX_BULK_BLOCK, b->lds, s>>>((int)b->N, K, G, b->T, b->P.p, b->AB.p,
-                                                                         b->par.p, b->ctl.p, b->part.p);
-            vrx_bulk_finish<<<1, 1024, (size_t)(W + 1) * sizeof(double), s>>>(
-                b->n_wg, K, G, b->part.p, b->par.p, b->trace.p, b->ctl.p, min_iter, max_iter, epsilon, learn_theta,
-                delay_fit_theta);
-        }
-        VRX_HIP(hipGetLastError());
-        VRX_HIP(hipEventRecord(b->t1, s));
-        VRX_HIP(hipMemcpyAsync(hctl, b->ctl.p, sizeof hctl, hipMemcpyDeviceToHost, s));
-        VRX_HIP(hipStreamSynchronize(s));
-    }
-    VRX_REQUIRE(hctl[VRX_BULK_STOP], "vrx_bulk_fit: the loop ended without its last iteration");
-    const int it = hctl[VRX_BULK_IT];
-    *last_it = it;
-    VRX_HIP(hipMemcpyAsync(logLik_trace, b->trace.p, (size_t)(it + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipMemcpyAsync(psi_io, b->par.p, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipMemcpyAsync(theta_io, b->par.p + K, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipStreamSynchronize(s));
-    if (ms_out) {
-        float ms = 0.f;
-        VRX_HIP(hipEventElapsedTime(&ms, b->t0, b->t1));
-        *ms_out = ms;
-    }
-    return VRX_OK;
-}
-
-extern "C" int vrx_bulk_loglik(vrx_bulk* b, int64_t n_psi, const double* psi, const double* theta, double* out) {
-    VRX_REQUIRE(b && psi && theta && out, "vrx_bulk_loglik: null argument");
-    VRX_REQUIRE(n_psi >= 1, "vrx_bulk_loglik: n_psi must be >= 1");
-    VRX_HIP(hipSetDevice(b->device));
-    hipStream_t s = b->stream;
-    const int K = b->K, G = b->G;
-    VRX_HIP(hipMemcpyAsync(b->par.p + K, theta, (size_t)G * sizeof(double), hipMemcpyHostToDevice, s));
-    for (int64_t q0 = 0; q0 < n_psi; q0 += VRX_BULK_Q) {
-        const int nq = (int)std::min<int64_t>(VRX_BULK_Q, n_psi - q0);
-        VRX_HIP(hipMemcpyAsync(b->psis.p, psi + q0 * K, (size_t)nq * K * sizeof(double), hipMemcpyHostToDevice, s));
-        if (G == 3)
-            vrx_bulk_ll<3><<<b->n_wg_ll, VRX_BULK_BLOCK, b->lds_ll, s>>>((int)b->N, K, G, b->T_ll, nq, b->P.p, b->AB.p,
-                                                                         b->psis.p, b->par.p + K, b->part.p);
-        else
-            vrx_bulk_ll<0><<<b->n_wg_ll, VRX_BULK_BLOCK, b->lds_ll, s>>>((int)b->N, K, G, b->T_ll, nq, b->P.p, b->AB.p,
-                                                                         b->psis.p, b->par.p + K, b->part.p);
-        vrx_bulk_ll_sum<<<1, 1024, 0, s>>>(b->n_wg_ll, nq, b->part.p, b->out.p);
-        VRX_HIP(hipGetLastError());
-        VRX_HIP(hipMemcpyAsync(out + q0, b->out.p, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    VRX_HIP(hipStreamSynchronize(s));
-    return VRX_OK;
-}
-
-extern "C" int32_t vrx_bulk_cohort_chunk(void) { return VRX_BULK_COHORT; }
-
-extern "C" int vrx_bulk_set_cohort(vrx_bulk* b, int64_t n_sample, const double* AD, const double* DP) {
-    VRX_REQUIRE(b && AD && DP, "vrx_bulk_set_cohort: null argument");
-    VRX_REQUIRE(n_sample >= 1 && n_sample <= (1 << 16), "vrx_bulk_set_cohort: 1 <= n_sample <= 65536");
-    VRX_REQUIRE(b->lds_co <= b->lds_max && b->lds_co_ll <= b->lds_max,
-                "vrx_bulk_set_cohort: n_donor x n_gt = %d x %d needs %zu bytes of LDS per workgroup for a chunk of "
-                "%d samples (limit %zu)",
-                b->K, b->G, std::max(b->lds_co, b->lds_co_ll), VRX_BULK_COHORT, b->lds_max);
-    VRX_HIP(hipSetDevice(b->device));
-    const size_t S = (size_t)n_sample, N = (size_t)b->N;
-    const size_t n_chunk = (S + VRX_BULK_COHORT - 1) / VRX_BULK_COHORT;
-    b->n_sample = 0;  // (no cohort while this one is half built)
-    {
-        std::vector<double2> ab(S * N);
-        for (size_t i = 0; i < S * N; ++i) ab[i] = make_double2(AD[i], DP[i] - AD[i]);
-        VRX_HIP(b->AB_co.upload(ab.data(), S * N, b->stream));
-        VRX_HIP(hipStreamSynchronize(b->stream));  // (ab dies here)
-    }
-    VRX_HIP(b->par_co.alloc(S * (size_t)(b->K + b->G)));
-    VRX_HIP(b->ctl_co.alloc(S * VRX_BULK_CTL_WORDS));
-    VRX_HIP(b->part_co.alloc(n_chunk * VRX_BULK_COHORT *
-                             std::max((size_t)b->n_wg_co * (b->K + 2 * b->G + 1), (size_t)b->n_wg_co_ll * VRX_BULK_Q)));
-    b->n_sample = n_sample;
-    return VRX_OK;
-}
-
-extern "C" int vrx_bulk_fit_cohort(vrx_bulk* b, double* psi_io, double* theta_io, int32_t max_iter, int32_t min_iter,
-                                   double epsilon, int32_t learn_theta, int32_t delay_fit_theta, double* logLik_trace,
-                                   int32_t* last_it, double* ms_out) {
-    VRX_REQUIRE(b && psi_io && theta_io && logLik_trace && last_it, "vrx_bulk_fit_cohort: null argument");
-    VRX_REQUIRE(b->n_sample >= 1, "vrx_bulk_fit_cohort: no cohort set (vrx_bulk_set_cohort)");
-    VRX_REQUIRE(max_iter >= 1, "vrx_bulk_fit_cohort: max_iter must be >= 1");
-    VRX_HIP(hipSetDevice(b->device));
-    hipStream_t s = b->stream;
-    const int K = b->K, G = b->G, S = (int)b->n_sample;
-    const int n_chunk = (S + VRX_BULK_COHORT - 1) / VRX_BULK_COHORT;
-    const size_t n_trace = (size_t)S * max_iter;
-    if (b->trace_co.n < n_trace) VRX_HIP(b->trace_co.alloc(n_trace));
-    std::vector<double> par((size_t)S * (K + G));
-    for (int i = 0; i < S; ++i) {
-        std::copy(psi_io + (size_t)i * K, psi_io + (size_t)(i + 1) * K, par.begin() + (size_t)i * (K + G));
-        std::copy(theta_io + (size_t)i * G, theta_io + (size_t)(i + 1) * G, par.begin() + (size_t)i * (K + G) + K);
-    }
-    VRX_HIP(hipMemcpyAsync(b->par_co.p, par.data(), par.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    VRX_HIP(hipMemsetAsync(b->ctl_co.p, 0, (size_t)S * VRX_BULK_CTL_WORDS * sizeof(int32_t), s));
-    VRX_HIP(hipMemsetAsync(b->trace_co.p, 0, n_trace * sizeof(double), s));
-    // The schedule of vrx_bulk_fit with a stop word per sample: a batch of passes, then the control
-    // words of every sample; the loop ends when all have stopped.  A stopped sample does no work in
-    // the passes behind its stop and its state is not written again.
-    const int batch = VRX_BULK_BATCH;
-    const int64_t n_pass = (int64_t)max_iter + 1;
-    int64_t next = 0;
-    std::vector<int32_t> hctl((size_t)S * VRX_BULK_CTL_WORDS, 0);
-    bool all = false;
-    const dim3 grid((unsigned)b->n_wg_co, (unsigned)n_chunk);
-    VRX_HIP(hipEventRecord(b->t0, s));
-    while (next < n_pass && !all) {
-        const int64_t first = std::max<int64_t>((int64_t)std::max(min_iter, 0) + 3, batch);
-        const int64_t upto = std::min(n_pass, next == 0 ? first : next + batch);
-        for (; next < upto; ++next) {
-            if (G == 3)
-                vrx_bulk_cohort_pass<3><<<grid, VRX_BULK_BLOCK, b->lds_co, s>>>(
-                    (int)b->N, K, G, b->T_co, S, b->P.p, b->AB_co.p, b->par_co.p, b->ctl_co.p, b->part_co.p);
-            else
-                vrx_bulk_cohort_pass<0><<<grid, VRX_BULK_BLOCK, b->lds_co, s>>>(
-                    (int)b->N, K, G, b->T_co, S, b->P.p, b->AB_co.p, b->par_co.p, b->ctl_co.p, b->part_co.p);
-            vrx_bulk_cohort_finish<<<S, 1024, (size_t)(K + 2 * G + 2) * sizeof(double), s>>>(
-                b->n_wg_co, K, G, b->part_co.p, b->par_co.p, b->trace_co.p, b->ctl_co.p, min_iter, max_iter, epsilon,
-                learn_theta, delay_fit_theta);
-        }
-        VRX_HIP(hipGetLastError());
-        VRX_HIP(hipEventRecord(b->t1, s));
-        VRX_HIP(hipMemcpyAsync(hctl.data(), b->ctl_co.p, hctl.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        VRX_HIP(hipStreamSynchronize(s));
-        all = true;
-        for (int i = 0; i < S; ++i) all = all && hctl[(size_t)i * VRX_BULK_CTL_WORDS + VRX_BULK_STOP];
-    }
-    VRX_REQUIRE(all, "vrx_bulk_fit_cohort: the loop ended without every sample's last iteration");
-    for (int i = 0; i < S; ++i) last_it[i] = hctl[(size_t)i * VRX_BULK_CTL_WORDS + VRX_BULK_IT];
-    // (the whole trace: entries behind a sample's last iteration are the zeros it started with)
-    VRX_HIP(hipMemcpyAsync(logLik_trace, b->trace_co.p, n_trace * sizeof(double), hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipMemcpyAsync(par.data(), b->par_co.p, par.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < S; ++i) {
-        const double* src = par.data() + (size_t)i * (K + G);
-        std::copy(src, src + K, psi_io + (size_t)i * K);
-        std::copy(src + K, src + K + G, theta_io + (size_t)i * G);
-    }
-    if (ms_out) {
-        float ms = 0.f;
-        VRX_HIP(hipEventElapsedTime(&ms, b->t0, b->t1));
-        *ms_out = ms;
-    }
-    return VRX_OK;
-}
-
-extern "C" int vrx_bulk_loglik_cohort(vrx_bulk* b, int64_t n_psi, const double* psi, const double* theta,
-                                      double* out) {
-    VRX_REQUIRE(b && psi && theta && out, "vrx_bulk_loglik_cohort: null argument");
-    VRX_REQUIRE(b->n_sample >= 1, "vrx_bulk_loglik_cohort: no cohort set (vrx_bulk_set_cohort)");
-    VRX_REQUIRE(n_psi >= 1 && n_psi <= (1 << 20), "vrx_bulk_loglik_cohort: 1 <= n_psi <= 2^20");
-    VRX_HIP(hipSetDevice(b->device));
-    hipStream_t s = b->stream;
-    const int K = b->K, G = b->G, S = (int)b->n_sample;
-    const int n_chunk = (S + VRX_BULK_COHORT - 1) / VRX_BULK_COHORT;
-    const size_t n_in = (size_t)S * n_psi * K, n_out = (size_t)S * n_psi;
-    if (b->psis_co.n < n_in) VRX_HIP(b->psis_co.alloc(n_in));
-    if (b->out_co.n < n_out) VRX_HIP(b->out_co.alloc(n_out));
-    VRX_HIP(hipMemcpyAsync(b->psis_co.p, psi, n_in * sizeof(double), hipMemcpyHostToDevice, s));
-    // (theta rides in par_co's first n_sample x G doubles: no fit is in flight on this stream)
-    VRX_HIP(hipMemcpyAsync(b->par_co.p, theta, (size_t)S * G * sizeof(double), hipMemcpyHostToDevice, s));
-    const dim3 grid((unsigned)b->n_wg_co_ll, (unsigned)n_chunk);
-    for (int64_t q0 = 0; q0 < n_psi; q0 += VRX_BULK_Q) {
-        const int nq = (int)std::min<int64_t>(VRX_BULK_Q, n_psi - q0);
-        if (G == 3)
-            vrx_bulk_cohort_ll<3><<<grid, VRX_BULK_BLOCK, b->lds_co_ll, s>>>((int)b->N, K, G, b->T_co_ll, S, (int)n_psi,
-                                                                             (int)q0, nq, b->P.p, b->AB_co.p,
-                                                                             b->psis_co.p, b->par_co.p, b->part_co.p);
-        else
-            vrx_bulk_cohort_ll<0><<<grid, VRX_BULK_BLOCK, b->lds_co_ll, s>>>((int)b->N, K, G, b->T_co_ll, S, (int)n_psi,
-                                                                             (int)q0, nq, b->P.p, b->AB_co.p,
-                                                                             b->psis_co.p, b->par_co.p, b->part_co.p);
-        vrx_bulk_cohort_ll_sum<<<S, 1024, 0, s>>>(b->n_wg_co_ll, (int)n_psi, (int)q0, nq, b->part_co.p, b->out_co.p);
-        VRX_HIP(hipGetLastError());
-    }
-    VRX_HIP(hipMemcpyAsync(out, b->out_co.p, n_out * sizeof(double), hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipStreamSynchronize(s));
-    return VRX_OK;
-}
-
-// ---- donor matching (vrx_match.h) -------------------------------------------------------------
-// the stream and the two events of one vrx_geno_dist call (released on every return path)
-struct GenoCall {
-    hipStream_t stream = nullptr;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    ~GenoCall() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (t0) (void)hipEventDestroy(t0);
-        if (t1) (void)hipEventDestroy(t1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
-extern "C" int vrx_geno_dist(int device, int64_t n_var, int64_t k1, int64_t k2, int64_t n_gt, const double* X,
-                             const double* Z, int64_t block_vars, double* D, double* ms_out) {
-    VRX_REQUIRE(X && D, "vrx_geno_dist: null argument");
-    if (!Z) VRX_REQUIRE(k2 == k1, "vrx_geno_dist: Z = NULL compares X with itself, k2 must equal k1");
-    VRX_REQUIRE(n_var >= 1 && k1 >= 1 && k2 >= 1 && n_gt >= 1 && block_vars >= 0,
-                "vrx_geno_dist: n_var >= 1, k1 >= 1, k2 >= 1, n_gt >= 1, block_vars >= 0");
-    const int64_t kmax = std::max(k1, k2);
-    if (n_gt > (1 << 20) || kmax > (1 << 20) || kmax * n_gt >= ((int64_t)1 << 28)) {
-        vrx_set_error("vrx_geno_dist: %lld x %lld donors x %lld genotypes: a variant's row is too long",
-                      (long long)k1, (long long)k2, (long long)n_gt);
-        return VRX_ERR_UNSUPPORTED;
-    }
-    const int G = (int)n_gt;
-    const VrxGenoShape h = vrx_geno_shape(k1, k2, G);
-    const size_t lds = vrx_geno_lds_doubles(h) * sizeof(double);
-    const int64_t n_ij = ((k1 + h.TI - 1) / h.TI) * ((k2 + h.TJ - 1) / h.TJ);
-    if (h.T < 1 || lds > (size_t)VRX_GENO_LDS || n_ij > 65535) {
-        vrx_set_error("vrx_geno_dist: %lld x %lld donors x %lld genotypes unsupported (one variant of a tile must "
-                      "fit %d bytes of LDS, at most 65535 output tiles)",
-                      (long long)k1, (long long)k2, (long long)n_gt, VRX_GENO_LDS);
-        return VRX_ERR_UNSUPPORTED;
-    }
-    int ndev = 0;
-    vrx_device_count(&ndev);
-    if (device < 0 || device >= ndev) {
-        vrx_set_error("vrx_geno_dist: device %d not available (%d HIP devices visible)", device, ndev);
-        return VRX_ERR_HIP;
-    }
-    VRX_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    VRX_HIP(hipGetDeviceProperties(&prop, device));
-    // variants per slab: each operand's slab at most 256 MiB by default, and below 2^31 - 1 variants
-    const int64_t row_bytes = kmax * n_gt * (int64_t)sizeof(double);
-    int64_t bv = block_vars > 0 ? block_vars : std::max<int64_t>(1, ((int64_t)256 << 20) / row_bytes);
-    bv = std::min(std::min(bv, n_var), (int64_t)0x7fffffff - VRX_GENO_MAX_T);
-    // workgroups of a slab: the output tiles times as many chunks of variant tiles as stay resident
-    const int64_t n_vt = (bv + h.T - 1) / h.T;
-    const int64_t resident = (int64_t)prop.multiProcessorCount * 4;
-    // (at least 4 variant tiles per chunk where the slab has them: fewer partials to add)
-    const int n_chunk = (int)std::max<int64_t>(1, std::min<int64_t>((n_vt + 3) / 4, resident / n_ij));
-    const int64_t n_cell = k1 * k2;
-    GenoCall c;
-    VRX_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-    VRX_HIP(hipEventCreate(&c.t0));
-    VRX_HIP(hipEventCreate(&c.t1));
-    DevBuf<double> dX, dZ, part, acc;
-    VRX_HIP(dX.alloc((size_t)(bv * k1 * n_gt)));
-    if (Z) VRX_HIP(dZ.alloc((size_t)(bv * k2 * n_gt)));
-    VRX_HIP(part.alloc((size_t)n_chunk * (size_t)n_cell));
-    VRX_HIP(acc.alloc((size_t)n_cell));
-    const double* pZ = Z ? dZ.p : dX.p;
-    hipStream_t s = c.stream;
-    double ms = 0.0;
-    for (int64_t n0 = 0; n0 < n_var; n0 += bv) {
-        const int64_t nv = std::min(bv, n_var - n0);
-        const bool last = n0 + nv == n_var;
-        VRX_HIP(hipMemcpyAsync(dX.p, X + n0 * k1 * n_gt, (size_t)(nv * k1 * n_gt) * sizeof(double),
-                               hipMemcpyHostToDevice, s));
-        if (Z)
-            VRX_HIP(hipMemcpyAsync(dZ.p, Z + n0 * k2 * n_gt, (size_t)(nv * k2 * n_gt) * sizeof(double),
-                                   hipMemcpyHostToDevice, s));
-        // (a short last slab keeps the grid: a chunk without variant tiles writes zeros)
-        const dim3 grid((unsigned)n_chunk, (unsigned)n_ij);
-        VRX_HIP(hipEventRecord(c.t0, s));
-        if (G == 3)
-            vrx_geno_pass<3><<<grid, VRX_GENO_BLOCK, lds, s>>>((int)nv, (int)k1, (int)k2, h, dX.p, pZ, part.p);
-        else
-            vrx_geno_pass<0><<<grid, VRX_GENO_BLOCK, lds, s>>>((int)nv, (int)k1, (int)k2, h, dX.p, pZ, part.p);
-        vrx_geno_sum<<<(unsigned)((n_cell + 63) / 64), 64 * VRX_GENO_SUM_RUNS, 0, s>>>(
-            n_chunk, n_cell, part.p, acc.p, n0 == 0, last ? (double)n_var * (double)n_gt : 0.0);
-        VRX_HIP(hipGetLastError());
-        VRX_HIP(hipEventRecord(c.t1, s));
-        VRX_HIP(hipStreamSynchronize(s));  // (the next upload overwrites the slab)
-        float t = 0.f;
-        VRX_HIP(hipEventElapsedTime(&t, c.t0, c.t1));
-        ms += t;
-    }
-    VRX_HIP(hipMemcpyAsync(D, acc.p, (size_t)n_cell * sizeof(double), hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipStreamSynchronize(s));
-    if (ms_out) *ms_out = ms;
-    return VRX_OK;
-}
-
-// ---- barcode selection (vrx_barcode.h) ----------------------------------------------------------
-struct vrx_barcode {
-    int device = 0;
-    int64_t N = 0;      // variants
-    size_t stride = 0;  // bytes between the donors' rows of GT
-    int K = 0, NC = 0;
-    bool has_vc = false, have_round = false;
-    int64_t n_kept = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    DevBuf<uint8_t> GT, flag, flag2, tmp;
-    DevBuf<double> vc, ent, keys, sorted, table, part, scal;
-    DevBuf<int32_t> state, tidx, kidx, ctl;  // state: order [K] | bnd [K + 1]
-    size_t tmp_bytes = 0;
-};
-
-extern "C" void vrx_barcode_destroy(vrx_barcode* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    for (hipEvent_t e : b->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
-    delete b;
-}
-
-extern "C" int vrx_barcode_create(int device, int64_t n_var, int64_t n_donor, int64_t n_cat, const uint8_t* GT,
-                                  const double* var_count, vrx_barcode** out) {
-    VRX_REQUIRE(GT && out, "vrx_barcode_create: null argument");
-    VRX_REQUIRE(n_var >= 1 && n_var < ((int64_t)1 << 31) - 4096, "vrx_barcode_create: 1 <= n_var < 2^31 - 4096");
-    VRX_REQUIRE(n_donor >= 1 && n_donor <= VRX_BC_MAX_DONORS, "vrx_barcode_create: 1 <= n_donor <= %d",
-                VRX_BC_MAX_DONORS);
-    VRX_REQUIRE(n_cat >= 1 && n_cat <= VRX_BC_MAX_CAT, "vrx_barcode_create: 1 <= categories <= %d", VRX_BC_MAX_CAT);
-    int ndev = 0;
-    vrx_device_count(&ndev);
-    if (device < 0 || device >= ndev) {
-        vrx_set_error("vrx_barcode_create: device %d not available (%d HIP devices visible)", device, ndev);
-        return VRX_ERR_HIP;
-    }
-    VRX_HIP(hipSetDevice(device));
-    struct Del {
-        void operator()(vrx_barcode* b) const { vrx_barcode_destroy(b); }
-    };
-    std::unique_ptr<vrx_barcode, Del> b(new vrx_barcode());
-    b->device = device;
-    b->N = n_var;
-    b->K = (int)n_donor;
-    b->NC = n_cat <= 3 ? 3 : VRX_BC_MAX_CAT;
-    b->stride = ((size_t)n_var + 255) & ~(size_t)255;
-    b->has_vc = var_count != nullptr;
-    const size_t N = (size_t)n_var;
-    VRX_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : b->ev) VRX_HIP(hipEventCreate(&e));
-    hipStream_t s = b->stream;
-    VRX_HIP(b->GT.alloc(b->stride * (size_t)b->K));
-    VRX_HIP(hipMemsetAsync(b->GT.p, 0, b->stride * (size_t)b->K, s));
-    VRX_HIP(hipMemcpy2DAsync(b->GT.p, b->stride, GT, N, N, (size_t)b->K, hipMemcpyHostToDevice, s));
-    if (var_count) VRX_HIP(b->vc.upload(var_count, N, s));
-    VRX_HIP(b->ent.alloc(N));
-    VRX_HIP(b->flag.alloc(N));
-    VRX_HIP(b->tidx.alloc(N));
-    if (var_count) {
-        VRX_HIP(b->flag2.alloc(N));
-        VRX_HIP(b->kidx.alloc(N));
-        VRX_HIP(b->keys.alloc(N));
-        VRX_HIP(b->sorted.alloc(N));
-    }
-    VRX_HIP(b->part.alloc(VRX_BC_MAX_BLOCKS));
-    VRX_HIP(b->scal.alloc(VRX_BC_SCALARS));
-    VRX_HIP(b->ctl.alloc(VRX_BC_CTL_WORDS));
-    VRX_HIP(b->state.alloc((size_t)(2 * b->K + 1)));
-    // the temporary storage of the largest of the three hipCUB calls of a round
-    size_t t1 = 0, t2 = 0, t3 = 0;
-    VRX_HIP(hipcub::DeviceSelect::Flagged(nullptr, t1, hipcub::CountingInputIterator<int32_t>(0), b->flag.p, b->tidx.p,
-                                          b->ctl.p + VRX_BC_TIED, (int)n_var, s));
-    if (var_count) {
-        VRX_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, t2, b->keys.p, b->sorted.p, (int)n_var, 0, 64, s));
-        VRX_HIP(hipcub::DeviceSelect::Flagged(nullptr, t3, b->tidx.p, b->flag2.p, b->kidx.p, b->ctl.p + VRX_BC_KEPT,
-                                              (int)n_var, s));
-    }
-    b->tmp_bytes = std::max(std::max(t1, t2), std::max(t3, (size_t)256));
-    VRX_HIP(b->tmp.alloc(b->tmp_bytes));
-    VRX_HIP(hipStreamSynchronize(s));  // (the caller's arrays may die at return)
-    *out = b.release();
-    return VRX_OK;
-}
-
-extern "C" int vrx_barcode_round(vrx_barcode* b, const int32_t* order, const int32_t* bnd, int32_t n_class,
-                                 const double* table, int32_t half_width, double log2, double* max_out,
-                                 int64_t* counts3, double* ms2) {
-    VRX_REQUIRE(b && order && bnd && table && max_out && counts3, "vrx_barcode_round: null argument");
-    const int K = b->K;
-    VRX_REQUIRE(n_class >= 1 && n_class <= K, "vrx_barcode_round: 1 <= n_class <= n_donor");
-    VRX_REQUIRE(half_width >= 0 && half_width <= VRX_BC_MAX_H, "vrx_barcode_round: 0 <= table half-width <= %d",
-                VRX_BC_MAX_H);
-    VRX_REQUIRE(log2 > 0.0, "vrx_barcode_round: log(2) must be positive");
-    // the state indexes GT and the table: every donor once, the classes non-empty and covering [0, K)
-    {
-        bool seen[VRX_BC_MAX_DONORS] = {};
-        for (int k = 0; k < K; ++k) {
-            VRX_REQUIRE(order[k] >= 0 && order[k] < K && !seen[order[k]],
-                        "vrx_barcode_round: order is not a permutation of the donors");
-            seen[order[k]] = true;
-        }
-        VRX_REQUIRE(bnd[0] == 0 && bnd[n_class] == K, "vrx_barcode_round: class boundaries must run from 0 to n_donor");
-        for (int c = 0; c < n_class; ++c)
-            VRX_REQUIRE(bnd[c] < bnd[c + 1], "vrx_barcode_round: class boundaries must increase");
-    }
-    VRX_HIP(hipSetDevice(b->device));
-    hipStream_t s = b->stream;
-    b->have_round = false;
-    const size_t n_tab = (size_t)(2 * half_width + 1) * (size_t)(K + 1);
-    if (b->table.n < n_tab) VRX_HIP(b->table.alloc(n_tab));
-    VRX_HIP(hipMemcpyAsync(b->table.p, table, n_tab * sizeof(double), hipMemcpyHostToDevice, s));
-    VRX_HIP(hipMemcpyAsync(b->state.p, order, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    VRX_HIP(hipMemcpyAsync(b->state.p + K, bnd, (size_t)(n_class + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    VRX_HIP(hipMemsetAsync(b->ctl.p, 0, VRX_BC_CTL_WORDS * sizeof(int32_t), s));
-    const int64_t N = b->N;
-    const unsigned n_blk = (unsigned)((N + VRX_BC_BLOCK - 1) / VRX_BC_BLOCK);
-    const int n_part = (int)std::min<int64_t>(n_blk, VRX_BC_MAX_BLOCKS);
-    VRX_HIP(hipEventRecord(b->ev[0], s));
-    if (b->NC == 3)
-        vrx_barcode_entropy<3><<<n_blk, VRX_BC_BLOCK, 0, s>>>(N, b->stride, K, n_class, b->GT.p, b->state.p,
-                                                              b->state.p + K, b->table.p, half_width, log2, b->ent.p,
-                                                              b->ctl.p);
-    else
-        vrx_barcode_entropy<VRX_BC_MAX_CAT><<<n_blk, VRX_BC_BLOCK, 0, s>>>(N, b->stride, K, n_class, b->GT.p,
-                                                                           b->state.p, b->state.p + K, b->table.p,
-                                                                           half_width, log2, b->ent.p, b->ctl.p);
-    VRX_HIP(hipEventRecord(b->ev[1], s));
-    vrx_barcode_max<<<n_part, VRX_BC_BLOCK, 0, s>>>(N, b->ent.p, b->part.p);
-    vrx_barcode_max2<<<1, VRX_BC_BLOCK, 0, s>>>(n_part, b->part.p, b->scal.p);
-    vrx_barcode_flag<<<n_blk, VRX_BC_BLOCK, 0, s>>>(N, b->ent.p, b->scal.p, b->flag.p);
-    VRX_HIP(hipGetLastError());
-    size_t tb = b->tmp_bytes;
-    VRX_HIP(hipcub::DeviceSelect::Flagged(b->tmp.p, tb, hipcub::CountingInputIterator<int32_t>(0), b->flag.p,
-                                          b->tidx.p, b->ctl.p + VRX_BC_TIED, (int)N, s));
-    VRX_HIP(hipEventRecord(b->ev[2], s));
-    int32_t hctl[VRX_BC_CTL_WORDS] = {};
-    double hmax = 0.0;
-    VRX_HIP(hipMemcpyAsync(hctl, b->ctl.p, sizeof hctl, hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipMemcpyAsync(&hmax, b->scal.p + VRX_BC_MAX, sizeof(double), hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipStreamSynchronize(s));
-    float t = 0.f;
-    double ms_ent = 0.0, ms_rest = 0.0;
-    VRX_HIP(hipEventElapsedTime(&t, b->ev[0], b->ev[1]));
-    ms_ent = t;
-    VRX_HIP(hipEventElapsedTime(&t, b->ev[1], b->ev[2]));
-    ms_rest = t;
-    counts3[0] = hctl[VRX_BC_TIED];
-    counts3[1] = 0;
-    counts3[2] = hctl[VRX_BC_OUTSIDE];
-    *max_out = hmax;
-    if (ms2) {
-        ms2[0] = ms_ent;
-        ms2[1] = ms_rest;
-    }
-    if (hctl[VRX_BC_OUTSIDE] > 0) {
-        vrx_set_error("vrx_barcode_round: %d variants have a normalising sum more than %d ulp from 1, outside the "
-                      "entropy table (nothing is evaluated approximately: pass a wider table)",
-                      hctl[VRX_BC_OUTSIDE], half_width);
-        return VRX_ERR_UNSUPPORTED;
-    }
-    const int n_tied = hctl[VRX_BC_TIED];
-    int64_t n_kept = n_tied;
-    if (b->has_vc && n_tied > 0) {
-        const unsigned t_blk = (unsigned)((n_tied + VRX_BC_BLOCK - 1) / VRX_BC_BLOCK);
-        VRX_HIP(hipEventRecord(b->ev[3], s));
-        vrx_barcode_gather<<<t_blk, VRX_BC_BLOCK, 0, s>>>(b->ctl.p, b->tidx.p, b->vc.p, b->keys.p);
-        VRX_HIP(hipGetLastError());
-        // (the temporary storage was sized for n_var items; should fewer items ever ask for more, grow it)
-        size_t q1 = 0, q2 = 0;
-        VRX_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, q1, b->keys.p, b->sorted.p, n_tied, 0, 64, s));
-        VRX_HIP(hipcub::DeviceSelect::Flagged(nullptr, q2, b->tidx.p, b->flag2.p, b->kidx.p, b->ctl.p + VRX_BC_KEPT,
-                                              n_tied, s));
-        if (std::max(q1, q2) > b->tmp_bytes) {
-            VRX_HIP(hipStreamSynchronize(s));
-            b->tmp_bytes = std::max(q1, q2);
-            VRX_HIP(b->tmp.alloc(b->tmp_bytes));
-        }
-        tb = b->tmp_bytes;
-        VRX_HIP(hipcub::DeviceRadixSort::SortKeys(b->tmp.p, tb, b->keys.p, b->sorted.p, n_tied, 0, 64, s));
-        vrx_barcode_median<<<1, 1, 0, s>>>(b->ctl.p, b->sorted.p, b->scal.p);
-        vrx_barcode_flag_ge<<<t_blk, VRX_BC_BLOCK, 0, s>>>(b->ctl.p, b->keys.p, b->scal.p, b->flag2.p);
-        VRX_HIP(hipGetLastError());
-        tb = b->tmp_bytes;
-        VRX_HIP(hipcub::DeviceSelect::Flagged(b->tmp.p, tb, b->tidx.p, b->flag2.p, b->kidx.p, b->ctl.p + VRX_BC_KEPT,
-                                              n_tied, s));
-        VRX_HIP(hipEventRecord(b->ev[4], s));
-        int32_t kept = 0;
-        VRX_HIP(hipMemcpyAsync(&kept, b->ctl.p + VRX_BC_KEPT, sizeof kept, hipMemcpyDeviceToHost, s));
-        VRX_HIP(hipStreamSynchronize(s));
-        VRX_HIP(hipEventElapsedTime(&t, b->ev[3], b->ev[4]));
-        if (ms2) ms2[1] = ms_rest + t;
-        n_kept = kept;
-    }
-    counts3[1] = n_kept;
-    b->n_kept = n_kept;
-    b->have_round = true;
-    return VRX_OK;
-}
-
-extern "C" int vrx_barcode_pick(vrx_barcode* b, int64_t r, int64_t* index_out, double* entropy_out) {
-    VRX_REQUIRE(b && index_out && entropy_out, "vrx_barcode_pick: null argument");
-    VRX_REQUIRE(b->have_round, "vrx_barcode_pick: no finished round");
-    VRX_REQUIRE(r >= 0 && r < b->n_kept, "vrx_barcode_pick: r = %lld is not one of the %lld survivors", (long long)r,
-                (long long)b->n_kept);
-    VRX_HIP(hipSetDevice(b->device));
-    hipStream_t s = b->stream;
-    int32_t idx = -1;
-    VRX_HIP(hipMemcpyAsync(&idx, (b->has_vc ? b->kidx.p : b->tidx.p) + r, sizeof idx, hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipStreamSynchronize(s));
-    VRX_REQUIRE(idx >= 0 && idx < b->N, "vrx_barcode_pick: the survivor list is corrupt");
-    VRX_HIP(hipMemcpyAsync(entropy_out, b->ent.p + idx, sizeof(double), hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipStreamSynchronize(s));
-    *index_out = idx;
-    return VRX_OK;
-}
-
-extern "C" int vrx_barcode_entropies(vrx_barcode* b, double* out) {
-    VRX_REQUIRE(b && out, "vrx_barcode_entropies: null argument");
-    VRX_REQUIRE(b->have_round, "vrx_barcode_entropies: no finished round");
-    VRX_HIP(hipSetDevice(b->device));
-    VRX_HIP(hipMemcpyAsync(out, b->ent.p, (size_t)b->N * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    VRX_HIP(hipStreamSynchronize(b->stream));
     return VRX_OK;
 }

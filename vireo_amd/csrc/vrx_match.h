@@ -1,6 +1,6 @@
 // Donor matching (vrx_geno_*): the genotype-distance matrix that optimal_match and donor_select of
 // the reference fill one donor pair at a time (vireoSNP/utils/vireo_base.py:197-201, :230-234; used
-// by match_VCF_samples, vcf_utils.py:404-405).  Included by vrx_engine.hip only.
+// by match_VCF_samples, vcf_utils.py:404-405).  Included by vrx_match.hip only.
 //
 //   D[i][j] = (sum_n sum_t |X[n][i][t] - Z[n][j][t]|) / (n_var * n_gt)
 //   X [n_var][k1][n_gt], Z [n_var][k2][n_gt], C-contiguous float64.  An L1 distance: no product to
