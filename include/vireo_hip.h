@@ -353,6 +353,39 @@ int vrx_barcode_round(vrx_barcode* b, const int32_t* order /* n_donor */, const 
 int vrx_barcode_pick(vrx_barcode* b, int64_t r, int64_t* index_out, double* entropy_out);
 int vrx_barcode_entropies(vrx_barcode* b, double* out /* n_var */);
 
+/* ---- per-variant clone mixtures (vrx_varmix.h) ----------------------------------------------
+ * BinomMixtureVB._fit_BV (vireoSNP/utils/bmm_model.py:178-201) on every variant's own 1 x n_cell row,
+ * with default priors (set_prior, :87-105), fix_beta_sum = False and a start computed from the counts,
+ * against the same bound with n_donor = 1: the "M1 multiple donors vs M0 single donor" of
+ * variant_ELBO_gain (variant_select.py:66-106) with the assignment learned per variant.
+ * vrx_varmix_create: a CSR of the covered entries only (dp > 0, 0 <= ad <= dp, in increasing cell
+ * index); no column indices -- update_theta_size (:133-144), get_E_logLik (:118-130), update_ID_prob
+ * (:147-154) and get_ELBO (:157-175) never ask which cell an entry is, and a cell without reads adds
+ * exactly nothing to any of them.  n_var = 0 and nnz = 0 are legal; an invalid entry or a rowptr that
+ * is not monotone from 0 to nnz is VRX_ERR_ARG.
+ * vrx_varmix_wave_rows: the longest row one wavefront fits; longer rows take a workgroup (a
+ * compile-time constant).
+ * vrx_varmix_fit: one launch fits every row with n_clone components from
+ *   ID_init_ik = w_k / sum_k w_k,  w_k = max(0, 1 - |a_i / d_i - k / (K - 1)| (K - 1)) + 1/64
+ * (what ID_prob_init would be, :80-81) and evaluates the stop rule of :190-199 per row on the device.
+ * Per row: n_iter = `it` at exit; elbo_k = ELBO[it - 1], the reference's ELBO_iters[-1] (:201);
+ * elbo_one = the value _fit_BV records at every iteration with n_donor = 1 (closed form); beta_mu,
+ * beta_sum of iteration `it`; size = sum of ID_prob of iteration `it` over the covered cells; warn
+ * bit 0: the bound decreased by more than 1e-6 (:191), bit 1: not converged (:195); trace (may be
+ * NULL) = ELBO[0 .. it], zeros after it.  An empty row returns elbo 0, beta_mu 0.5, beta_sum 2,
+ * size 0.  Results are bitwise a function of the row's entries and the parameters.  n_clone outside
+ * 2 ... 8 or max_iter < 2: VRX_ERR_UNSUPPORTED.  ms (may be NULL): milliseconds of the kernel. */
+typedef struct vrx_varmix vrx_varmix;
+int vrx_varmix_create(int device, int64_t n_var, int64_t nnz, const int64_t* rowptr /* n_var + 1 */,
+                      const int32_t* ad, const int32_t* dp, vrx_varmix** out);
+void vrx_varmix_destroy(vrx_varmix* h);
+int32_t vrx_varmix_wave_rows(void);
+int vrx_varmix_fit(vrx_varmix* h, int32_t n_clone, int32_t max_iter, int32_t min_iter, double epsilon_conv,
+                   double* elbo_k, double* elbo_one,                /* n_var each */
+                   double* beta_mu, double* beta_sum, double* size, /* n_var x n_clone, any may be NULL */
+                   int32_t* n_iter, int32_t* warn,                  /* n_var */
+                   double* trace /* n_var x max_iter or NULL */, double* ms /* kernel ms or NULL */);
+
 /* ---- timing (bench.py roofline leg) ---------------------------------------------------
  * When enabled, every launch of a pass kernel is bracketed by hipEvents on the model's
  * stream; totals are read back after a sync.  Kernel ids: */

@@ -21,11 +21,13 @@ from .vireo_model import Vireo
 from .bmm_model import BinomMixtureVB
 from .vireo_doublet import predict_doublet, add_doublet_GT, add_doublet_theta, predit_ambient
 from .variant_select import variant_ELBO_gain, variant_select, barcode_entropy
+from .variant_mixture import variant_mixture_gain, VariantMixtures
 from .vireo_wrap import vireo_wrap
 from .vireo_bulk import VireoBulk, VireoBulkCohort, LikRatio_test, BulkData, device_bulk
 
 __all__ = ["__version__", "Vireo", "BinomMixtureVB", "vireo_wrap", "predict_doublet",
-           "predit_ambient", "variant_ELBO_gain", "variant_select", "barcode_entropy", "VireoBulk", "VireoBulkCohort", "LikRatio_test", "BulkData", "device_bulk",
+           "predit_ambient", "variant_ELBO_gain", "variant_select", "barcode_entropy",
+           "variant_mixture_gain", "VariantMixtures", "VireoBulk", "VireoBulkCohort", "LikRatio_test", "BulkData", "device_bulk",
            "DeviceCounts", "device_counts", "load_VCF", "match_SNPs", "read_cellSNP",
            "read_vartrix", "normalize", "tensor_normalize", "loglik_amplify", "get_binom_coeff",
            "binom_coeff_sum", "beta_entropy", "match", "optimal_match", "donor_select",

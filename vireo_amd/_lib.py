@@ -94,6 +94,11 @@ SIGNATURES = {
     "vrx_barcode_round": (C.c_int, [_P, _I32, _I32, C.c_int32, _D, C.c_int32, C.c_double, _D, _I64, _D]),
     "vrx_barcode_pick": (C.c_int, [_P, C.c_int64, _I64, _D]),
     "vrx_barcode_entropies": (C.c_int, [_P, _D]),
+    "vrx_varmix_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _I64, _I32, _I32, C.POINTER(_P)]),
+    "vrx_varmix_destroy": (None, [_P]),
+    "vrx_varmix_wave_rows": (C.c_int32, []),
+    "vrx_varmix_fit": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, _D, _D, _D, _D, _D, _I32, _I32,
+                                 _D, _D]),
     "vrx_model_info": (C.c_int, [_P, _I32]),
     "vrx_model_profile": (C.c_int, [_P, C.c_int32]),
     "vrx_model_profile_read": (C.c_int, [_P, _D, _I64]),
