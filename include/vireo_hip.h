@@ -386,6 +386,48 @@ int vrx_varmix_fit(vrx_varmix* h, int32_t n_clone, int32_t max_iter, int32_t min
                    int32_t* n_iter, int32_t* warn,                  /* n_var */
                    double* trace /* n_var x max_iter or NULL */, double* ms /* kernel ms or NULL */);
 
+/* ---- SNP-to-gene matching and gene-level counts (vrx_genematch.h) ----------------------------
+ * snp_gene_match (vireoSNP/utils/vcf_utils.py:423-491): the Python loop over SNPs, each forming its
+ * distance to every gene of its chromosome once per gap (:466-482), as two launches over all SNPs.
+ * Integers only; every result equals the reference's.
+ * vrx_genematch_create: the genes grouped by chromosome code (gene_df[gene_df['chrom'] == _chrom],
+ * :461, for every chromosome at once): chrom_ptr[c] .. chrom_ptr[c + 1] are the genes of code c in
+ * gene_df row order, row[] their gene_df rows; start, stop and row in [0, 2^31 - 1].  n_gene = 0 and a
+ * code without genes are legal.
+ * vrx_genematch_tile / _block: genes of one LDS tile, SNPs of one workgroup (compile-time constants).
+ * vrx_genematch_match: the SNPs sorted by code (code[] non-decreasing, pos[] in [0, 2^31 - 1]);
+ * perm[j] = the index the results of the j-th sorted SNP are written at (a permutation).  gap_m1[k] =
+ * gaps[k] - 1 clamped to the int32 range ("dist < gap", :475, as dist <= gap - 1); single[k] != 0 where
+ * gaps[k] > 0 or multi_gene is False (:477).  flag[i] (:467, :485) and count[i] = len(idx_chrom)
+ * (:475-481) per SNP in the caller's order.  The handle keeps what the second call needs.
+ * vrx_genematch_lists: rows[] = the gene_df rows of idx_chrom (:488), SNP after SNP in the caller's order,
+ * `total` = the sum of the counts of the match before it (anything else: VRX_ERR_ARG).
+ * ms (may be NULL): milliseconds of the kernels of the call.
+ *
+ * vrx_genecount_*: what follows the matching in gene-level ASE, G @ AD and G @ DP with G[g, v] = the
+ * number of times gene g is listed for variant v (the SciPy products of a 0/1 gene x SNP matrix).
+ * vrx_genecount_create: the merged CSC of vrx_merge_counts (variants x cells) and the map as a CSR over
+ * variants (gptr[v] .. gptr[v + 1] index gid[], gene numbers in [0, n_gene)).  Expands every entry to
+ * its genes, sorts by (cell, gene) and adds equal keys in 64 bits.  n_out: distinct (cell, gene) pairs.
+ * vrx_genecount_read: key = cell * n_gene + gene, ascending (column-major), and the two sums. */
+typedef struct vrx_genematch vrx_genematch;
+int vrx_genematch_create(int device, int64_t n_chrom, int64_t n_gene, const int64_t* chrom_ptr /* n_chrom + 1 */,
+                         const int32_t* start, const int32_t* stop, const int32_t* row, vrx_genematch** out);
+void vrx_genematch_destroy(vrx_genematch* h);
+int32_t vrx_genematch_tile(void);
+int32_t vrx_genematch_block(void);
+int vrx_genematch_match(vrx_genematch* h, int64_t n_snp, const int32_t* code, const int32_t* pos,
+                        const int32_t* perm, int32_t n_gap, const int32_t* gap_m1, const uint8_t* single,
+                        int32_t* flag /* n_snp */, int64_t* count /* n_snp */, double* ms);
+int vrx_genematch_lists(vrx_genematch* h, int64_t total, int32_t* rows /* total */, double* ms);
+typedef struct vrx_genecount vrx_genecount;
+int vrx_genecount_create(int device, int64_t n_var, int64_t n_cell, int64_t n_gene,
+                         const int64_t* colptr /* n_cell + 1 */, const int32_t* rowidx, const int32_t* ad,
+                         const int32_t* dp, const int64_t* gptr /* n_var + 1 */, const int32_t* gid,
+                         vrx_genecount** out, int64_t* n_out, double* ms);
+int vrx_genecount_read(vrx_genecount* h, int64_t* key, int64_t* ad, int64_t* dp /* n_out each */);
+void vrx_genecount_destroy(vrx_genecount* h);
+
 /* ---- timing (bench.py roofline leg) ---------------------------------------------------
  * When enabled, every launch of a pass kernel is bracketed by hipEvents on the model's
  * stream; totals are read back after a sync.  Kernel ids: */

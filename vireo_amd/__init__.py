@@ -12,7 +12,7 @@ from . import vcf_utils as vcf
 from . import vireo_base as base
 from . import vireo_model as model
 from .counts import DeviceCounts, device_counts
-from .vcf_utils import load_VCF, match_SNPs, match_VCF_samples
+from .vcf_utils import load_VCF, match_SNPs, match_VCF_samples, snp_gene_match
 from .io_utils import read_cellSNP, read_vartrix
 from .vireo_base import (normalize, tensor_normalize, loglik_amplify, get_binom_coeff,
                          binom_coeff_sum, beta_entropy, match, optimal_match, donor_select,
@@ -22,6 +22,7 @@ from .bmm_model import BinomMixtureVB
 from .vireo_doublet import predict_doublet, add_doublet_GT, add_doublet_theta, predit_ambient
 from .variant_select import variant_ELBO_gain, variant_select, barcode_entropy
 from .variant_mixture import variant_mixture_gain, VariantMixtures
+from .gene_match import gene_counts
 from .vireo_wrap import vireo_wrap
 from .vireo_bulk import VireoBulk, VireoBulkCohort, LikRatio_test, BulkData, device_bulk
 
@@ -31,5 +32,5 @@ __all__ = ["__version__", "Vireo", "BinomMixtureVB", "vireo_wrap", "predict_doub
            "DeviceCounts", "device_counts", "load_VCF", "match_SNPs", "read_cellSNP",
            "read_vartrix", "normalize", "tensor_normalize", "loglik_amplify", "get_binom_coeff",
            "binom_coeff_sum", "beta_entropy", "match", "optimal_match", "donor_select",
-           "genotype_distance", "donor_match", "match_VCF_samples",
+           "genotype_distance", "donor_match", "match_VCF_samples", "snp_gene_match", "gene_counts",
            "vcf", "base", "model"]

@@ -99,6 +99,17 @@ SIGNATURES = {
     "vrx_varmix_wave_rows": (C.c_int32, []),
     "vrx_varmix_fit": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, _D, _D, _D, _D, _D, _I32, _I32,
                                  _D, _D]),
+    "vrx_genematch_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _I64, _I32, _I32, _I32, C.POINTER(_P)]),
+    "vrx_genematch_destroy": (None, [_P]),
+    "vrx_genematch_tile": (C.c_int32, []),
+    "vrx_genematch_block": (C.c_int32, []),
+    "vrx_genematch_match": (C.c_int, [_P, C.c_int64, _I32, _I32, _I32, C.c_int32, _I32, C.POINTER(C.c_uint8), _I32,
+                                      _I64, _D]),
+    "vrx_genematch_lists": (C.c_int, [_P, C.c_int64, _I32, _D]),
+    "vrx_genecount_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, _I64, _I32, _I32, _I32, _I64, _I32,
+                                       C.POINTER(_P), _I64, _D]),
+    "vrx_genecount_read": (C.c_int, [_P, _I64, _I64, _I64]),
+    "vrx_genecount_destroy": (None, [_P]),
     "vrx_model_info": (C.c_int, [_P, _I32]),
     "vrx_model_profile": (C.c_int, [_P, C.c_int32]),
     "vrx_model_profile_read": (C.c_int, [_P, _D, _I64]),

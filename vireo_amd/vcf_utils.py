@@ -16,6 +16,7 @@ import numpy as np
 from scipy.sparse import csr_matrix
 
 from . import _lib
+from .gene_match import snp_gene_match                         # noqa: F401  (vcf_utils.py:423-491)
 from .vireo_base import donor_match, match
 
 _MISSING = (".", "./.", ".|.")
