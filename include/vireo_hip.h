@@ -428,6 +428,34 @@ int vrx_genecount_create(int device, int64_t n_var, int64_t n_cell, int64_t n_ge
 int vrx_genecount_read(vrx_genecount* h, int64_t* key, int64_t* ad, int64_t* dp /* n_out each */);
 void vrx_genecount_destroy(vrx_genecount* h);
 
+/* ---- pooling cell columns of several samples (vrx_pool.h) ---------------------------------------
+ * The matrix-level counterpart of simulate/synth_pool.py: its BAM step only rewrites each read's cell
+ * tag to the pooled barcode (:126-141) and pile-up is additive over reads, so on a fixed variant list
+ * the counts of a pooled cell are the sum of its source cells' columns.  Integers only.
+ * vrx_pool_create: the merged CSC of vrx_merge_counts of every sample, concatenated along the columns
+ * (n_src source cells; rows strictly increasing inside a column and below n_var, counts not negative:
+ * anything else is VRX_ERR_ARG).  The handle keeps the sources on the device.
+ * vrx_pool_run: pooled column j = source column src0[j], plus source column src1[j] unless that is -1,
+ * on the union of their rows; a source may serve several pooled columns.  colptr_out: the n_pool + 1
+ * offsets of the result.  bad = -1, or the smallest pooled column in which a sum reached 2^31 (the
+ * result is then not to be used).  A pooled column is a function of its sources alone, bit for bit.
+ * One launch covers the plan, so long columns + ceil(short columns / 4) must stay below 2^24 workgroups
+ * (16.7 M long or 67 M short pooled columns); a larger plan is VRX_ERR_ARG and has to be run in parts.
+ * ms (may be NULL): milliseconds of the kernels.
+ * vrx_pool_read: the colptr_out[n_pool] entries of the run before it (rows increasing per column).
+ * vrx_pool_wave_limit: the most source entries of a pooled column that one wavefront walks; above it a
+ * workgroup does.  vrx_pool_scan_block: pooled columns per workgroup of the offset scan.  Both are
+ * compile-time constants. */
+typedef struct vrx_pool vrx_pool;
+int vrx_pool_create(int device, int64_t n_var, int64_t n_src, const int64_t* colptr /* n_src + 1 */,
+                    const int32_t* rowidx, const int32_t* ad, const int32_t* dp, vrx_pool** out);
+void vrx_pool_destroy(vrx_pool* h);
+int32_t vrx_pool_wave_limit(void);
+int32_t vrx_pool_scan_block(void);
+int vrx_pool_run(vrx_pool* h, int64_t n_pool, const int32_t* src0, const int32_t* src1 /* n_pool each */,
+                 int64_t* colptr_out /* n_pool + 1 */, int64_t* bad, double* ms);
+int vrx_pool_read(vrx_pool* h, int32_t* rowidx, int32_t* ad, int32_t* dp);
+
 /* ---- timing (bench.py roofline leg) ---------------------------------------------------
  * When enabled, every launch of a pass kernel is bracketed by hipEvents on the model's
  * stream; totals are read back after a sync.  Kernel ids: */

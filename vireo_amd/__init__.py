@@ -25,6 +25,23 @@ from .variant_mixture import variant_mixture_gain, VariantMixtures
 from .gene_match import gene_counts
 from .vireo_wrap import vireo_wrap
 from .vireo_bulk import VireoBulk, VireoBulkCohort, LikRatio_test, BulkData, device_bulk
+from .base_utils import get_confusion
+
+_POOL = ("sample_barcodes", "pool_barcodes", "pool_plan", "PoolPlan", "pool_counts", "DevicePool")
+
+
+def __getattr__(name):
+    # vireo_amd.synth_pool is also a command (python -m): its names are looked up on first use, so that running
+    # the command does not find its module imported already
+    if name in _POOL:
+        from . import synth_pool
+        return getattr(synth_pool, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+def __dir__():
+    return sorted(set(globals()) | set(_POOL))
+
 
 __all__ = ["__version__", "Vireo", "BinomMixtureVB", "vireo_wrap", "predict_doublet",
            "predit_ambient", "variant_ELBO_gain", "variant_select", "barcode_entropy",
@@ -33,4 +50,4 @@ __all__ = ["__version__", "Vireo", "BinomMixtureVB", "vireo_wrap", "predict_doub
            "read_vartrix", "normalize", "tensor_normalize", "loglik_amplify", "get_binom_coeff",
            "binom_coeff_sum", "beta_entropy", "match", "optimal_match", "donor_select",
            "genotype_distance", "donor_match", "match_VCF_samples", "snp_gene_match", "gene_counts",
-           "vcf", "base", "model"]
+           "get_confusion", "vcf", "base", "model"] + list(_POOL)

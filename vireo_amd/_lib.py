@@ -110,6 +110,12 @@ SIGNATURES = {
                                        C.POINTER(_P), _I64, _D]),
     "vrx_genecount_read": (C.c_int, [_P, _I64, _I64, _I64]),
     "vrx_genecount_destroy": (None, [_P]),
+    "vrx_pool_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _I64, _I32, _I32, _I32, C.POINTER(_P)]),
+    "vrx_pool_destroy": (None, [_P]),
+    "vrx_pool_wave_limit": (C.c_int32, []),
+    "vrx_pool_scan_block": (C.c_int32, []),
+    "vrx_pool_run": (C.c_int, [_P, C.c_int64, _I32, _I32, _I64, _I64, _D]),
+    "vrx_pool_read": (C.c_int, [_P, _I32, _I32, _I32]),
     "vrx_model_info": (C.c_int, [_P, _I32]),
     "vrx_model_profile": (C.c_int, [_P, C.c_int32]),
     "vrx_model_profile_read": (C.c_int, [_P, _D, _I64]),
