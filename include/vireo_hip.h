@@ -456,6 +456,47 @@ int vrx_pool_run(vrx_pool* h, int64_t n_pool, const int32_t* src0, const int32_t
                  int64_t* colptr_out /* n_pool + 1 */, int64_t* bad, double* ms);
 int vrx_pool_read(vrx_pool* h, int32_t* rowidx, int32_t* ad, int32_t* dp);
 
+/* ---- donor VCF text (vrx_vcf.h) ---------------------------------------------------------------------
+ * The decompressed text of a donor VCF -> the unnormalised genotype values of the lines whose variant
+ * occurs in the cell data: what load_VCF (vcf_utils.py:80-159: the line loop, the id CHROM_POS_REF_ALT,
+ * the biallelic filter, the tag counts), match_donor_VCF / match_SNPs (io_utils.py:10-39 over match(),
+ * vireo_base.py:130-184) and the code conversion of parse_donor_GPb (vcf_utils.py:299-350) do one
+ * Python string at a time.  The host inflates the file, reads the header and feeds whole lines in slabs;
+ * the text stays on the device for one slab.
+ * vrx_vcf_create: tag 0 GT / 1 PL / 2 GP; n_sample = the sample columns of the #CHROM line; the cell
+ * variant ids as one byte buffer with n_ids + 1 offsets (n_ids = -1: no matching, every kept line is a
+ * row); pl_table = the 4096 values 10 ** (-0.1 * d - 0.025) made by NumPy (PL only, else may be NULL).
+ * The ids are hashed (64 bits) with the device function that hashes a line's id, sorted once, and equal
+ * hashes compared on bytes.
+ * vrx_vcf_begin: starts a pass over the file.  mode 0: ids as they are; 1: "chr" + cell id; 2: "chr" +
+ * donor id (the retries of match_SNPs, in that order; the caller re-feeds the file when a pass matched
+ * nothing); -1 with n_ids = -1.  *status = the status of the cell table.
+ * vrx_vcf_slab: n_bytes (< 2^31 - 64) of whole lines; only the last line of the file may lack its line
+ * end.  info[0] = kept lines (after the filter), info[1] = those whose FORMAT names the tag, info[2] =
+ * matched lines, info[3] = status bits: 1 equal cell ids, 2 a cell variant claimed by a second line,
+ * 4 equal hashes on different bytes, 8 a '#' line, 16 a line with fewer than 9 fields, 32 a non-ASCII
+ * byte or a '\r' not followed by '\n'.  With a status the results of the pass are void (the caller uses
+ * the host functions).  seconds (may be NULL): upload, kernels.
+ * vrx_vcf_rows: the info[2] matched lines of the slab before it, in file order: gpb[row][sample][3],
+ * slot = the cell variant (the line's ordinal without matching), line = its ordinal among the kept lines
+ * of the file, flag 1 = outside the device's grammar (the caller parses the line; its gpb row is
+ * undefined), span = the line's [start, end) bytes in the slab, line end included.  Accepted: '.', './.',
+ * '.|.'; GT first and last character digits with sum <= 2; PL three unsigned integers <= 4095; GP three
+ * digits[.digits] of at most 15 significant and 22 fractional digits (integer / exact power of ten, one
+ * correctly rounded division).  A row is bitwise a function of its line.  seconds (may be NULL): kernels,
+ * download.
+ * vrx_vcf_chunk: bytes of a line a wavefront looks at per step (a compile-time constant). */
+typedef struct vrx_vcf vrx_vcf;
+int vrx_vcf_create(int device, int32_t tag, int32_t n_sample, int32_t biallelic_only, int64_t n_ids,
+                   const char* id_bytes, const int64_t* id_off /* n_ids + 1 */, const double* pl_table /* 4096 */,
+                   vrx_vcf** out);
+void vrx_vcf_destroy(vrx_vcf* h);
+int32_t vrx_vcf_chunk(void);
+int vrx_vcf_begin(vrx_vcf* h, int32_t mode, int32_t* status);
+int vrx_vcf_slab(vrx_vcf* h, const char* text, int64_t n_bytes, int64_t* info /* 4 */, double* seconds /* 2 */);
+int vrx_vcf_rows(vrx_vcf* h, double* gpb, int64_t* slot, int64_t* line, int32_t* flag, int64_t* span,
+                 double* seconds /* 2 */);
+
 /* ---- timing (bench.py roofline leg) ---------------------------------------------------
  * When enabled, every launch of a pass kernel is bracketed by hipEvents on the model's
  * stream; totals are read back after a sync.  Kernel ids: */

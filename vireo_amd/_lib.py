@@ -116,6 +116,13 @@ SIGNATURES = {
     "vrx_pool_scan_block": (C.c_int32, []),
     "vrx_pool_run": (C.c_int, [_P, C.c_int64, _I32, _I32, _I64, _I64, _D]),
     "vrx_pool_read": (C.c_int, [_P, _I32, _I32, _I32]),
+    "vrx_vcf_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_char_p, _I64, _D,
+                                 C.POINTER(_P)]),
+    "vrx_vcf_destroy": (None, [_P]),
+    "vrx_vcf_chunk": (C.c_int32, []),
+    "vrx_vcf_begin": (C.c_int, [_P, C.c_int32, _I32]),
+    "vrx_vcf_slab": (C.c_int, [_P, C.c_char_p, C.c_int64, _I64, _D]),
+    "vrx_vcf_rows": (C.c_int, [_P, _D, _I64, _I64, _I32, _I64, _D]),
     "vrx_model_info": (C.c_int, [_P, _I32]),
     "vrx_model_profile": (C.c_int, [_P, C.c_int32]),
     "vrx_model_profile_read": (C.c_int, [_P, _D, _I64]),

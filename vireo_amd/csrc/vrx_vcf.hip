@@ -1,0 +1,285 @@
+// Donor VCF text on the device: the vrx_vcf_* entries of include/vireo_hip.h on the kernels of vrx_vcf.h.
+// A handle owns its stream and buffers; nothing here touches a vrx_problem or a vrx_model.
+#include <algorithm>
+#include <chrono>
+#include <memory>
+
+#include <hipcub/hipcub.hpp>
+
+#include "vrx_common.h"
+#include "vrx_vcf.h"
+
+namespace {
+constexpr size_t kRowBatchBytes = (size_t)128 << 20;  // rows of one vrx_vcf_rows launch (device staging)
+
+double seconds_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+}  // namespace
+
+struct vrx_vcf {
+    int device = 0;
+    int32_t tag = 0, n_sample = 0, biallelic_only = 1, mode = -1;
+    bool matching = false;
+    int64_t n_ids = 0;
+    uint32_t table_status = 0;
+    hipStream_t stream = nullptr;
+    // cell table
+    DevBuf<uint8_t> id_bytes;
+    DevBuf<int64_t> id_off;
+    DevBuf<uint64_t> hash;
+    DevBuf<int32_t> idx, claim;
+    DevBuf<double> pl_table;
+    // slab
+    uint32_t n = 0, n_lines = 0;
+    int64_t n_matched = 0, line_base = 0, kept_total = 0;
+    DevBuf<uint8_t> text, flag, match, tmp;
+    DevBuf<uint32_t> lstart, ctl;  // ctl: 0 lines of the slab, 1 status, 2 matched, 3 tagged
+    DevBuf<int32_t> kept, tagged, ord, mlist;
+    DevBuf<VrxVcfLine> rec;
+    // rows
+    DevBuf<double> gpb;
+    DevBuf<int64_t> slot, ordinal, span;
+    DevBuf<int32_t> rflag;
+};
+
+template <typename T>
+static hipError_t vrx_vcf_reserve(DevBuf<T>& b, size_t count) {
+    return b.n >= count ? hipSuccess : b.alloc(count + count / 8);
+}
+
+extern "C" int32_t vrx_vcf_chunk(void) { return VRX_VCF_CHUNK; }
+
+extern "C" void vrx_vcf_destroy(vrx_vcf* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->stream) {
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipStreamDestroy(h->stream);
+    }
+    delete h;
+}
+
+extern "C" int vrx_vcf_create(int device, int32_t tag, int32_t n_sample, int32_t biallelic_only, int64_t n_ids,
+                              const char* id_bytes, const int64_t* id_off, const double* pl_table, vrx_vcf** out) {
+    VRX_REQUIRE(out, "vrx_vcf_create: null argument");
+    VRX_REQUIRE(tag == VRX_VCF_GT || tag == VRX_VCF_PL || tag == VRX_VCF_GP, "vrx_vcf_create: tag must be 0 (GT), 1 (PL) or 2 (GP)");
+    VRX_REQUIRE(n_sample >= 1 && n_sample < (1 << 24), "vrx_vcf_create: 1 <= n_sample < 2^24");
+    VRX_REQUIRE(tag != VRX_VCF_PL || pl_table, "vrx_vcf_create: PL needs its table");
+    VRX_REQUIRE(n_ids < ((int64_t)1 << 31) - 4, "vrx_vcf_create: n_ids < 2^31 - 4");
+    if (n_ids >= 0) {
+        VRX_REQUIRE(id_off && id_off[0] == 0, "vrx_vcf_create: id_off must start at 0");
+        for (int64_t i = 0; i < n_ids; ++i)
+            VRX_REQUIRE(id_off[i] <= id_off[i + 1], "vrx_vcf_create: id_off decreases at id %lld", (long long)i);
+        VRX_REQUIRE(id_off[n_ids] == 0 || id_bytes, "vrx_vcf_create: ids need their bytes");
+    }
+    if (int e = vrx_use_device("vrx_vcf_create", device)) return e;
+    struct Del {
+        void operator()(vrx_vcf* h) const { vrx_vcf_destroy(h); }
+    };
+    std::unique_ptr<vrx_vcf, Del> h(new vrx_vcf());
+    h->device = device;
+    h->tag = tag;
+    h->n_sample = n_sample;
+    h->biallelic_only = biallelic_only != 0;
+    h->matching = n_ids >= 0;
+    h->n_ids = std::max<int64_t>(n_ids, 0);
+    VRX_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    hipStream_t s = h->stream;
+    VRX_HIP(h->ctl.alloc(4));
+    VRX_HIP(hipMemsetAsync(h->ctl.p, 0, 4 * sizeof(uint32_t), s));
+    if (pl_table) VRX_HIP(h->pl_table.upload(pl_table, VRX_VCF_PL_MAX + 1, s));
+    const size_t N = (size_t)h->n_ids;
+    if (N > 0) {
+        DevBuf<uint64_t> hash_in;
+        DevBuf<int32_t> idx_in;
+        VRX_HIP(h->id_bytes.upload(reinterpret_cast<const uint8_t*>(id_bytes), (size_t)id_off[N], s));
+        VRX_HIP(h->id_off.upload(id_off, N + 1, s));
+        VRX_HIP(hash_in.alloc(N));
+        VRX_HIP(idx_in.alloc(N));
+        VRX_HIP(h->hash.alloc(N));
+        VRX_HIP(h->idx.alloc(N));
+        VRX_HIP(h->claim.alloc(N));
+        const unsigned n_blk = (unsigned)((N + VRX_VCF_BLOCK - 1) / VRX_VCF_BLOCK);
+        vrx_vcf_hash_ids<<<n_blk, VRX_VCF_BLOCK, 0, s>>>(h->id_bytes.p, h->id_off.p, (int64_t)N, hash_in.p, idx_in.p);
+        VRX_HIP(hipGetLastError());
+        size_t tb = 0;
+        VRX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, hash_in.p, h->hash.p, idx_in.p, h->idx.p, (int)N, 0, 64, s));
+        VRX_HIP(vrx_vcf_reserve(h->tmp, tb));
+        VRX_HIP(hipcub::DeviceRadixSort::SortPairs(h->tmp.p, tb, hash_in.p, h->hash.p, idx_in.p, h->idx.p, (int)N, 0, 64, s));
+        vrx_vcf_table_check<<<n_blk, VRX_VCF_BLOCK, 0, s>>>(h->id_bytes.p, h->id_off.p, (int64_t)N, h->hash.p, h->idx.p,
+                                                            h->ctl.p + 1);
+        VRX_HIP(hipGetLastError());
+        VRX_HIP(hipMemcpyAsync(&h->table_status, h->ctl.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipStreamSynchronize(s));  // (the staging buffers die at return)
+    }
+    VRX_HIP(hipStreamSynchronize(s));
+    *out = h.release();
+    return VRX_OK;
+}
+
+extern "C" int vrx_vcf_begin(vrx_vcf* h, int32_t mode, int32_t* status) {
+    VRX_REQUIRE(h && status, "vrx_vcf_begin: null argument");
+    VRX_REQUIRE(h->matching ? (mode >= 0 && mode <= 2) : mode == -1,
+                "vrx_vcf_begin: mode is 0, 1 or 2 with a cell table and -1 without");
+    VRX_HIP(hipSetDevice(h->device));
+    h->mode = mode;
+    h->n = h->n_lines = 0;
+    h->n_matched = h->line_base = h->kept_total = 0;
+    if (h->n_ids > 0) VRX_HIP(hipMemsetAsync(h->claim.p, 0, (size_t)h->n_ids * sizeof(int32_t), h->stream));
+    VRX_HIP(hipStreamSynchronize(h->stream));
+    *status = (int32_t)h->table_status;
+    return VRX_OK;
+}
+
+extern "C" int vrx_vcf_slab(vrx_vcf* h, const char* text, int64_t n_bytes, int64_t* info, double* seconds) {
+    VRX_REQUIRE(h && info, "vrx_vcf_slab: null argument");
+    VRX_REQUIRE(h->mode >= -1 && (h->mode >= 0) == h->matching, "vrx_vcf_slab: vrx_vcf_begin first");
+    VRX_REQUIRE(n_bytes >= 0 && n_bytes < ((int64_t)1 << 31) - 64, "vrx_vcf_slab: a slab holds fewer than 2^31 - 64 bytes");
+    VRX_REQUIRE(n_bytes == 0 || text, "vrx_vcf_slab: null text");
+    VRX_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    info[0] = info[1] = info[2] = 0;
+    info[3] = (int64_t)h->table_status;
+    if (seconds) seconds[0] = seconds[1] = 0.0;
+    h->line_base = h->kept_total;
+    h->n = (uint32_t)n_bytes;
+    h->n_lines = 0;
+    h->n_matched = 0;
+    if (n_bytes == 0) return VRX_OK;
+    const size_t n = (size_t)n_bytes;
+    const size_t n_pad = (n + VRX_VCF_MARK_BYTES - 1) / VRX_VCF_MARK_BYTES * VRX_VCF_MARK_BYTES;
+    auto t0 = std::chrono::steady_clock::now();
+    VRX_HIP(vrx_vcf_reserve(h->text, n_pad + 2 * VRX_VCF_MARK_BYTES));
+    VRX_HIP(vrx_vcf_reserve(h->flag, n_pad + VRX_VCF_MARK_BYTES));
+    VRX_HIP(hipMemcpyAsync(h->text.p, text, n, hipMemcpyHostToDevice, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    if (seconds) seconds[0] = seconds_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    uint32_t ctl[4] = {0, h->table_status, 0, 0};
+    VRX_HIP(hipMemcpyAsync(h->ctl.p, ctl, sizeof ctl, hipMemcpyHostToDevice, s));
+    const size_t per_block = (size_t)VRX_VCF_BLOCK * VRX_VCF_MARK_BYTES;
+    vrx_vcf_mark<<<(unsigned)((n + per_block - 1) / per_block), VRX_VCF_BLOCK, 0, s>>>(h->text.p, (uint32_t)n, h->flag.p,
+                                                                                        h->ctl.p, h->ctl.p + 1);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(hipMemcpyAsync(ctl, h->ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    const size_t L = ctl[0];
+    // a line that load_VCF can index has 8 tabs and a line end, the last one may lack the line end
+    if (L * 9 > n + 1) ctl[1] |= VRX_VCF_ST_SHORT;
+    if (ctl[1]) {  // the caller takes the host path: nothing more to do here
+        info[3] = ctl[1];
+        if (seconds) seconds[1] = seconds_since(t0);
+        return VRX_OK;
+    }
+    h->n_lines = (uint32_t)L;
+    VRX_HIP(vrx_vcf_reserve(h->lstart, L));
+    VRX_HIP(vrx_vcf_reserve(h->kept, L));
+    VRX_HIP(vrx_vcf_reserve(h->tagged, L));
+    VRX_HIP(vrx_vcf_reserve(h->ord, L));
+    VRX_HIP(vrx_vcf_reserve(h->mlist, L));
+    VRX_HIP(vrx_vcf_reserve(h->match, L));
+    VRX_HIP(vrx_vcf_reserve(h->rec, L));
+    size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0;
+    hipcub::CountingInputIterator<uint32_t> bytes_it(0);
+    hipcub::CountingInputIterator<int32_t> lines_it(0);
+    VRX_HIP(hipcub::DeviceSelect::Flagged(nullptr, t1, bytes_it, h->flag.p, h->lstart.p, h->ctl.p + 2, (int)n, s));
+    VRX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, t2, h->kept.p, h->ord.p, (int)L, s));
+    VRX_HIP(hipcub::DeviceSelect::Flagged(nullptr, t3, lines_it, h->match.p, h->mlist.p, h->ctl.p + 2, (int)L, s));
+    VRX_HIP(hipcub::DeviceReduce::Sum(nullptr, t4, h->tagged.p, reinterpret_cast<int32_t*>(h->ctl.p + 3), (int)L, s));
+    const size_t tb = std::max(std::max(t1, t2), std::max(t3, t4));
+    VRX_HIP(vrx_vcf_reserve(h->tmp, tb));
+    VRX_HIP(hipcub::DeviceSelect::Flagged(h->tmp.p, t1, bytes_it, h->flag.p, h->lstart.p, h->ctl.p + 2, (int)n, s));
+    VrxVcfLinesArgs g;
+    g.text = h->text.p;
+    g.n = (uint32_t)n;
+    g.lstart = h->lstart.p;
+    g.n_lines = (uint32_t)L;
+    g.tag = h->tag;
+    g.biallelic_only = h->biallelic_only;
+    g.mode = h->mode;
+    g.n_ids = h->n_ids;
+    g.id_bytes = h->id_bytes.p;
+    g.id_off = h->id_off.p;
+    g.hash = h->hash.p;
+    g.idx = h->idx.p;
+    g.claim = h->claim.p;
+    g.kept = h->kept.p;
+    g.tagged = h->tagged.p;
+    g.match = h->match.p;
+    g.rec = h->rec.p;
+    g.status = h->ctl.p + 1;
+    vrx_vcf_lines<<<(unsigned)((L + VRX_VCF_WAVES - 1) / VRX_VCF_WAVES), VRX_VCF_BLOCK, 0, s>>>(g);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(hipcub::DeviceScan::InclusiveSum(h->tmp.p, t2, h->kept.p, h->ord.p, (int)L, s));
+    VRX_HIP(hipcub::DeviceSelect::Flagged(h->tmp.p, t3, lines_it, h->match.p, h->mlist.p, h->ctl.p + 2, (int)L, s));
+    VRX_HIP(hipcub::DeviceReduce::Sum(h->tmp.p, t4, h->tagged.p, reinterpret_cast<int32_t*>(h->ctl.p + 3), (int)L, s));
+    int32_t n_kept = 0;
+    VRX_HIP(hipMemcpyAsync(ctl, h->ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(&n_kept, h->ord.p + (L - 1), sizeof n_kept, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    if (seconds) seconds[1] = seconds_since(t0);
+    h->n_matched = ctl[2];
+    h->kept_total += n_kept;
+    info[0] = n_kept;
+    info[1] = ctl[3];
+    info[2] = ctl[2];
+    info[3] = ctl[1];
+    return VRX_OK;
+}
+
+extern "C" int vrx_vcf_rows(vrx_vcf* h, double* gpb, int64_t* slot, int64_t* line, int32_t* flag, int64_t* span,
+                            double* seconds) {
+    VRX_REQUIRE(h, "vrx_vcf_rows: null handle");
+    if (seconds) seconds[0] = seconds[1] = 0.0;
+    const int64_t M = h->n_matched;
+    if (M == 0) return VRX_OK;
+    VRX_REQUIRE(gpb && slot && line && flag && span, "vrx_vcf_rows: null output");
+    VRX_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t row = (size_t)h->n_sample * 3;
+    const int64_t cap = std::min<int64_t>(M, std::max<size_t>(1, kRowBatchBytes / (row * sizeof(double))));
+    VRX_HIP(vrx_vcf_reserve(h->gpb, (size_t)cap * row));
+    VRX_HIP(vrx_vcf_reserve(h->slot, (size_t)cap));
+    VRX_HIP(vrx_vcf_reserve(h->ordinal, (size_t)cap));
+    VRX_HIP(vrx_vcf_reserve(h->rflag, (size_t)cap));
+    VRX_HIP(vrx_vcf_reserve(h->span, (size_t)cap * 2));
+    VrxVcfRowsArgs g;
+    g.text = h->text.p;
+    g.n = h->n;
+    g.n_lines = h->n_lines;
+    g.lstart = h->lstart.p;
+    g.rec = h->rec.p;
+    g.ord = h->ord.p;
+    g.mlist = h->mlist.p;
+    g.line_base = h->line_base;
+    g.tag = h->tag;
+    g.n_sample = h->n_sample;
+    g.matching = h->matching;
+    g.pl_table = h->pl_table.p;
+    g.gpb = h->gpb.p;
+    g.slot = h->slot.p;
+    g.ordinal = h->ordinal.p;
+    g.flag = h->rflag.p;
+    g.span = h->span.p;
+    for (int64_t first = 0; first < M; first += cap) {
+        const int64_t count = std::min(cap, M - first);
+        g.first = first;
+        g.count = count;
+        auto t0 = std::chrono::steady_clock::now();
+        vrx_vcf_rows<<<(unsigned)((count + VRX_VCF_WAVES - 1) / VRX_VCF_WAVES), VRX_VCF_BLOCK, 0, s>>>(g);
+        VRX_HIP(hipGetLastError());
+        VRX_HIP(hipStreamSynchronize(s));
+        if (seconds) seconds[0] += seconds_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        const size_t c = (size_t)count;
+        VRX_HIP(hipMemcpyAsync(gpb + (size_t)first * row, g.gpb, c * row * sizeof(double), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipMemcpyAsync(slot + first, g.slot, c * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipMemcpyAsync(line + first, g.ordinal, c * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipMemcpyAsync(flag + first, g.flag, c * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipMemcpyAsync(span + first * 2, g.span, c * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipStreamSynchronize(s));
+        if (seconds) seconds[1] += seconds_since(t0);
+    }
+    return VRX_OK;
+}

@@ -1,14 +1,19 @@
-"""VCF text I/O used by the ``vireo`` command (host side, no GPU work).
+"""VCF text I/O used by the ``vireo`` command (host side, but for ``load_donor_GPb``).
 
 Own implementation of what the command needs from vireoSNP/utils/vcf_utils.py: loading a
 cellSNP / donor VCF (:80-159), its sparse per-cell AD/DP (:192-205), donor genotype
 probabilities from GT / GP / PL tags (:299-336), SNP matching with or without the ``chr``
 prefix (:339-350) and writing the estimated donor genotypes (:208-296).  Return
 structures keep the reference's dict keys so downstream code reads the same.
+``load_donor_GPb`` does the donor side of ``vireo -d`` -- load, match to the cell variants,
+convert -- in one pass over the text on the GPU (csrc/vrx_vcf.h); the host functions stay
+as its yardstick and its host path.
 """
 import gzip
+import os
 import shutil
 import subprocess
+import time
 
 import ctypes as C
 
@@ -176,20 +181,25 @@ def parse_donor_GPb(GT_dat, tag='GT', min_prob=0.0):
     P = _parse_codes_vectorised(GT_dat, tag)
     if P is None:           # ragged rows or fields that are not three numbers: one code at a time
         P = np.zeros((len(GT_dat), len(GT_dat[0]), 3))
-        for i, row in enumerate(GT_dat):
-            for j, code in enumerate(row):
-                if code in _MISSING:
-                    P[i, j] = 1 / 3
-                elif tag == 'GT':
-                    P[i, j, int(float(code[0]) + float(code[-1]))] = 1
-                elif tag == 'GP':
-                    P[i, j] = np.array(code.split(','), float)
-                else:
-                    phred = np.array(code.split(','), float)
-                    P[i, j] = 10 ** (-0.1 * (phred - min(phred)) - 0.025)
+        _parse_codes_one_by_one(GT_dat, tag, P)
     P += min_prob
     P /= P.sum(axis=2, keepdims=True)
     return P
+
+
+def _parse_codes_one_by_one(GT_dat, tag, P):
+    """the reference's own loop (vcf_utils.py:311-331) into the zeroed P: raises what it raises"""
+    for i, row in enumerate(GT_dat):
+        for j, code in enumerate(row):
+            if code in _MISSING:
+                P[i, j] = 1 / 3
+            elif tag == 'GT':
+                P[i, j, int(float(code[0]) + float(code[-1]))] = 1
+            elif tag == 'GP':
+                P[i, j] = np.array(code.split(','), float)
+            else:
+                phred = np.array(code.split(','), float)
+                P[i, j] = 10 ** (-0.1 * (phred - min(phred)) - 0.025)
 
 
 def match_SNPs(SNP_ids1, SNPs_ids2):
@@ -200,6 +210,230 @@ def match_SNPs(SNP_ids1, SNPs_ids2):
     if np.mean(idx == None) == 1:                                  # noqa: E711
         idx = match(SNP_ids1, ["chr" + x for x in SNPs_ids2])
     return idx
+
+
+_TAG_CODE = {'GT': 0, 'PL': 1, 'GP': 2}
+_VCF_STATUS = ((1, "equal ids among the cell variants"), (2, "a donor line repeats a matched variant"),
+               (4, "two ids share a 64-bit hash"), (8, "a '#' line after the first data line"),
+               (16, "a line with fewer than 9 fields"),
+               (32, "a non-ASCII byte or a carriage return inside a line"))
+_READ_BYTES = 8 << 20
+_SLAB_BYTES = 256 << 20
+_SLAB_LIMIT = (1 << 31) - 64
+
+
+def _status_reason(status):
+    return "; ".join(text for bit, text in _VCF_STATUS if status & bit)
+
+
+def _donor_host(vcf_file, tag, variants, biallelic_only, min_prob, reason):
+    """load_donor_GPb as the composition it replaces: load_VCF, match_SNPs, parse_donor_GPb"""
+    t0 = time.perf_counter()
+    v = load_VCF(vcf_file, biallelic_only=biallelic_only, sparse=False, format_list=[tag])
+    rows = v['GenoINFO'][tag] if v['GenoINFO'] is not None else []
+    n_tagged = int(v['n_SNP_tagged'][0]) if rows else 0
+    if variants is None:
+        keep = line = np.arange(len(rows), dtype=np.int64)
+        sel = rows
+    else:
+        mm = match_SNPs(variants, v['variants'])
+        keep = np.where(mm != None)[0].astype(np.int64)             # noqa: E711
+        line = mm[keep].astype(np.int64)
+        sel = [rows[x] for x in line]
+    GPb = parse_donor_GPb(sel, tag, min_prob) if sel else np.zeros((0, len(v['samples']), 3))
+    sec = dict(inflate=0.0, upload=0.0, kernels=0.0, download=0.0, host=time.perf_counter() - t0)
+    return dict(GPb=GPb, samples=v['samples'], keep=keep, line=line, n_lines=len(rows), n_tagged=n_tagged,
+                n_repaired=0, path='host', reason=reason, seconds=sec)
+
+
+class _DonorText:
+    """The decompressed bytes of a VCF: the '#' lines at its head, then slabs of whole lines."""
+
+    def __init__(self, path, seconds):
+        self.fh = gzip.open(path, "rb") if path.endswith((".gz", ".bgz")) else open(path, "rb")
+        self.seconds = seconds
+        self.buf, self.pos, self.eof = bytearray(), 0, False
+
+    def close(self):
+        self.fh.close()
+
+    def _more(self):
+        t0 = time.perf_counter()
+        chunk = self.fh.read(_READ_BYTES)
+        self.seconds['inflate'] += time.perf_counter() - t0
+        if not chunk:
+            self.eof = True
+        else:
+            del self.buf[:self.pos]
+            self.pos = 0
+            self.buf += chunk
+
+    def header(self):
+        lines = []
+        while True:
+            if self.pos >= len(self.buf):
+                if self.eof:
+                    break
+                self._more()
+                continue
+            if self.buf[self.pos] != 0x23:
+                break
+            end = self.buf.find(b"\n", self.pos)
+            if end < 0 and not self.eof:
+                self._more()
+                continue
+            end = len(self.buf) if end < 0 else end + 1
+            lines.append(bytes(self.buf[self.pos:end]))
+            self.pos = end
+        return lines
+
+    def slabs(self, slab_bytes):
+        """bytearrays of at most slab_bytes that end at a line end; a longer line gets a slab that holds it"""
+        while True:
+            while not self.eof and len(self.buf) - self.pos < slab_bytes:
+                self._more()
+            if self.pos >= len(self.buf):
+                return
+            cut = self.buf.rfind(b"\n", self.pos, self.pos + slab_bytes)
+            while cut < 0:
+                cut = self.buf.find(b"\n", self.pos + slab_bytes)
+                if cut < 0:
+                    if self.eof:
+                        cut = len(self.buf) - 1
+                    else:
+                        self._more()
+            slab = self.buf[self.pos:cut + 1]
+            self.pos = cut + 1
+            yield slab
+
+
+def load_donor_GPb(vcf_file, tag='GT', variants=None, biallelic_only=True, min_prob=0.0,
+                   device=None, slab_bytes=None, force_host=False):
+    """Genotype probabilities of the donor VCF's variants that occur in ``variants`` (the cell data's
+    "CHROM_POS_REF_ALT" ids), in the order of ``variants``: what ``load_VCF(sparse=False, format_list=[tag])``
+    (vcf_utils.py:80-159), ``match_donor_VCF`` (io_utils.py:10-39; ``match_SNPs`` with its "chr" retries, :339-350)
+    and ``parse_donor_GPb`` (:299-336) give together, bit for bit, from one pass over the text on the GPU
+    (``vrx_vcf_*``).  ``variants=None``: every kept line in file order.  The host inflates the file and feeds it in
+    slabs of whole lines (``slab_bytes``, default 256 MiB); the device finds the lines, ids, filter, tag counts,
+    matches and the unnormalised values of the codes; rows outside its grammar come back flagged and are parsed
+    here by the host functions; ``P += min_prob; P /= P.sum(2)`` is NumPy's.  Returns dict(GPb (n_rows, n_sample,
+    3), samples, keep (indices into variants), line (ordinal among the kept lines), n_lines, n_tagged, n_repaired,
+    path 'device' | 'host', reason, seconds dict(inflate, upload, kernels, download, host)).  The host path, the
+    composition above, is taken with ``force_host`` or VIREO_DONOR_VCF=host and for files whose lines the device
+    cannot vouch for (``reason`` says which).  Without ``force_host`` there is no fallback for a missing GPU."""
+    if force_host or os.environ.get("VIREO_DONOR_VCF") == "host":
+        return _donor_host(vcf_file, tag, variants, biallelic_only, min_prob, "forced")
+    if tag not in _TAG_CODE:
+        return _donor_host(vcf_file, tag, variants, biallelic_only, min_prob, "tag %s has no device grammar" % tag)
+    _lib.require_gpu()
+    from .counts import default_device
+    L = _lib.lib()
+    device = default_device() if device is None else int(device)
+    slab_bytes = _SLAB_BYTES if slab_bytes is None else int(slab_bytes)
+    if not 1 <= slab_bytes <= _SLAB_LIMIT:
+        raise ValueError("slab_bytes must lie in 1 ... %d" % _SLAB_LIMIT)
+    t_all = time.perf_counter()
+    sec = dict(inflate=0.0, upload=0.0, kernels=0.0, download=0.0, host=0.0)
+
+    def host(reason):
+        return _donor_host(vcf_file, tag, variants, biallelic_only, min_prob, reason)
+
+    text = _DonorText(vcf_file, sec)
+    handle = C.c_void_p()
+    try:
+        head = text.header()
+        chrom = [x for x in head if x.startswith(b"#CHROM")]
+        if any(max(x) >= 0x80 for x in chrom) or any(b"\r" in x.rstrip(b"\r\n") for x in head):
+            return host(_status_reason(32))
+        samples = chrom[-1].decode("ascii").rstrip()[1:].split("\t")[9:] if chrom else []
+        S = len(samples)
+        if S == 0:
+            return host("no sample columns")
+        if variants is None:
+            n_ids, blob, off = -1, None, None
+        else:
+            enc = [str(x).encode() for x in variants]
+            n_ids, blob = len(enc), b"".join(enc)
+            off = np.zeros(n_ids + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in enc], out=off[1:])
+        table = 10 ** (-0.1 * np.arange(4096.) - 0.025) if tag == 'PL' else None
+        _lib.check(L.vrx_vcf_create(device, _TAG_CODE[tag], S, int(bool(biallelic_only)), n_ids, blob,
+                                    None if off is None else off.ctypes.data_as(_lib._I64), _lib.dptr(table),
+                                    C.byref(handle)))
+        info = np.zeros(4, dtype=np.int64)
+        t2 = np.zeros(2)
+        status = C.c_int32(0)
+        for mode in ((-1,) if variants is None else (0, 1, 2)):
+            if text is None:                                      # a "chr" retry of match_SNPs: the file once more
+                text = _DonorText(vcf_file, sec)
+                text.header()
+            _lib.check(L.vrx_vcf_begin(handle, mode, C.byref(status)))
+            if status.value:
+                return host(_status_reason(status.value))
+            n_lines = n_tagged = 0
+            parts, repair = [], []
+            for slab in text.slabs(slab_bytes):
+                if len(slab) > _SLAB_LIMIT:
+                    return host("a line of 2 GiB")
+                raw = (C.c_char * len(slab)).from_buffer(slab)
+                _lib.check(L.vrx_vcf_slab(handle, raw, len(slab), info.ctypes.data_as(_lib._I64), _lib.dptr(t2)))
+                sec['upload'] += t2[0]
+                sec['kernels'] += t2[1]
+                if info[3]:
+                    return host(_status_reason(int(info[3])))
+                n_lines += int(info[0])
+                n_tagged += int(info[1])
+                m = int(info[2])
+                if m == 0:
+                    continue
+                rows, slot, line = np.empty((m, S, 3)), np.empty(m, np.int64), np.empty(m, np.int64)
+                flag, span = np.empty(m, np.int32), np.empty((m, 2), np.int64)
+                _lib.check(L.vrx_vcf_rows(handle, _lib.dptr(rows), slot.ctypes.data_as(_lib._I64),
+                                          line.ctypes.data_as(_lib._I64), flag.ctypes.data_as(_lib._I32),
+                                          span.ctypes.data_as(_lib._I64), _lib.dptr(t2)))
+                sec['kernels'] += t2[0]
+                sec['download'] += t2[1]
+                parts.append((rows, slot, line, flag))
+                for r in np.flatnonzero(flag):                    # the text of a flagged row outlives its slab
+                    repair.append((int(slot[r]), bytes(slab[span[r, 0]:span[r, 1]])))
+                del raw
+            text.close()
+            text = None
+            if parts or variants is None:
+                break
+    finally:
+        if text is not None:
+            text.close()
+        if handle:
+            L.vrx_vcf_destroy(handle)
+
+    if parts:
+        rows, slot, line, flag = (np.concatenate([p[k] for p in parts]) for k in range(4))
+    else:
+        rows, slot, line, flag = np.zeros((0, S, 3)), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int32)
+    if variants is not None and len(parts) > 0:
+        order = np.argsort(slot, kind="stable")
+        rows, slot, line, flag = rows[order], slot[order], line[order], flag[order]
+    # the host functions on the flagged lines: FORMAT and the codes in file order (where load_VCF would raise),
+    # the values one row at a time in cell order (where parse_donor_GPb would)
+    codes = {}
+    for where, raw in repair:
+        f = raw.decode("ascii").rstrip().split("\t")
+        codes[where] = _dense_geno([f[9:]], [f[8].split(":")], [tag])[0][tag][0]
+    if repair and flag[0] and len(codes[int(slot[0])]) != S:
+        # parse_donor_GPb sizes its result by the first row, which is not the header's sample count here
+        return host("the first row has %d sample fields for %d samples" % (len(codes[int(slot[0])]), S))
+    if n_lines and n_tagged < 0.1 * n_lines:
+        print('[vireo] Warning: too few variants with tags!', tag + ": " + str(n_tagged))
+    for r in np.flatnonzero(flag):
+        fixed = np.zeros((1, S, 3))
+        _parse_codes_one_by_one([codes[int(slot[r])]], tag, fixed)
+        rows[r] = fixed[0]
+    rows += min_prob
+    rows /= rows.sum(axis=2, keepdims=True)
+    sec['host'] = time.perf_counter() - t_all - sec['inflate'] - sec['upload'] - sec['kernels'] - sec['download']
+    return dict(GPb=rows, samples=samples, keep=slot, line=line, n_lines=n_lines, n_tagged=n_tagged,
+                n_repaired=len(repair), path='device', reason=None, seconds=sec)
 
 
 def match_VCF_samples(VCF_file1, VCF_file2, GT_tag1, GT_tag2):

@@ -22,7 +22,7 @@ from .counts import device_counts
 from . import launch
 from .dist import LocalComm, env_rank_world, make_comm
 from .io_utils import match_donor_VCF, read_cellSNP, read_vartrix, write_donor_id
-from .vcf_utils import (GenoINFO_maker, load_VCF, parse_donor_GPb, read_sparse_GeneINFO,
+from .vcf_utils import (GenoINFO_maker, load_VCF, load_donor_GPb, parse_donor_GPb, read_sparse_GeneINFO,
                         write_VCF)
 from .vireo_base import optimal_match
 from .vireo_wrap import vireo_wrap
@@ -117,6 +117,11 @@ def load_cells(options):
     return dat
 
 
+# how the last donor VCF was read (resolve_donors): path 'device' | 'host', reason, seconds, n_lines, n_tagged,
+# n_repaired of load_donor_GPb; nothing of it is printed
+DONOR_LOAD = {}
+
+
 def _fail(*lines):
     for line in lines:
         print(line)
@@ -136,14 +141,37 @@ def resolve_donors(options, cell_dat):
         _fail("Error: No variants information is loaded, please provide base.vcf.gz")
     print("[vireo] Loading donor VCF file ...")
     tag = options.geno_tag
-    vcf = load_VCF(options.donor_file, biallelic_only=True, sparse=False, format_list=[tag])
-    if vcf['n_SNP_tagged'][0] < 0.1 * len(vcf['GenoINFO'][tag]):
-        _fail("Error: No " + tag + " tag in donor genotype; please try another tag for genotype, e.g., GT",
-              "        %s" % options.donor_file)
-    cell_dat, vcf = match_donor_VCF(cell_dat, vcf)
-    if len(vcf['GenoINFO'][tag]) == 0:
-        _fail("Error: No matching variants found between cell data and donor VCF.")
-    GPb = parse_donor_GPb(vcf['GenoINFO'][tag], tag)
+    if tag in ('GT', 'GP', 'PL'):
+        # the donor file read, matched to the cell variants and converted in one pass on the GPU
+        # (VIREO_DONOR_VCF=host: by the host functions below); the lines are those of load_VCF / match_donor_VCF
+        got = load_donor_GPb(options.donor_file, tag, cell_dat['variants'], biallelic_only=True)
+        DONOR_LOAD.clear()
+        DONOR_LOAD.update({k: got[k] for k in ('path', 'reason', 'seconds', 'n_lines', 'n_tagged', 'n_repaired')})
+        if got['n_tagged'] < 0.1 * got['n_lines']:
+            _fail("Error: No " + tag + " tag in donor genotype; please try another tag for genotype, e.g., GT",
+                  "        %s" % options.donor_file)
+        keep = got['keep']
+        if len(keep) == 0:
+            print("[vireo] warning: no variants matched to donor VCF, please check chr format!")
+        else:
+            print("[vireo] %d out %d variants matched to donor VCF" % (len(keep), len(cell_dat['variants'])))
+        cell_dat['AD'] = cell_dat['AD'][keep, :]
+        cell_dat['DP'] = cell_dat['DP'][keep, :]
+        cell_dat["variants"] = [cell_dat["variants"][x] for x in keep]
+        for k in cell_dat["FixedINFO"]:
+            cell_dat["FixedINFO"][k] = [cell_dat["FixedINFO"][k][x] for x in keep]
+        if len(keep) == 0:
+            _fail("Error: No matching variants found between cell data and donor VCF.")
+        GPb, vcf = got['GPb'], dict(samples=got['samples'])
+    else:               # a tag parse_donor_GPb does not know: the host functions say so
+        vcf = load_VCF(options.donor_file, biallelic_only=True, sparse=False, format_list=[tag])
+        if vcf['n_SNP_tagged'][0] < 0.1 * len(vcf['GenoINFO'][tag]):
+            _fail("Error: No " + tag + " tag in donor genotype; please try another tag for genotype, e.g., GT",
+                  "        %s" % options.donor_file)
+        cell_dat, vcf = match_donor_VCF(cell_dat, vcf)
+        if len(vcf['GenoINFO'][tag]) == 0:
+            _fail("Error: No matching variants found between cell data and donor VCF.")
+        GPb = parse_donor_GPb(vcf['GenoINFO'][tag], tag)
     known = GPb.shape[1]
     if n_donor is None or n_donor == known:       # every donor genotyped: nothing to learn
         n_donor, learn_GT, names = known, False, vcf['samples']
