@@ -433,6 +433,20 @@ typedef uint32_t vrx_u4 __attribute__((ext_vector_type(4)));
 #define VRX_LDS_RING 512  // entries per wave
 constexpr int VRX_RING = VRX_LDS_RING;
 constexpr int VRX_CHUNK = 256;  // entries per refill (64 lanes x 16 B of one LDS-DMA load)
+// Cache policy of the entry stream's LDS-DMA.  Every entry word is read by exactly one wave, once per
+// pass, and the stream is half of what a pass moves: loaded non-temporally it does not displace the
+// slab operand (re-read by every tile) and the partial planes from L2 and the Infinity Cache.
+// Measured at c3: 0.624 -> 0.600 ms per iteration, dense kernels 0.104 -> 0.097 ms
+// (profiles/r07_ab_stream_nt.txt).  -DVRX_STREAM_NT=0 builds the default policy (the A/B).  The slab
+// prefetch never takes it, and neither do the per-slab record loads (bnd_load, rows_load: measured, slower).
+#ifndef VRX_STREAM_NT
+#define VRX_STREAM_NT 1
+#endif
+#if VRX_STREAM_NT
+#define VRX_STREAM_POLICY " nt"
+#else
+#define VRX_STREAM_POLICY ""
+#endif
 // LDS of a pass = one 2-KiB entry ring per wave + the slab; a slab is staged through PF 16-B
 // registers per thread: 16 waves: 32 KiB + 8 x 16 KiB = 160 KiB
 constexpr int VRX_LDS_PF = (160 * 1024 - VRX_LDS_WAVES * VRX_RING * 4) / (VRX_LDS_WAVES * 64 * 16);
@@ -747,7 +761,7 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
         unsigned keep;  // M0 = LDS destination of lane 0; written and restored in one statement
         asm volatile(
             "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+            "global_load_lds_dwordx4 %1, off" VRX_STREAM_POLICY "\n\ts_mov_b32 m0, %0"
             : "=&s"(keep)
             : "v"(gsrc), "s"(dst)
             : "memory");
