@@ -1,0 +1,610 @@
+"""The per-update sweep shared by tests/test_exact_cpu.py (float64 oracle in the device's place) and
+tests/test_gpu_update_exact.py (the device): cases, the two flows, and the judge.
+
+A case names its data, model shape, flags, state, priors, the environment that selects a kernel
+path and what ``DeviceModel.info()`` / ``DeviceCounts.build_info()`` must then report.  Flow A runs
+every update once from the case's state (theta, GT, ID with logLik_ID, ELBO from a given logLik_ID,
+ELBO recomputed); flow B runs whole iterations (theta, GT, ID, ELBO in the reference's order,
+vireo_model.py:257-264, bmm_model.py:183-188) and judges each of their updates from the float64
+state the backend read back in front of it.  A *backend* computes the outputs in float64 -- the
+oracle here, the device in the GPU test; ``distances`` expresses them in the error units of
+tests/exact_np.py.
+"""
+import functools
+from types import SimpleNamespace
+
+import numpy as np
+from scipy.sparse import csc_matrix
+from scipy.stats import entropy
+
+from oracle import vireo_oracle as O
+from tests import exact_np as X
+
+PARTS = ("LB_p", "KL_ID", "KL_GT", "KL_theta")
+EDGE_SHAPES = (1e-3, 0.5, 9.9999999, 10.0, 10.0000001, 1e4, 1e8)   # digamma: recurrence, its switch, pure series
+
+
+# ------------------------------------------------------------------------------------
+# data
+# ------------------------------------------------------------------------------------
+def _draw(N, M, density, depth, seed, top=None):
+    rng = np.random.default_rng(seed)
+    dp = (rng.random((N, M)) < density) * (1 + rng.poisson(depth, (N, M)))
+    if top:
+        dp = np.minimum(dp, top)
+    ad = rng.binomial(dp, rng.choice([0.03, 0.5, 0.96], (N, 1)))
+    return ad, dp
+
+
+def _small():
+    ad, dp = _draw(300, 200, 0.08, 1.0, 1)
+    for m in range(200):                      # every cell has an entry: the fused cell softmax needs it
+        if not dp[:, m].any():
+            dp[m, m], ad[m, m] = 2, 1
+    return ad, dp
+
+
+def _ragged():
+    """empty variants and cells, one variant that covers every cell, one cell that covers every variant"""
+    ad, dp = _draw(400, 300, 0.05, 1.0, 5)
+    rng = np.random.default_rng(6)
+    dp[7, :] = 1 + rng.poisson(2.0, 300)
+    dp[:, 11] = 1 + rng.poisson(2.0, 400)
+    dp[100:120, :] = 0
+    dp[:, 200:230] = 0
+    return rng.binomial(dp, 0.4), dp
+
+
+def _one_beyond():
+    """test_deep_counts_with_one_beyond_pair_words: deep counts, two of them beyond the pair words"""
+    rng = np.random.default_rng(77)
+    N, M = 1300, 700
+    dp = (1 + rng.poisson(40.0, (N, M))) * (rng.random((N, M)) < 0.04)
+    dp[1111, 5] = 2048
+    dp[17, 600] = 5000
+    return rng.binomial(dp, rng.choice([0.02, 0.5, 0.97], (N, 1))), dp
+
+
+def _split():
+    """test_fit_loop_and_stepwise_api_agree_on_split_rows: heavy-tailed rows, cut into pieces"""
+    from vireo_amd import synth                    # (the generator only: host NumPy)
+    return synth.as_scipy(synth.donor_workload(3000, 1500, 6, 0.04, seed=3, skew=(1.5, 1.0)))
+
+
+def _clone():
+    rng = np.random.default_rng(9)
+    N, M = 60, 400
+    dp = rng.poisson(30, (N, M)) * (rng.random((N, M)) < 0.6)
+    af = rng.beta(0.3, 3, (N, 5))
+    return rng.binomial(dp, af[:, rng.integers(0, 5, M)]), dp
+
+
+def _size(N, M):
+    def make():
+        ad, dp = _draw(N, M, 0.3, 2.0, N + M)
+        dp[0, 0] = max(dp[0, 0], 1)
+        return np.minimum(ad, dp), dp
+    return make
+
+
+DATA = {
+    "small": _small,
+    "mid": lambda: _draw(600, 900, 0.05, 1.0, 2),
+    "tiny": lambda: _draw(60, 40, 0.3, 20.0, 5),                # one contracted range: each side inside one slab of 64
+    "many": lambda: O.synth_donor(2600, 2300, 6, 0.03, seed=3),  # several slabs per orientation
+    "ragged": _ragged,
+    "split": _split,
+    "clone": _clone,
+    "depth3": lambda: _draw(600, 900, 0.05, 1.0, 11, top=3),
+    "depth255": lambda: _draw(600, 900, 0.05, 50.0, 12, top=255),
+    "depth2047": lambda: _draw(600, 900, 0.05, 1000.0, 13, top=2047),
+    "depth_beyond": lambda: _draw(600, 900, 0.05, 3000.0, 14),
+    "one_beyond": _one_beyond,
+    "deep": lambda: _draw(200, 150, 0.3, 50.0, 15),             # spreads beyond exp's range
+    "count_free": lambda: _count_free(),
+}
+for _n, _m in ((255, 1), (1, 63), (256, 64), (257, 65), (1025, 257)):
+    DATA["size_%dx%d" % (_n, _m)] = _size(_n, _m)
+
+
+def _count_free():
+    ad, dp = _draw(120, 90, 0.2, 3.0, 16)
+    dp[:28, :] = 0                                  # variants whose theta posterior is their prior
+    return np.minimum(ad, dp), dp
+
+
+@functools.lru_cache(maxsize=None)
+def data(name):
+    ad, dp = DATA[name]()
+    return csc_matrix(ad), csc_matrix(dp)
+
+
+# ------------------------------------------------------------------------------------
+# states and priors
+# ------------------------------------------------------------------------------------
+def _theta_from_shapes(s, s1, s2):
+    s1, s2 = np.asarray(s1, dtype=float), np.asarray(s2, dtype=float)
+    s.sm = np.broadcast_to(s1 + s2, s.mu.shape).copy()
+    s.mu = np.broadcast_to(s1 / (s1 + s2), s.mu.shape).copy()
+
+
+def st_edge_a(s, p, rng):        # T = 8: s1 and s2 walk through the edge values
+    v = np.array(EDGE_SHAPES + (6.5,))
+    _theta_from_shapes(s, v, np.roll(v, 3))
+
+
+def st_edge_b(s, p, rng):        # T = 8: s1 + s2 is (within a rounding) an edge value
+    v = np.array(EDGE_SHAPES + (6.5,))
+    _theta_from_shapes(s, 0.3 * v, v - 0.3 * v)
+
+
+def st_twins(s, p, rng):         # classes 0 and 1 equal, class 2 1e-6 away
+    _theta_from_shapes(s, [7.25, 7.25, 7.25 * (1 + 1e-6)], [41.5, 41.5, 41.5 * (1 + 1e-6)])
+
+
+def st_in_6_7(s, p, rng):        # a shape where a recurrence that stops early shows
+    _theta_from_shapes(s, [6.4, 25.0, 43.5], [43.6, 25.0, 6.5])
+
+
+def st_one_hot_id(s, p, rng):
+    s.ID[:] = 0.0
+    s.ID[np.arange(p.M), rng.integers(0, p.K, p.M)] = 1.0
+
+
+def st_tiny_gt(s, p, rng):
+    s.GT[::3, :, 0] = 1e-300
+    s.GT[::3, :, 1:] = O.unit_sum(s.GT[::3, :, 1:])
+
+
+def st_sharp_gt(s, p, rng):      # confident genotypes on deep data: logLik_ID spreads beyond 745
+    g = rng.integers(0, p.T, (p.N, p.K))
+    s.GT[:] = 0.01 / (p.T - 1)
+    np.put_along_axis(s.GT, g[:, :, None], 0.99, axis=2)
+    s.GT = O.unit_sum(s.GT)
+
+
+def st_random_theta(s, p, rng):
+    s.mu = rng.uniform(0.02, 0.98, s.mu.shape)
+    s.sm = rng.uniform(3.0, 200.0, s.mu.shape)
+
+
+def pr_gt_row(p, rng):
+    return dict(GT_prior=O.unit_sum(rng.random((1, p.K, p.T)) + 0.05))
+
+
+def pr_gt_full(p, rng):
+    return dict(GT_prior=O.unit_sum(rng.random((p.N, p.K, p.T)) + 0.05))
+
+
+def pr_id_vector(p, rng):        # not normalised: the reference keeps it as given (vireo_model.py:118)
+    return dict(ID_prior=(rng.random((1, p.K)) + 0.1) * 1.7)
+
+
+def pr_id_cells(p, rng):
+    return dict(ID_prior=O.unit_sum(rng.random((p.M, p.K)) + 0.05))
+
+
+def pr_theta(p, rng):
+    rows, cols = (1, p.T) if p.kind == "vireo" else (1, p.K)
+    return dict(th1=rng.uniform(0.3, 40.0, (rows, cols)), th2=rng.uniform(0.3, 40.0, (rows, cols)))
+
+
+def pr_theta_rows(p, rng):
+    """per-variant theta priors (ASE mode) with the edge shapes on the count-free variants: the
+    update leaves s1 = prior there"""
+    th1 = rng.uniform(0.3, 40.0, (p.N, p.T))
+    th2 = rng.uniform(0.3, 40.0, (p.N, p.T))
+    v = np.array(EDGE_SHAPES)
+    for i in range(4):           # 4 x 7 = 28 rows: every (s1, s2) offset of the edge list, class by class
+        th1[7 * i:7 * i + 7, :] = v[:, None]
+        th2[7 * i:7 * i + 7, :] = np.roll(v, i + 1)[:, None]
+    th1[:7, 0], th2[:7, 0] = 0.3 * v, v - 0.3 * v       # s1 + s2 an edge value
+    return dict(th1=th1, th2=th2)
+
+
+def pr_bmm_clones(p, rng):       # differs per clone, one row: broadcast over variants (bmm_model.py:92-98)
+    return dict(th1=rng.uniform(0.3, 5.0, (1, p.K)), th2=rng.uniform(0.3, 5.0, (1, p.K)))
+
+
+# ------------------------------------------------------------------------------------
+# the cases
+# ------------------------------------------------------------------------------------
+CASES_A, CASES_B = {}, {}
+
+
+def _case(table, name, data, K=4, T=3, kind="vireo", ase=False, fix=False, learn_gt=True, state=(),
+          prior=(), env=None, balance=None, want=None, seed=0, restarts=1, iters=1, fused_softmax=None):
+    assert name not in table
+    table[name] = SimpleNamespace(name=name, data=data, K=K, T=T, kind=kind, ase=ase, fix=fix,
+                                  learn_gt=learn_gt, state=tuple(state), prior=tuple(prior),
+                                  env=dict(env or {}), balance=balance, want=dict(want or {}), seed=seed,
+                                  restarts=restarts, iters=iters, fused_softmax=fused_softmax)
+
+
+LDS0, LDS1 = {"VIREO_LDS": "0"}, {"VIREO_LDS": "1"}
+ON = dict(lds_variant=True, lds_cell=True)
+OFF = dict(lds_variant=False, lds_cell=False)
+many = lambda v: v > 1                                                    # noqa: E731
+some = lambda v: v > 0                                                    # noqa: E731
+
+
+def _a(*a, **k):
+    _case(CASES_A, *a, **k)
+
+
+def _b(*a, **k):
+    _case(CASES_B, *a, **k)
+
+
+# paths: gather kernels / LDS-resident passes, work-list sizes, one and many contracted ranges
+_a("gather", "mid", K=6, env=LDS0, want=OFF)
+_a("lds", "mid", K=6, env=LDS1, want=dict(ON, cell_form=1, var_form=3))
+for blocks in (1, 16, 1024):
+    _a("blocks%d_one" % blocks, "tiny", K=8, env=dict(LDS1, VIREO_LDS_BLOCKS=str(blocks)),
+       want=dict(ON, ranges_variant=1, ranges_cell=1))
+    _a("blocks%d_many" % blocks, "many", K=6, env=dict(LDS1, VIREO_LDS_BLOCKS=str(blocks)),
+       want=dict(ON, ranges_variant=1, ranges_cell=1) if blocks == 1 else
+       dict(ON, ranges_variant=many, ranges_cell=many))
+for fmt in (0, 1, 2):
+    for lds, tag in ((LDS0, "gather"), (LDS1, "lds")):
+        _a("fmt%d_%s" % (fmt, tag), "mid", K=5, env=dict(lds, VIREO_ENTRY_FMT=str(fmt)),
+           want=dict(ON if lds is LDS1 else OFF, fmt_variant=fmt, fmt_cell=fmt))
+for cf, vf in ((0, 0), (1, 3), (0, 3), (1, 0)):
+    _a("form_c%d_v%d" % (cf, vf), "depth255", K=5,
+       env=dict(LDS1, VIREO_CELL_FORM=str(cf), VIREO_VAR_FORM=str(vf)), want=dict(ON, cell_form=cf, var_form=vf))
+# count depths that choose each form by themselves
+_a("depth3", "depth3", K=5, env=LDS1, want=dict(ON, cell_form=1, var_form=3))
+_a("depth255", "depth255", K=5, env=LDS1, want=dict(ON, cell_form=0, var_form=0))
+_a("depth2047", "depth2047", K=5, env=LDS1, want=dict(ON, cell_form=0, var_form=0))
+_a("depth_beyond", "depth_beyond", K=5, env=LDS1, want=dict(ON, cell_form=1, var_form=3))
+_a("one_beyond", "one_beyond", K=6, env=LDS1, want=dict(ON, cell_form=1, var_form=3))
+_a("balanced", "many", K=6, balance=True,
+   env=dict(LDS1, VIREO_BUILD="device", VIREO_LDS_SPLIT_X10="60"),
+   want=dict(ON, balanced_variant=True, balanced_cell=True, device_built=True))
+_a("build_host", "mid", K=6, env=dict(LDS1, VIREO_BUILD="host"), want=dict(ON, device_built=False))
+_a("build_device", "mid", K=6, env=dict(LDS1, VIREO_BUILD="device"), want=dict(ON, device_built=True))
+# K: padded K % 4, 2 / 4 entries at once, every vrx_cell_softmax<KP>, the K > KP loop
+for K in (1, 2, 3, 4, 5, 8, 9, 16, 17, 33, 64, 70):
+    _a("K%d_gather" % K, "small", K=K, env=LDS0, want=OFF)
+    if K >= 2:                                   # (one column stays on the gather kernels)
+        _a("K%d_lds" % K, "small", K=K, env=LDS1, want=ON)
+for T in (2, 3, 4, 8):
+    _a("T%d_gather" % T, "small", K=4, T=T, env=LDS0, want=OFF)
+    _a("T%d_lds" % T, "small", K=5, T=T, env=LDS1, want=ON)
+# sizes around the wave and the block; empty rows and columns; rows that cover everything
+for n, m in ((255, 1), (1, 63), (256, 64), (257, 65), (1025, 257)):
+    _a("size_%dx%d_gather" % (n, m), "size_%dx%d" % (n, m), K=3, env=LDS0, want=OFF)
+    if min(n, m) >= 63:
+        _a("size_%dx%d_lds" % (n, m), "size_%dx%d" % (n, m), K=3, env=LDS1, want=ON)
+_a("ragged_gather", "ragged", K=7, env=LDS0, want=OFF)
+_a("ragged_lds", "ragged", K=7, env=LDS1, want=ON)
+_a("split_rows", "split", K=6, env=LDS1, want=dict(ON, extra_pieces_cell=some, extra_pieces_variant=some))
+# modes
+_a("ase", "small", K=4, ase=True, state=[st_random_theta], env=LDS0, want=OFF)
+_a("ase_lds", "small", K=4, ase=True, state=[st_random_theta], env=LDS1, want=ON)
+_a("fix_beta_sum", "small", K=4, fix=True, env=LDS0, want=OFF)
+_a("ase_fix_beta_sum", "small", K=4, ase=True, fix=True, env=LDS0, want=OFF)
+# (``step`` runs the update it is asked for whatever learn_GT says: this case holds that the flag
+# changes nothing there.  The W / KL-only variant of the GT kernel runs in every case's ID and ELBO
+# steps; the fit loop with learn_GT off is flow B's fixed_gt)
+_a("fixed_gt", "small", K=4, learn_gt=False, env=LDS0, want=OFF)
+_a("theta_prior", "small", K=4, prior=[pr_theta], env=LDS0, want=OFF)
+_a("gt_prior_row", "small", K=4, prior=[pr_gt_row], env=LDS0, want=OFF)
+_a("gt_prior_full", "small", K=4, prior=[pr_gt_full], env=LDS0, want=OFF)
+_a("gt_prior_full_T4", "small", K=5, T=4, prior=[pr_gt_full], env=LDS1, want=ON)
+_a("id_prior_vector", "small", K=4, prior=[pr_id_vector], env=LDS0, want=OFF)
+_a("id_prior_cells", "small", K=4, prior=[pr_id_cells], env=LDS0, want=OFF)
+_a("id_prior_cells_K17", "small", K=17, prior=[pr_id_cells], env=LDS1, want=ON)
+_a("bmm", "clone", K=5, kind="bmm", state=[st_random_theta], env=LDS0, want=OFF)
+_a("bmm_lds", "clone", K=5, kind="bmm", state=[st_random_theta], env=LDS1, want=ON)
+_a("bmm_clone_priors", "clone", K=5, kind="bmm", state=[st_random_theta], prior=[pr_bmm_clones], env=LDS0, want=OFF)
+_a("bmm_fix_beta_sum", "clone", K=5, kind="bmm", fix=True, state=[st_random_theta], prior=[pr_bmm_clones],
+   env=LDS0, want=OFF)
+_a("bmm_id_prior_K3", "clone", K=3, kind="bmm", state=[st_random_theta], prior=[pr_id_cells], env=LDS1, want=ON)
+# states where the special functions and the softmaxes break
+_a("edge_shapes_a", "small", K=4, T=8, state=[st_edge_a], env=LDS0, want=OFF)
+_a("edge_shapes_b", "small", K=4, T=8, state=[st_edge_b], env=LDS0, want=OFF)
+_a("edge_shapes_prior", "count_free", K=3, T=3, ase=True, prior=[pr_theta_rows], env=LDS0, want=OFF)
+_a("twin_classes", "small", K=4, state=[st_twins], env=LDS0, want=OFF)
+_a("shape_in_6_7", "small", K=4, state=[st_in_6_7], env=LDS0, want=OFF)
+_a("one_hot_id", "small", K=5, state=[st_one_hot_id], env=LDS0, want=OFF)
+_a("one_hot_id_lds", "small", K=5, state=[st_one_hot_id], env=LDS1, want=ON)
+_a("tiny_gt", "small", K=4, state=[st_tiny_gt], env=LDS0, want=OFF)
+_a("underflow_id", "deep", K=4, state=[st_sharp_gt], env=LDS0, want=OFF)
+_a("underflow_gt", "deep", K=4, state=[st_one_hot_id], env=LDS0, want=OFF)
+_a("underflow_lds", "deep", K=4, state=[st_sharp_gt, st_one_hot_id], env=LDS1, want=ON)
+
+# the fit loop's own kernels and fusions
+FUSE1, FUSE0 = {"VIREO_FUSE_SOFTMAX": "1"}, {"VIREO_FUSE_SOFTMAX": "0"}
+# (fused_softmax: whether the cell softmax runs in the cell pass's epilogue -- small gather problems,
+# one restart, K <= 16, no empty or split cell; the GPU test counts the launches of the run)
+_b("fused_softmax", "small", K=4, env=dict(LDS0, **FUSE1), want=OFF, fused_softmax=True)
+_b("separate_softmax", "small", K=4, env=dict(LDS0, **FUSE0), want=OFF, fused_softmax=False)
+_b("fused_softmax_id_prior", "small", K=16, prior=[pr_id_cells], env=dict(LDS0, **FUSE1), want=OFF,
+   fused_softmax=True)
+_b("ride", "small", K=4, iters=2, env=dict(LDS0, VIREO_ELBO_RIDE="1", **FUSE1), want=OFF, fused_softmax=True)
+_b("no_ride", "small", K=4, iters=2, env=dict(LDS0, VIREO_ELBO_RIDE="0", **FUSE1), want=OFF, fused_softmax=True)
+_b("ride_lds", "mid", K=6, iters=2, env=dict(LDS1, VIREO_ELBO_RIDE="1"), want=ON, fused_softmax=False)
+_b("lds_many_ranges", "many", K=6, env=LDS1, want=dict(ON, ranges_variant=many, ranges_cell=many))
+_b("lds_split_rows", "split", K=6, env=LDS1, want=dict(ON, extra_pieces_cell=some, extra_pieces_variant=some))
+_b("T8", "small", K=5, T=8, env=LDS0, want=OFF)
+_b("ase", "small", K=4, ase=True, env=LDS0, want=OFF)
+_b("fix_beta_sum", "small", K=4, fix=True, prior=[pr_theta], env=LDS0, want=OFF)
+_b("fixed_gt", "small", K=4, learn_gt=False, iters=2, env=LDS0, want=OFF)
+_b("gt_prior_full_lds", "small", K=9, prior=[pr_gt_full], env=LDS1, want=ON)
+_b("clone", "clone", K=5, kind="bmm", state=[st_random_theta], iters=2,
+   env=dict(LDS0, VIREO_ELBO_RIDE="1", **FUSE0), want=OFF, fused_softmax=False)
+_b("clone_lds", "clone", K=5, kind="bmm", state=[st_random_theta], prior=[pr_bmm_clones],
+   env=dict(LDS1, VIREO_ELBO_RIDE="0"), want=ON, fused_softmax=False)
+_b("batch3", "mid", K=4, restarts=3, env=LDS1, want=dict(ON, n_batch=3))
+_b("batch3_gather", "small", K=4, restarts=3, iters=2, env=LDS0, want=dict(OFF, n_batch=3))
+
+
+# ------------------------------------------------------------------------------------
+# a case's problem: data, states, priors, exact counts
+# ------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=2)
+def _problem(flow, name):
+    spec = (CASES_A if flow == "A" else CASES_B)[name]
+    AD, DP = data(spec.data)
+    p = SimpleNamespace(spec=spec, AD=AD, DP=DP, N=AD.shape[0], M=AD.shape[1], K=spec.K, T=spec.T,
+                        kind=spec.kind)
+    p.C = X.Counts(AD, DP)
+    rng = np.random.default_rng(1000 + spec.seed)
+    rows, cols = ((p.N if spec.ase else 1), p.T) if p.kind == "vireo" else (p.N, p.K)
+    p.states = []
+    for _ in range(spec.restarts):
+        s = SimpleNamespace(ID=O.unit_sum(rng.random((p.M, p.K))),
+                            GT=O.unit_sum(rng.random((p.N, p.K, p.T))) if p.kind == "vireo" else None)
+        if p.kind == "vireo":   # the constructor's theta (vireo_model.py:84-93, bmm_model.py:70-77)
+            s.mu = np.ones((rows, cols)) * np.linspace(0.01, 0.99, p.T)
+            s.sm = np.full((rows, cols), 50.0)
+        else:
+            s.mu, s.sm = np.full((rows, cols), 0.5), np.full((rows, cols), 30.0)
+        for f in spec.state:
+            f(s, p, rng)
+        p.states.append(s)
+    p.s0 = p.states[0]
+    if p.kind == "vireo":       # default priors: vireo_model.py:107-137, bmm_model.py:87-105
+        g = np.linspace(0.01, 0.99, p.T)[None, :]
+        pri = dict(ID_prior=None, GT_prior=None, th1=g * 50.0, th2=(1 - g) * 50.0)
+    else:
+        pri = dict(ID_prior=None, GT_prior=None, th1=np.ones((1, p.K)), th2=np.ones((1, p.K)))
+    for f in spec.prior:
+        pri.update(f(p, rng))
+    p.pri = SimpleNamespace(**pri)
+    return p
+
+
+def problem_a(name):
+    return _problem("A", name)
+
+
+def problem_b(name):
+    return _problem("B", name)
+
+
+# ------------------------------------------------------------------------------------
+# the exact side
+# ------------------------------------------------------------------------------------
+def _elbo_of(parts):
+    """LB_p - KL_ID - KL_GT - KL_theta (vireo_model.py:248, bmm_model.py:175); units add"""
+    have = [k for k in PARTS if k in parts]
+    val = parts["LB_p"][0] - sum(parts[k][0] for k in have[1:])
+    return val, sum(parts[k][1] for k in have)
+
+
+def exact_a(p):
+    """name -> (value, unit) of every update from the case's state, and the logLik_ID handed to the
+    ELBO (the exact one rounded to float64)"""
+    if getattr(p, "_exact_a", None) is None:
+        c, s, pri, sp = p.C, p.s0, p.pri, p.spec
+        if p.kind == "vireo":
+            out = X.vireo_theta(c, s.ID, s.GT, pri.th1, pri.th2, s.sm, ase=sp.ase, fix_beta_sum=sp.fix)
+            out.update(X.vireo_gt(c, s.ID, s.mu, s.sm, pri.GT_prior, p.T))
+            out.update(X.vireo_loglik(c, s.GT, s.mu, s.sm))
+        else:
+            out = X.bmm_theta(c, s.ID, pri.th1, pri.th2, s.sm, fix_beta_sum=sp.fix)
+            out.update(X.bmm_loglik(c, s.mu, s.sm))
+        out.update(X.id_from_loglik(*out["logLik_ID"], pri.ID_prior, p.K))
+        p.L_given = out["logLik_ID"][0].astype(np.float64)
+        out.update(_exact_parts(p, p.L_given))
+        out["re_logLik_ID"] = out["logLik_ID"]
+        p._exact_a = out
+    return p._exact_a
+
+
+def _exact_parts(p, L):
+    s, pri = p.s0, p.pri
+    if p.kind == "vireo":
+        out = X.vireo_elbo_parts(L, s.ID, s.GT, s.mu, s.sm, pri.ID_prior, pri.GT_prior, pri.th1, pri.th2)
+    else:
+        out = X.bmm_elbo_parts(L, s.ID, s.mu, s.sm, pri.ID_prior, pri.th1, pri.th2)
+    out["ELBO"] = _elbo_of(out)
+    return out
+
+
+# ------------------------------------------------------------------------------------
+# the float64 oracle as a backend
+# ------------------------------------------------------------------------------------
+def oracle_state(p, s):
+    sp, pri = p.spec, p.pri
+    st = SimpleNamespace(n_cell=p.M, n_var=p.N, n_donor=p.K, n_GT=p.T, learn_GT=sp.learn_gt,
+                         learn_theta=True, ASE_mode=sp.ase, fix_beta_sum=sp.fix,
+                         beta_mu=s.mu.copy(), beta_sum=s.sm.copy(), ID_prob=s.ID.copy(),
+                         theta_s1_prior=pri.th1, theta_s2_prior=pri.th2)
+    st.ID_prior = pri.ID_prior if pri.ID_prior is not None else O.unit_sum(np.ones((p.M, p.K)))
+    if p.kind == "vireo":
+        st.GT_prob = s.GT.copy()
+        # (one (1, K, T) slab: spelled out, update_GT_prob sizes its logits by the prior, vireo_model.py:210)
+        st.GT_prior = (np.broadcast_to(pri.GT_prior, s.GT.shape) if pri.GT_prior is not None
+                       else O.unit_sum(np.ones((p.N, p.K, p.T))))
+    return st
+
+
+def _bmm_parts(st, L):
+    """the terms of bmm_model.py:157-175, apart"""
+    s1, s2 = O._shape12(st)
+    return (np.sum(L * st.ID_prob), np.sum(entropy(st.ID_prob, st.ID_prior, axis=-1)), 0.0,
+            O.beta_kl(np.append(s1[:, None, :], s2[:, None, :], axis=1),
+                      np.append(st.theta_s1_prior[:, None, :], st.theta_s2_prior[:, None, :], axis=1)))
+
+
+class OracleBackend:
+    """oracle/vireo_oracle.py's step functions; ``digamma`` may be swapped for the corruption tests"""
+
+    def __init__(self, p):
+        self.p = p
+
+    def _st(self, r=0):
+        return oracle_state(self.p, self.p.states[r])
+
+    def theta(self):
+        st, p = self._st(), self.p
+        (O.vireo_theta_step if p.kind == "vireo" else O.bmm_theta_step)(st, p.AD, p.DP)
+        return st.beta_mu, st.beta_sum
+
+    def gt(self):
+        st = self._st()
+        O.vireo_gt_step(st, self.p.AD, self.p.DP)
+        return st.GT_prob
+
+    def loglik(self, st=None):
+        st, p = st or self._st(), self.p
+        if p.kind == "vireo":
+            return O._cell_loglik(st.GT_prob, *O._psi3(st), p.AD, p.DP)
+        return O.bmm_cell_loglik(st, p.AD, p.DP)
+
+    def id(self):
+        st = self._st()
+        L = self.loglik(st)
+        st.ID_prob = O.softmax_log(L + np.log(st.ID_prior))
+        return L, st.ID_prob
+
+    def parts(self, st, L):
+        return np.array(O.vireo_elbo_parts(st, L) if self.p.kind == "vireo" else _bmm_parts(st, L))
+
+    def elbo(self, L):
+        return self.parts(self._st(), L)
+
+    def elbo_recomputed(self):
+        st = self._st()
+        L = self.loglik(st)
+        return L, self.parts(st, L)
+
+    def run(self, r, n):
+        """n iterations from restart r's state (vireo_model.py:257-264, bmm_model.py:183-188)"""
+        st, p = self._st(r), self.p
+        trace = []
+        for _ in range(n):
+            if p.kind == "vireo":
+                O.vireo_theta_step(st, p.AD, p.DP)
+                if p.spec.learn_gt:
+                    O.vireo_gt_step(st, p.AD, p.DP)
+            else:
+                O.bmm_theta_step(st, p.AD, p.DP)
+            L = self.loglik(st)
+            st.ID_prob = O.softmax_log(L + np.log(st.ID_prior))
+            parts = self.parts(st, L)
+            trace.append(parts[0] - parts[1] - parts[2] - parts[3])
+        return SimpleNamespace(ID=st.ID_prob, GT=getattr(st, "GT_prob", None), mu=st.beta_mu, sm=st.beta_sum,
+                               L=L, trace=np.array(trace), parts=parts)
+
+
+# ------------------------------------------------------------------------------------
+# the flows and the judge
+# ------------------------------------------------------------------------------------
+def _name_parts(out, parts, pre=""):
+    for k, v in zip(PARTS, parts):
+        out[pre + k] = v
+    out[pre + "ELBO"] = parts[0] - parts[1] - parts[2] - parts[3]
+
+
+def run_a(p, be):
+    """every update once, each from the case's state -> name -> float64 result"""
+    exact_a(p)                                   # (fixes the logLik_ID handed to the ELBO)
+    out = {}
+    out["beta_mu"], out["beta_sum"] = be.theta()
+    if p.kind == "vireo":
+        out["GT_prob"] = be.gt()
+    out["logLik_ID"], out["ID_prob"] = be.id()
+    _name_parts(out, be.elbo(p.L_given))
+    out["re_logLik_ID"], parts = be.elbo_recomputed()
+    out["re_LB_p"] = parts[0]
+    if p.kind != "vireo":
+        del out["KL_GT"]
+    return out
+
+
+def distances_a(p, out):
+    ex = dict(exact_a(p))
+    ex["re_LB_p"] = _exact_parts(p, out["re_logLik_ID"])["LB_p"]     # its own logLik_ID is the input
+    return {k: X.distance(np.reshape(v, np.shape(ex[k][0])), *ex[k]) for k, v in out.items()}
+
+
+def run_b(p, be, r=0):
+    """restart r after 1, 2, ... iterations of the fit loop, each run from the case's state: the
+    float64 state, logLik_ID, trace and ELBO parts a backend reads back after each length"""
+    return [be.run(r, n) for n in range(1, p.spec.iters + 1)]
+
+
+def _exact_stages(p, prev, res):
+    """one iteration, every update judged on its own: the exact update of the float64 state the
+    backend itself read back in front of it (as re_LB_p in flow A), so what an earlier update
+    rounded is input here, not error.  prev: the state before the iteration, res: what the backend
+    holds after it.  A backend that cannot read its logLik_ID back (a restart batch) leaves
+    res.L = None: the exact logLik_ID of its state stands in, and its unit is carried into ID_prob
+    (the softmax's rule) and into LB_p (sum of unit(L) * ID_prob)."""
+    c, pri, sp = p.C, p.pri, p.spec
+    if p.kind == "vireo":
+        ex = X.vireo_theta(c, prev.ID, prev.GT, pri.th1, pri.th2, prev.sm, ase=sp.ase, fix_beta_sum=sp.fix)
+        if sp.learn_gt:
+            ex.update(X.vireo_gt(c, prev.ID, res.mu, res.sm, pri.GT_prior, p.T))
+        else:                                     # GT_prob stays, to the bit
+            ex["GT_prob"] = (X.ld(prev.GT), np.zeros(prev.GT.shape))
+        ex.update(X.vireo_loglik(c, res.GT, res.mu, res.sm))
+    else:
+        ex = X.bmm_theta(c, prev.ID, pri.th1, pri.th2, prev.sm, fix_beta_sum=sp.fix)
+        ex.update(X.bmm_loglik(c, res.mu, res.sm))
+    if res.L is None:
+        L, uL = ex.pop("logLik_ID")
+        ex.update(X.id_from_loglik(L, uL, pri.ID_prior, p.K))
+    else:                                         # its own logLik_ID: one rounding of each logit
+        L, uL = X.ld(res.L), 0.0
+        ex.update(X.id_from_loglik(L, X.EPS * np.abs(L), pri.ID_prior, p.K))
+    if p.kind == "vireo":
+        parts = X.vireo_elbo_parts(L, res.ID, res.GT, res.mu, res.sm, pri.ID_prior, pri.GT_prior, pri.th1, pri.th2)
+    else:
+        parts = X.bmm_elbo_parts(L, res.ID, res.mu, res.sm, pri.ID_prior, pri.th1, pri.th2)
+    parts["LB_p"] = (parts["LB_p"][0], parts["LB_p"][1] + np.sum(uL * X.ld(res.ID)))
+    parts["ELBO"] = _elbo_of(parts)
+    ex.update(parts)
+    return ex
+
+
+def distances_b(p, snaps, r=0):
+    """name -> distance in units.  The last iteration's outputs carry their plain names, an earlier
+    one's end in @<iteration>.  ELBO is the entry of the LONGEST run's trace (the one that rode in
+    the next iteration's theta launch), judged from the state the run of that length left; the four
+    parts are those of the last iteration."""
+    prev, out, last = p.states[r], {}, len(snaps) - 1
+    for it, res in enumerate(snaps):
+        ex = _exact_stages(p, prev, res)
+        got = dict(beta_mu=res.mu, beta_sum=res.sm, ID_prob=res.ID, ELBO=snaps[-1].trace[it])
+        if p.kind == "vireo":
+            got["GT_prob"] = res.GT
+        if res.L is not None:
+            got["logLik_ID"] = res.L
+        if it == last:
+            got.update((k, v) for k, v in zip(PARTS, res.parts) if k in ex)
+        for k, v in got.items():
+            u = X.distance(np.reshape(v, np.shape(ex[k][0])), *ex[k])
+            out[k if it == last else "%s@%d" % (k, it)] = u
+        prev = res
+    return out
+
+
+def a_priori(p):
+    """what recursive summation of the longest contracted row or column may lose, in units, plus 16
+    for forming a term: the float64 oracle has to stay inside, or the unit is degenerate"""
+    return p.C.longest + 16

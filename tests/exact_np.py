@@ -1,0 +1,271 @@
+"""One EM update in extended precision, with the error unit of every output.  TEST INFRASTRUCTURE ONLY.
+
+A restatement of the single updates of the reference (vireoSNP 0.5.9; the lines are cited per
+function, relative to the reference tree) in ``np.longdouble`` (eps 1.1e-19): SciPy's sparse
+products run on long-double data, ``digamma`` / ``loggamma`` come from ``mpmath`` at 40 digits, as
+in tests/golden/make_c3_arbiter.py.  Its own rounding is ~5e-4 of float64's, so it can judge a
+float64 kernel to a fraction of one rounding.
+
+The float64 state handed in (what ``DeviceModel.get_state`` / ``get_loglik`` read back) is taken
+as exact input.  Every function returns ``{name: (value, unit)}`` with ``unit`` the size of ONE
+float64 rounding of that output, an absolute number per element:
+
+* a sum of signed terms (beta_sum, the two parts of beta_mu, logLik_ID, every ELBO part):
+  ``EPS * sum|terms|``, from a second pass over the absolute values; the Beta KL counts each
+  lgamma and each (q - 1) * psi on its own;
+* a softmax output p: ``p * (2 * max_k unit(logit[row, k]) + EPS)``  (d p_k = p_k (dz_k - sum_j
+  p_j dz_j), at most 2 max|dz| relative, plus the rounding of the result);
+* a ratio (beta_mu): the relative units of numerator and denominator added.
+
+``distance`` expresses a float64 result in these units; ``held`` is the rule the tests assert.
+"""
+import mpmath
+import numpy as np
+from scipy.sparse import csc_matrix
+
+LD = np.longdouble
+EPS = 2.0 ** -53
+TINY = 1e-290           # below this the suite compares probabilities absolutely (ATOL of the parity tests)
+FACTOR = 4.0            # the margin of tests/test_gpu_postfit_sweep.py: two correct float64 sums
+
+
+def ld(x):
+    return np.asarray(x, dtype=LD)
+
+
+# ------------------------------------------------------------------------------------
+# special functions: mpmath at 40 digits on the distinct arguments
+# ------------------------------------------------------------------------------------
+def _mp(x):
+    """long double -> mpf without loss (two float64 halves)"""
+    hi = float(x)
+    return mpmath.mpf(hi) + mpmath.mpf(float(x - LD(hi)))
+
+
+def _special(fn, v):
+    v = ld(v)
+    u, inv = np.unique(v.ravel(), return_inverse=True)
+    with mpmath.workdps(40):
+        out = np.array([LD(mpmath.nstr(fn(_mp(x)), 30)) for x in u], dtype=LD)
+    return out[inv.ravel()].reshape(v.shape)
+
+
+def psi(v):
+    return _special(mpmath.digamma, v)
+
+
+def lgam(v):
+    return _special(mpmath.loggamma, v)
+
+
+# ------------------------------------------------------------------------------------
+# the count matrices, long double, both orientations
+# ------------------------------------------------------------------------------------
+class Counts:
+    """AD, BD = DP - AD and DP as long-double CSC (N x M) and their transposes (M x N)"""
+
+    def __init__(self, AD, DP):
+        AD, DP = csc_matrix(AD), csc_matrix(DP)
+        BD = csc_matrix(DP - AD)
+
+        def up(X):
+            return csc_matrix((X.data.astype(LD), X.indices, X.indptr), shape=X.shape)
+
+        self.AD, self.BD, self.DP = up(AD), up(BD), up(DP)
+        self.ADt, self.BDt, self.DPt = (up(csc_matrix(X.T)) for X in (AD, BD, DP))
+        self.shape = AD.shape
+        per_cell = np.diff(DP.indptr)
+        per_var = np.diff(csc_matrix(DP.T).indptr)
+        # the longest contracted row or column: the length of the longest sequential sum
+        self.longest = int(max(per_cell.max(initial=0), per_var.max(initial=0)))
+
+
+def shapes(mu, sm):
+    """theta_s1, theta_s2 (vireo_model.py:139-147, bmm_model.py:107-115)"""
+    mu, sm = ld(mu), ld(sm)
+    return mu * sm, (1 - mu) * sm
+
+
+def softmax(L, unit_L, log_prior):
+    """normalize(exp(loglik_amplify(L + log prior))) over the last axis (vireo_model.py:198-199,
+    :218-219, bmm_model.py:153-154; vireo_base.py:44-74) -> (p, unit)"""
+    z = L + log_prior
+    uz = unit_L + EPS * np.abs(log_prior)
+    z = z - z.max(axis=-1, keepdims=True)
+    p = np.exp(z)
+    p = p / p.sum(axis=-1, keepdims=True)
+    return p, p * (2 * uz.max(axis=-1, keepdims=True) + EPS)
+
+
+def _log_prior(prior, n_class):
+    """log of a prior table (None: uniform over the last axis)"""
+    if prior is None:
+        return -np.log(LD(n_class))
+    return np.log(ld(prior))
+
+
+def _rel_entr(p, prior, n_class):
+    """sum of scipy.stats.entropy(p, prior, axis=-1) (vireo_model.py:237-238, bmm_model.py:162):
+    both normalised over the last axis, 0 log 0 = 0.  Terms: p log p and -p log q."""
+    p = ld(p)
+    p = p / p.sum(axis=-1, keepdims=True)
+    if prior is None:
+        logq = np.full(p.shape, -np.log(LD(n_class)), dtype=LD)
+    else:
+        q = ld(prior)
+        logq = np.broadcast_to(np.log(q / q.sum(axis=-1, keepdims=True)), p.shape)
+    m = p > 0
+    a = p[m] * np.log(p[m])
+    b = p[m] * logq[m]
+    return np.sum(a - b), EPS * np.sum(np.abs(a) + np.abs(b))
+
+
+def _beta_kl(s1, s2, q1, q2):
+    """KL(Beta(s1, s2) || Beta(q1, q2)) summed over all entries: beta_entropy with a prior
+    (vireo_base.py:77-127), cross(post, prior) - cross(post, post) -> (value, unit)"""
+    q1, q2 = np.broadcast_to(ld(q1), s1.shape), np.broadcast_to(ld(q2), s1.shape)
+    d1, d2, ds = psi(s1), psi(s2), psi(s1 + s2)
+
+    def cross(a, b):
+        terms = [lgam(a), lgam(b), -lgam(a + b), -(a - 1) * d1, -(b - 1) * d2, (a + b - 2) * ds]
+        return sum(terms), sum(np.abs(t) for t in terms)
+
+    cq, aq = cross(q1, q2)
+    cp, ap = cross(s1, s2)
+    return np.sum(cq - cp), EPS * np.sum(aq + ap)
+
+
+# ------------------------------------------------------------------------------------
+# Vireo (vireoSNP/utils/vireo_model.py)
+# ------------------------------------------------------------------------------------
+def vireo_theta(C, ID, GT, p1, p2, sm_old, ase=False, fix_beta_sum=False):
+    """update_theta_size (vireo_model.py:165-185): s1 = prior + sum (AD @ ID) * GT over donors
+    (ASE mode) or over variants and donors."""
+    ID, GT = ld(ID), ld(GT)
+    A, B = C.AD @ ID, C.BD @ ID
+    ax = 1 if ase else (0, 1)
+    t1 = np.sum(A[:, :, None] * GT, axis=ax).reshape(-1, GT.shape[2])
+    t2 = np.sum(B[:, :, None] * GT, axis=ax).reshape(-1, GT.shape[2])
+    a1 = np.abs(ld(p1)) + np.sum(np.abs(A)[:, :, None] * np.abs(GT), axis=ax).reshape(t1.shape)
+    a2 = np.abs(ld(p2)) + np.sum(np.abs(B)[:, :, None] * np.abs(GT), axis=ax).reshape(t2.shape)
+    s1, s2 = ld(p1) + t1, ld(p2) + t2
+    mu = s1 / (s1 + s2)
+    out = {"beta_mu": (mu, mu * EPS * (a1 / s1 + (a1 + a2) / (s1 + s2)))}
+    if fix_beta_sum:        # vireo_model.py:184: beta_sum stays
+        sm = np.broadcast_to(ld(sm_old), mu.shape)
+        out["beta_sum"] = (sm, EPS * np.abs(sm))
+    else:
+        out["beta_sum"] = (s1 + s2, EPS * (a1 + a2))
+    return out
+
+
+def vireo_gt(C, ID, mu, sm, GT_prior, n_gt):
+    """update_GT_prob (vireo_model.py:204-219)"""
+    ID = ld(ID)
+    A, S = C.AD @ ID, C.DP @ ID
+    B = S - A
+    s1, s2 = shapes(mu, sm)
+    d1, d2, ds = (x[:, None, :] for x in (psi(s1), psi(s2), psi(s1 + s2)))
+    A, B, S = A[:, :, None], B[:, :, None], S[:, :, None]
+    L = A * d1 + B * d2 - S * ds
+    unit = EPS * (A * np.abs(d1) + B * np.abs(d2) + S * np.abs(ds))
+    GT, u = softmax(L, unit, _log_prior(GT_prior, n_gt))
+    return {"GT_prob": (GT, u)}
+
+
+def vireo_loglik(C, GT, mu, sm):
+    """logLik_ID of update_ID_prob / get_ELBO (vireo_model.py:190-196, :227-234): the 3 T
+    transposed products, regrouped as AD' Wa + BD' Wb - DP' Ws (make_c3_arbiter.py)"""
+    GT = ld(GT)
+    s1, s2 = shapes(mu, sm)
+    d = [x[:, None, :] for x in (psi(s1), psi(s2), psi(s1 + s2))]
+    W = [np.sum(GT * x, axis=2) for x in d]
+    Wabs = [np.sum(np.abs(GT) * np.abs(x), axis=2) for x in d]
+    L = C.ADt @ W[0] + C.BDt @ W[1] - C.DPt @ W[2]
+    unit = EPS * (C.ADt @ Wabs[0] + C.BDt @ Wabs[1] + C.DPt @ Wabs[2])
+    return {"logLik_ID": (L, unit)}
+
+
+def id_from_loglik(L, unit_L, ID_prior, n_donor):
+    """the tail of update_ID_prob (vireo_model.py:198-199, bmm_model.py:153-154)"""
+    p, u = softmax(ld(L), unit_L, _log_prior(ID_prior, n_donor))
+    return {"ID_prob": (p, u)}
+
+
+def vireo_elbo_parts(L, ID, GT, mu, sm, ID_prior, GT_prior, p1, p2):
+    """LB_p, KL_ID, KL_GT, KL_theta of get_ELBO (vireo_model.py:236-248)"""
+    L, ID, GT = ld(L), ld(ID), ld(GT)
+    s1, s2 = shapes(mu, sm)
+    t = L * ID
+    return {"LB_p": (np.sum(t), EPS * np.sum(np.abs(t))),
+            "KL_ID": _rel_entr(ID, ID_prior, ID.shape[1]),
+            "KL_GT": _rel_entr(GT, GT_prior, GT.shape[2]),
+            "KL_theta": _beta_kl(s1, s2, p1, p2)}
+
+
+# ------------------------------------------------------------------------------------
+# BinomMixtureVB (vireoSNP/utils/bmm_model.py)
+# ------------------------------------------------------------------------------------
+def bmm_theta(C, ID, p1, p2, sm_old, fix_beta_sum=False):
+    """update_theta_size (bmm_model.py:133-144)"""
+    ID = ld(ID)
+    s1 = C.AD @ ID + ld(p1)
+    s2 = C.BD @ ID + ld(p2)
+    a1 = C.AD @ np.abs(ID) + np.abs(ld(p1))
+    a2 = C.BD @ np.abs(ID) + np.abs(ld(p2))
+    mu = s1 / (s1 + s2)
+    out = {"beta_mu": (mu, mu * EPS * (a1 / s1 + (a1 + a2) / (s1 + s2)))}
+    if fix_beta_sum:        # bmm_model.py:143
+        sm = np.broadcast_to(ld(sm_old), mu.shape)
+        out["beta_sum"] = (sm, EPS * np.abs(sm))
+    else:
+        out["beta_sum"] = (s1 + s2, EPS * (a1 + a2))
+    return out
+
+
+def bmm_loglik(C, mu, sm):
+    """get_E_logLik (bmm_model.py:118-130)"""
+    s1, s2 = shapes(mu, sm)
+    d1, d2, ds = psi(s1), psi(s2), psi(s1 + s2)
+    L = C.ADt @ d1 + C.BDt @ d2 - C.DPt @ ds
+    unit = EPS * (C.ADt @ np.abs(d1) + C.BDt @ np.abs(d2) + C.DPt @ np.abs(ds))
+    return {"logLik_ID": (L, unit)}
+
+
+def bmm_elbo_parts(L, ID, mu, sm, ID_prior, p1, p2):
+    """LB_p, KL_ID, KL_theta of get_ELBO (bmm_model.py:157-175)"""
+    L, ID = ld(L), ld(ID)
+    s1, s2 = shapes(mu, sm)
+    t = L * ID
+    return {"LB_p": (np.sum(t), EPS * np.sum(np.abs(t))),
+            "KL_ID": _rel_entr(ID, ID_prior, ID.shape[1]),
+            "KL_theta": _beta_kl(s1, s2, p1, p2)}
+
+
+# ------------------------------------------------------------------------------------
+# the judge
+# ------------------------------------------------------------------------------------
+def distance(got, exact, unit):
+    """max |got - exact| / unit over the elements; differences below TINY count as none
+    (probabilities that underflow), a difference where the unit is 0 as infinite"""
+    got, exact, unit = ld(got), ld(exact), ld(unit)
+    if got.shape != exact.shape:
+        raise ValueError("shape %s against %s" % (got.shape, exact.shape))
+    if not np.all(np.isfinite(got)):
+        return float("inf")
+    d = np.abs(got - exact)
+    live = d > TINY
+    if not live.any():
+        return 0.0
+    with np.errstate(divide="ignore"):
+        return float(np.max(d[live] / np.broadcast_to(unit, d.shape)[live]))
+
+
+def bound(u_orc):
+    """what a float64 implementation may be away from exact, given the float64 oracle's own
+    distance on the same input: FACTOR x that, and never less than FACTOR roundings"""
+    return FACTOR * max(u_orc, 1.0)
+
+
+def held(u_dev, u_orc):
+    return u_dev <= bound(u_orc)

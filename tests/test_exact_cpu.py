@@ -1,0 +1,243 @@
+"""The per-update harness checked without a GPU: the float64 oracle stands in the device's place.
+
+* On every case of the sweep (tests/exact_cases.py) the oracle's distance from the extended-precision
+  restatement (tests/exact_np.py), in error units, stays inside the a-priori bound of recursive
+  summation -- the longest contracted row or column plus 16.  A unit that were degenerate (too small
+  for honest float64 arithmetic) or a restatement that computed something else would show here.
+* The checker has teeth: results corrupted the way a kernel would be wrong fail the rule the GPU
+  test asserts (``exact_np.held``).
+* On the c1_onestep fixture (values of the real reference) the restatement agrees with the golden
+  values within the same rule.
+"""
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+from scipy.special import betaln, digamma
+
+from oracle import vireo_oracle as O
+from tests import exact_cases as EC
+from tests import exact_np as X
+from tests import gold
+
+
+def _report(tag, name, us, limit):
+    print("%s %-24s limit %6d  " % (tag, name, limit) + "  ".join("%s %.2f" % kv for kv in us.items()))
+
+
+@pytest.mark.parametrize("name", list(EC.CASES_A))
+def test_oracle_stays_within_a_priori_bound_per_update(name):
+    p = EC.problem_a(name)
+    us = EC.distances_a(p, EC.run_a(p, EC.OracleBackend(p)))
+    _report("A", name, us, EC.a_priori(p))
+    for k, u in us.items():
+        assert u <= EC.a_priori(p), (name, k, u)
+
+
+@pytest.mark.parametrize("name", list(EC.CASES_B))
+def test_oracle_through_whole_iterations(name):
+    """the fit loop's flow: every update of every iteration is judged from the float64 state the
+    backend read back in front of it, so the same a-priori bound holds for every output"""
+    p = EC.problem_b(name)
+    for r in range(p.spec.restarts):
+        us = EC.distances_b(p, EC.run_b(p, EC.OracleBackend(p), r), r)
+        _report("B", "%s[%d]" % (name, r), us, EC.a_priori(p))
+        for k, u in us.items():
+            assert u <= EC.a_priori(p), (name, r, k, u)
+
+
+def test_named_states_are_what_they_say():
+    """the underflow cases reach exact zeros in both softmaxes, the one-hot and 1e-300 states hold them"""
+    for name in ("underflow_id", "underflow_gt", "underflow_lds"):
+        p = EC.problem_a(name)
+        be = EC.OracleBackend(p)
+        L, ID = be.id()
+        assert np.ptp(L, axis=1).max() > 745 and (ID == 0).any() and (be.gt() == 0).any()
+    s = EC.problem_a("one_hot_id").s0
+    assert set(np.unique(s.ID)) == {0.0, 1.0} and np.all(s.ID.sum(1) == 1)
+    s = EC.problem_a("tiny_gt").s0
+    assert (s.GT == 1e-300).any() and np.allclose(s.GT.sum(2), 1, rtol=0, atol=4e-16)
+    p = EC.problem_a("edge_shapes_a")
+    s1 = (p.s0.mu * p.s0.sm)[0]
+    assert np.allclose(s1[:7], EC.EDGE_SHAPES, rtol=4e-16, atol=0)
+    assert s1[2] < 10 <= s1[3] < s1[4]
+
+
+def test_units_and_rule():
+    one = np.ones(3)
+    assert X.distance(one + 2 * X.EPS, one, X.EPS * one) == pytest.approx(2.0)
+    assert X.distance(np.array([0.0]), X.ld([1e-320]), X.ld([1e-335])) == 0.0     # both underflowed
+    assert X.distance(np.array([1e-17]), X.ld([0.0]), X.ld([0.0])) == float("inf")
+    assert X.distance(np.array([np.nan]), X.ld([1.0]), X.ld([1.0])) == float("inf")
+    assert X.held(4.0, 0.3) and not X.held(4.1, 0.3) and X.held(39.9, 10.0) and not X.held(40.1, 10.0)
+
+
+# ---------------------------------------------------------------- the checker has teeth
+@pytest.fixture(scope="module")
+def gather():
+    p = EC.problem_a("gather")
+    out = EC.run_a(p, EC.OracleBackend(p))
+    return p, out, EC.distances_a(p, out)
+
+
+def _fails(p, out, u_orc, key, value):
+    u = EC.distances_a(p, dict(out, **{key: value}))[key]
+    print("corrupted %-10s %.3g units against the oracle's %.2f" % (key, u, u_orc[key]))
+    return not X.held(u, u_orc[key])
+
+
+def test_a_dropped_smallest_entry_fails(gather):
+    """(a) the entry with the smallest |term| of one row left out of logLik_ID / of the theta sums"""
+    p, out, u_orc = gather
+    s, k = p.s0, 0
+    # logLik_ID[m, k]: the cell with the most entries; its terms per entry (vireo_model.py:190-196)
+    m = int(np.argmax(np.diff(p.DP.indptr)))
+    rows = p.DP.indices[p.DP.indptr[m]:p.DP.indptr[m + 1]]
+    ad, dp = p.AD[rows, m].toarray().ravel(), p.DP[rows, m].toarray().ravel()
+    s1, s2 = s.mu * s.sm, (1 - s.mu) * s.sm
+    terms = np.sum(s.GT[rows, k, :] * (ad[:, None] * digamma(s1) + (dp - ad)[:, None] * digamma(s2)
+                                       - dp[:, None] * digamma(s1 + s2)), axis=1)
+    t = terms[np.argmin(np.where(terms != 0, np.abs(terms), np.inf))]
+    L = out["logLik_ID"].copy()
+    L[m, k] -= t
+    assert _fails(p, out, u_orc, "logLik_ID", L)
+    # theta: the variant with the most entries; s1[g] loses ad * ID[m, k] * GT[n, k, g] (vireo_model.py:176-179)
+    csr = p.AD.tocsr()
+    n = int(np.argmax(np.diff(csr.indptr)))
+    cells, ad = csr.indices[csr.indptr[n]:csr.indptr[n + 1]], csr.data[csr.indptr[n]:csr.indptr[n + 1]]
+    terms = ad * s.ID[cells, k] * s.GT[n, k, 0]
+    t = terms[np.argmin(np.where(terms != 0, terms, np.inf))]
+    s1, s2 = out["beta_mu"] * out["beta_sum"], (1 - out["beta_mu"]) * out["beta_sum"]
+    s1[0, 0] -= t
+    assert _fails(p, out, u_orc, "beta_mu", s1 / (s1 + s2))
+    assert _fails(p, out, u_orc, "beta_sum", s1 + s2)
+
+
+def series_digamma(x, switch):
+    """digamma for x > 0 the classic way: psi(x) = psi(x + 1) - 1 / x up to x >= switch, then
+    ln x - 1 / (2x) - sum_k B_2k / (2k x^2k) with seven terms"""
+    x = np.array(x, dtype=np.float64)
+    w = np.zeros_like(x)
+    while np.any(x < switch):
+        low = x < switch
+        w[low] += 1.0 / x[low]
+        x[low] += 1.0
+    z = 1.0 / (x * x)
+    y = np.zeros_like(x)
+    for c in (1 / 12, -691 / 32760, 1 / 132, -1 / 240, 1 / 252, -1 / 120, 1 / 12):   # B_14/14 .. B_2/2
+        y = y * z + c
+    return np.log(x) - 0.5 / x - y * z - w
+
+
+def test_b_digamma_recurrence_stopped_early_fails(monkeypatch):
+    """(b) the recurrence stopped at x >= 6 instead of 10: the series' truncation shows (1.6e-13 on
+    a shape in [6, 7)); the same scheme with the switch at 10 is held"""
+    p = EC.problem_a("shape_in_6_7")
+    be = EC.OracleBackend(p)
+    ex = EC.exact_a(p)
+
+    def units():
+        L, ID = be.id()
+        return np.array([X.distance(L, *ex["logLik_ID"]), X.distance(be.gt(), *ex["GT_prob"]),
+                         X.distance(ID, *ex["ID_prob"])])
+
+    u_orc = units()
+    us = {}
+    for switch in (10.0, 6.0):
+        monkeypatch.setattr(O, "digamma", lambda x, s=switch: series_digamma(x, s))
+        us[switch] = units()
+    print("logLik_ID / GT_prob / ID_prob: oracle %s, switch at 10 %s, at 6 %s" % (u_orc, us[10.0], us[6.0]))
+    assert all(X.held(u, o) for u, o in zip(us[10.0], u_orc))
+    # the logits and the genotype posterior show it; the cells' softmax, whose unit is twice the
+    # largest logit's of the row, need not
+    assert not X.held(us[6.0][0], u_orc[0]) and not X.held(us[6.0][1], u_orc[1])
+
+
+def test_c_digamma_of_the_neighbouring_class_fails():
+    """(c) KL_theta with class t + 1's digamma for class t, the two shapes 1e-6 apart (relative)"""
+    p = EC.problem_a("twin_classes")
+    s, pri = p.s0, p.pri
+    u_orc = EC.distances_a(p, EC.run_a(p, EC.OracleBackend(p)))["KL_theta"]
+    s1, s2 = (s.mu * s.sm)[0], ((1 - s.mu) * s.sm)[0]
+    q1, q2 = pri.th1[0], pri.th2[0]
+    assert abs(s1[2] / s1[1] - 1 - 1e-6) < 1e-9
+
+    def kl(d1):                                   # vireo_base.py:96-125
+        d2, ds = digamma(s2), digamma(s1 + s2)
+        cq = betaln(q1, q2) - (q1 - 1) * d1 - (q2 - 1) * d2 + (q1 + q2 - 2) * ds
+        cp = betaln(s1, s2) - (s1 - 1) * d1 - (s2 - 1) * d2 + (s1 + s2 - 2) * ds
+        return np.sum(cq - cp)
+
+    ex = EC.exact_a(p)["KL_theta"]
+    good, bad = digamma(s1), digamma(s1)
+    bad[1] = bad[2]
+    assert X.held(X.distance(kl(good), *ex), u_orc)
+    u = X.distance(kl(bad), *ex)
+    print("KL_theta with the neighbour's digamma: %.3g units against %.2f" % (u, u_orc))
+    assert not X.held(u, u_orc)
+
+
+def test_d_partial_added_twice_fails(gather):
+    """(d) one partial added a second time, scaled by 1e-9"""
+    p, out, u_orc = gather
+    s = p.s0
+    assert _fails(p, out, u_orc, "LB_p", out["LB_p"] + 1e-9 * np.sum(p.L_given[:64] * s.ID[:64]))
+    gt_block = np.sum(s.GT[:43] * (np.log(s.GT[:43]) + np.log(p.T)))      # 43 variants x K = 258 rows
+    assert _fails(p, out, u_orc, "KL_GT", out["KL_GT"] + 1e-9 * gt_block)
+    mu, sm = out["beta_mu"], out["beta_sum"]
+    A = (p.AD @ s.ID)[:256]
+    s1, s2 = mu * sm, (1 - mu) * sm
+    s1 = s1 + 1e-9 * np.sum(A[:, :, None] * s.GT[:256], axis=(0, 1))
+    assert _fails(p, out, u_orc, "beta_mu", s1 / (s1 + s2))
+    assert _fails(p, out, u_orc, "beta_sum", s1 + s2)
+
+
+# ---------------------------------------------------------------- the restatement against the fixture
+def test_exact_functions_agree_with_the_golden_onestep():
+    """c1_onestep holds the real reference's values after each update; the extended-precision
+    functions, fed the fixture's float64 states, land within the rule's distance of them"""
+    g = gold.load("c1_onestep")
+    AD, DP = gold.c1()
+    C = X.Counts(AD, DP)
+    T = g["s0_GT_prob"].shape[2]
+    K = g["s0_ID_prob"].shape[1]
+    grid = np.linspace(0.01, 0.99, T)[None, :]
+    th1, th2 = grid * 50.0, (1 - grid) * 50.0
+
+    def state(pre):
+        return SimpleNamespace(ID=g[pre + "ID_prob"], GT=g[pre + "GT_prob"], mu=g[pre + "beta_mu"],
+                               sm=g[pre + "beta_sum"])
+
+    s0, s1, s2, s3 = (state(x) for x in ("s0_", "s1_", "s2_", "s3_"))
+    ex = {}
+    ex.update(X.vireo_theta(C, s0.ID, s0.GT, th1, th2, s0.sm))
+    ex.update(X.vireo_gt(C, s1.ID, s1.mu, s1.sm, None, T))
+    ex.update(X.vireo_loglik(C, s2.GT, s2.mu, s2.sm))
+    ex.update(X.id_from_loglik(*ex["logLik_ID"], None, K))
+    parts = X.vireo_elbo_parts(g["logLik_ID"], s3.ID, s3.GT, s3.mu, s3.sm, None, None, th1, th2)
+    ex["ELBO"] = EC._elbo_of(parts)
+    ex["ELBO_recompute"] = ex["ELBO"]
+    golden = dict(beta_mu=g["s1_beta_mu"], beta_sum=g["s1_beta_sum"], GT_prob=g["s2_GT_prob"],
+                  logLik_ID=g["logLik_ID"], ID_prob=g["s3_ID_prob"], ELBO=g["ELBO"],
+                  ELBO_recompute=g["ELBO_recompute"])
+    # the oracle on the same inputs (it reproduces the fixture bit for bit: tests/test_oracle_golden.py)
+    st = O.vireo_new(C.shape[1], C.shape[0], K, beta_mu_init=s0.mu.copy(), beta_sum_init=s0.sm.copy(),
+                     ID_prob_init=s0.ID, GT_prob_init=s0.GT)
+    st.ID_prob, st.GT_prob = s0.ID.copy(), s0.GT.copy()
+    O.vireo_theta_step(st, AD, DP)
+    orc = dict(beta_mu=st.beta_mu, beta_sum=st.beta_sum)
+    O.vireo_gt_step(st, AD, DP)
+    orc["GT_prob"] = st.GT_prob
+    orc["logLik_ID"] = O.vireo_id_step(st, AD, DP)
+    orc["ID_prob"] = st.ID_prob
+    orc["ELBO"] = O.vireo_elbo(st, orc["logLik_ID"])
+    orc["ELBO_recompute"] = O.vireo_elbo(st, None, AD, DP)
+    for k, v in golden.items():
+        u_gold = X.distance(np.reshape(v, np.shape(ex[k][0])), *ex[k])
+        u_orc = X.distance(np.reshape(orc[k], np.shape(ex[k][0])), *ex[k])
+        print("c1_onestep %-15s golden %.2f oracle %.2f units" % (k, u_gold, u_orc))
+        assert X.held(u_gold, u_orc), k
+        # (oracle and fixture coincide to the bit, so the line above cannot fail by itself: the
+        # restatement is also held to the rule's bound for an oracle two roundings out, which is
+        # what summing c1's short rows in float64 costs)
+        assert u_gold <= X.bound(2.0), k

@@ -27,6 +27,10 @@ def _prior_rows(P, full_rows):
     return f64(P), full_rows
 
 
+def _destroy_model(handle, counts):
+    _lib.lib().vrx_model_destroy(handle)
+
+
 class DeviceModel:
     def __init__(self, counts, kind, n_donor, n_gt=3, learn_gt=True, learn_theta=True,
                  ase_mode=False, fix_beta_sum=False, n_batch=1):
@@ -44,7 +48,9 @@ class DeviceModel:
                             fix_beta_sum=int(bool(fix_beta_sum)), n_batch=self.R)
         self._h = C.c_void_p()
         _lib.check(_lib.lib().vrx_model_create(counts.handle, C.byref(cfg), C.byref(self._h)))
-        self._fin = weakref.finalize(self, _lib.lib().vrx_model_destroy, self._h)
+        # vrx_model_destroy reads its vrx_problem (device, stream): the finaliser holds ``counts``, so
+        # that a garbage-collection pass that frees both in one go cannot destroy the problem first
+        self._fin = weakref.finalize(self, _destroy_model, self._h, counts)
 
     def close(self):
         self._fin()
