@@ -497,6 +497,43 @@ int vrx_vcf_slab(vrx_vcf* h, const char* text, int64_t n_bytes, int64_t* info /*
 int vrx_vcf_rows(vrx_vcf* h, double* gpb, int64_t* slot, int64_t* line, int32_t* flag, int64_t* span,
                  double* seconds /* 2 */);
 
+/* ---- cell VCF text (vrx_cellvcf.h) ------------------------------------------------------------------
+ * The decompressed text of cellSNP's cells.vcf.gz -> the sparse AD / DP entries of its kept lines: what
+ * load_VCF(sparse=True) (vcf_utils.py:80-159: the line loop, the biallelic filter, FixedINFO),
+ * parse_sample_info (vcf_utils.py:12-57: one FORMAT for all lines, '.' and '.:.:.' are missing calls,
+ * every other sample field is an entry of the cell it stands for) and read_sparse_GeneINFO
+ * (vcf_utils.py:192-205: the text after the last comma of a subfield, '.' -> 0, float()) do one Python
+ * string at a time.  The host inflates the file, reads the header and feeds whole lines in slabs, as for
+ * vrx_vcf_*.
+ * vrx_cellvcf_create: n_sample = the sample columns of the #CHROM line (>= 1).
+ * vrx_cellvcf_format: the FORMAT bytes of the file's first kept line (1 ... 255 bytes; the host reads
+ * that one line) and the positions of the two keys among its ':'-separated names.  Slabs fed before it
+ * must hold no kept line: a kept line then counts as one with another FORMAT.
+ * vrx_cellvcf_slab: n_bytes (< 2^31 - 64) of whole lines; only the last line of the file may lack its
+ * line end.  A line's sample region is cut into segments of vrx_cellvcf_segment() bytes, a wavefront
+ * each; results do not depend on the cut.  info[0] = kept lines, info[1] = entries, info[2] = kept lines
+ * with a value outside the device's grammar, info[3] = status bits: 8 a '#' line, 16 a line with fewer
+ * than 9 fields, 32 a non-ASCII byte or a '\r' not followed by '\n', 64 a kept line with other FORMAT
+ * bytes, 128 a kept line whose sample-field count is not n_sample, 256 an entry with fewer subfields
+ * than FORMAT has names.  With a status the results are void (the caller uses the host functions).
+ * seconds (may be NULL): upload, kernels.
+ * vrx_cellvcf_rows: the slab before it as CSR: indptr (info[0] + 1, within the slab), and per entry in
+ * file order the cell and the values of the two keys ('.' or 1-9 decimal digits); per kept line flag 1 =
+ * some value of the line is outside that grammar or a field is longer than the device walks (the caller
+ * parses the line and overwrites its values: the entry count does not depend on the values), span = the
+ * line's [start, end) bytes in the slab, line end included, off = the positions of its first nine tabs
+ * (the ninth = the end when there is no sample field) and its end after rstrip().  seconds (may be
+ * NULL): download.
+ * vrx_cellvcf_segment: bytes of a sample region per wavefront (a compile-time constant). */
+typedef struct vrx_cellvcf vrx_cellvcf;
+int vrx_cellvcf_create(int device, int32_t n_sample, int32_t biallelic_only, vrx_cellvcf** out);
+void vrx_cellvcf_destroy(vrx_cellvcf* h);
+int32_t vrx_cellvcf_segment(void);
+int vrx_cellvcf_format(vrx_cellvcf* h, const char* fmt, int32_t fmt_len, int32_t key0, int32_t key1);
+int vrx_cellvcf_slab(vrx_cellvcf* h, const char* text, int64_t n_bytes, int64_t* info /* 4 */, double* seconds /* 2 */);
+int vrx_cellvcf_rows(vrx_cellvcf* h, int64_t* indptr, int32_t* cell, int32_t* v0, int32_t* v1, int32_t* flag,
+                     int64_t* span /* [rows][2] */, int32_t* off /* [rows][10] */, double* seconds /* 1 */);
+
 /* ---- timing (bench.py roofline leg) ---------------------------------------------------
  * When enabled, every launch of a pass kernel is bracketed by hipEvents on the model's
  * stream; totals are read back after a sync.  Kernel ids: */

@@ -13,7 +13,7 @@ from . import vireo_base as base
 from . import vireo_model as model
 from .counts import DeviceCounts, device_counts
 from .vcf_utils import load_VCF, match_SNPs, match_VCF_samples, snp_gene_match
-from .io_utils import read_cellSNP, read_vartrix
+from .io_utils import read_cellSNP, read_cellVCF, read_vartrix
 from .vireo_base import (normalize, tensor_normalize, loglik_amplify, get_binom_coeff,
                          binom_coeff_sum, beta_entropy, match, optimal_match, donor_select,
                          genotype_distance, donor_match)
@@ -47,7 +47,7 @@ __all__ = ["__version__", "Vireo", "BinomMixtureVB", "vireo_wrap", "predict_doub
            "predit_ambient", "variant_ELBO_gain", "variant_select", "barcode_entropy",
            "variant_mixture_gain", "VariantMixtures", "VireoBulk", "VireoBulkCohort", "LikRatio_test", "BulkData", "device_bulk",
            "DeviceCounts", "device_counts", "load_VCF", "match_SNPs", "read_cellSNP",
-           "read_vartrix", "normalize", "tensor_normalize", "loglik_amplify", "get_binom_coeff",
+           "read_cellVCF", "read_vartrix", "normalize", "tensor_normalize", "loglik_amplify", "get_binom_coeff",
            "binom_coeff_sum", "beta_entropy", "match", "optimal_match", "donor_select",
            "genotype_distance", "donor_match", "match_VCF_samples", "snp_gene_match", "gene_counts",
            "get_confusion", "vcf", "base", "model"] + list(_POOL)

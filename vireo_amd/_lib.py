@@ -123,6 +123,12 @@ SIGNATURES = {
     "vrx_vcf_begin": (C.c_int, [_P, C.c_int32, _I32]),
     "vrx_vcf_slab": (C.c_int, [_P, C.c_char_p, C.c_int64, _I64, _D]),
     "vrx_vcf_rows": (C.c_int, [_P, _D, _I64, _I64, _I32, _I64, _D]),
+    "vrx_cellvcf_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "vrx_cellvcf_destroy": (None, [_P]),
+    "vrx_cellvcf_segment": (C.c_int32, []),
+    "vrx_cellvcf_format": (C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32]),
+    "vrx_cellvcf_slab": (C.c_int, [_P, C.c_char_p, C.c_int64, _I64, _D]),
+    "vrx_cellvcf_rows": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I64, _I32, _D]),
     "vrx_model_info": (C.c_int, [_P, _I32]),
     "vrx_model_profile": (C.c_int, [_P, C.c_int32]),
     "vrx_model_profile_read": (C.c_int, [_P, _D, _I64]),

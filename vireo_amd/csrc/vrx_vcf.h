@@ -13,6 +13,7 @@
 //                   three unnormalised values of the tag's code written to the row
 // Integers, table entries and one correctly rounded division only: a row is bitwise a function of its line.
 // Whatever is outside the accepted grammar is flagged for the host and never guessed at.
+// vrx_vcf_mark, vrx_vcf_space, vrx_vcf_raw_end and vrx_vcf_nine_tabs also serve the cell VCF kernels (vrx_cellvcf.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -43,6 +44,32 @@ typedef int4 VrxVcfLine;
 
 __device__ __forceinline__ bool vrx_vcf_space(uint8_t c) {  // what str.rstrip() removes, ASCII
     return c == ' ' || (c >= 9 && c <= 13) || (c >= 28 && c <= 31);
+}
+
+// where line `line` of the slab ends: its line end excluded, the last line of a slab may lack one
+__device__ __forceinline__ uint32_t vrx_vcf_raw_end(const uint8_t* b, uint32_t n, const uint32_t* lstart, uint32_t n_lines,
+                                                    uint32_t line) {
+    return line + 1 < n_lines ? lstart[line + 1] - 1 : (b[n - 1] == '\n' ? n - 1 : n);
+}
+
+// the first nine tabs of [s, e) into tp, by a whole wavefront: every step looks at VRX_VCF_CHUNK bytes, one per lane.
+// -> how many were found (at most 9); the same in every lane
+__device__ __forceinline__ uint32_t vrx_vcf_nine_tabs(const uint8_t* b, uint32_t s, uint32_t e, uint32_t lane,
+                                                      uint32_t (&tp)[9]) {
+    uint32_t nt = 0;
+    for (uint32_t base = s; base < e && nt < 9; base += VRX_VCF_CHUNK) {
+        const uint32_t pos = base + lane;
+        unsigned long long m = __ballot(pos < e && b[pos] == '\t');
+        while (m && nt < 9) {
+            const uint32_t p = base + (uint32_t)__builtin_ctzll(m);
+            m &= m - 1;
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+                if (nt == (uint32_t)k) tp[k] = p;
+            ++nt;
+        }
+    }
+    return nt;
 }
 
 // 64-bit FNV-1a, one byte at a time: the cell ids and the ids of the donor lines go through this one function
@@ -171,7 +198,7 @@ __global__ __launch_bounds__(VRX_VCF_BLOCK) void vrx_vcf_lines(const VrxVcfLines
     if (line >= g.n_lines) return;
     const uint8_t* b = g.text;
     const uint32_t s = g.lstart[line];
-    const uint32_t raw_end = line + 1 < g.n_lines ? g.lstart[line + 1] - 1 : (b[g.n - 1] == '\n' ? g.n - 1 : g.n);
+    const uint32_t raw_end = vrx_vcf_raw_end(b, g.n, g.lstart, g.n_lines, line);
     uint32_t e = raw_end;
     while (e > s && vrx_vcf_space(b[e - 1])) --e;
     int32_t kept = 0, tagidx = -1, slot = -1;
@@ -187,19 +214,7 @@ __global__ __launch_bounds__(VRX_VCF_BLOCK) void vrx_vcf_lines(const VrxVcfLines
         }
         // the first nine tabs: every step looks at VRX_VCF_CHUNK bytes, one per lane
         uint32_t tp[9];
-        uint32_t nt = 0;
-        for (uint32_t base = s; base < e && nt < 9; base += VRX_VCF_CHUNK) {
-            const uint32_t pos = base + lane;
-            unsigned long long m = __ballot(pos < e && b[pos] == '\t');
-            while (m && nt < 9) {
-                const uint32_t p = base + (uint32_t)__builtin_ctzll(m);
-                m &= m - 1;
-#pragma unroll
-                for (int k = 0; k < 9; ++k)
-                    if (nt == (uint32_t)k) tp[k] = p;
-                ++nt;
-            }
-        }
+        const uint32_t nt = vrx_vcf_nine_tabs(b, s, e, lane, tp);
         if (nt < 8) {
             st = VRX_VCF_ST_SHORT;
             break;

@@ -1,4 +1,5 @@
-// Donor VCF text on the device: the vrx_vcf_* entries of include/vireo_hip.h on the kernels of vrx_vcf.h.
+// VCF text on the device: the vrx_vcf_* entries of include/vireo_hip.h on the kernels of vrx_vcf.h (donor VCFs) and
+// the vrx_cellvcf_* entries on those of vrx_cellvcf.h (cell VCFs).
 // A handle owns its stream and buffers; nothing here touches a vrx_problem or a vrx_model.
 #include <algorithm>
 #include <chrono>
@@ -7,6 +8,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "vrx_common.h"
+#include "vrx_cellvcf.h"
 #include "vrx_vcf.h"
 
 namespace {
@@ -281,5 +283,273 @@ extern "C" int vrx_vcf_rows(vrx_vcf* h, double* gpb, int64_t* slot, int64_t* lin
         VRX_HIP(hipStreamSynchronize(s));
         if (seconds) seconds[1] += seconds_since(t0);
     }
+    return VRX_OK;
+}
+
+// ---- cell VCF text: the vrx_cellvcf_* entries on the kernels of vrx_cellvcf.h ------------------------------------
+struct vrx_cellvcf {
+    int device = 0;
+    int32_t n_sample = 0, biallelic_only = 1;
+    int32_t n_fmt = 0, key0 = 0, key1 = 0;
+    uint32_t fmt_len = 0;
+    hipStream_t stream = nullptr;
+    DevBuf<uint8_t> fmt;
+    // slab
+    uint32_t n = 0, n_lines = 0;
+    int64_t n_rows = 0, n_entries = 0;
+    DevBuf<uint8_t> text, flag, tmp;
+    DevBuf<uint32_t> lstart, ctl, off;  // ctl: 0 lines of the slab, 1 status, 2 (select count), 3 flagged lines
+    DevBuf<int32_t> kept, ord, nseg, segbase, seg_tabs, seg_entries, tab0, ent0, lineflag;
+    // rows
+    DevBuf<int32_t> cell, v0, v1, rflag, roff;
+    DevBuf<int64_t> indptr, span;
+};
+
+extern "C" int32_t vrx_cellvcf_segment(void) { return VRX_CELLVCF_SEGMENT; }
+
+extern "C" void vrx_cellvcf_destroy(vrx_cellvcf* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->stream) {
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipStreamDestroy(h->stream);
+    }
+    delete h;
+}
+
+extern "C" int vrx_cellvcf_create(int device, int32_t n_sample, int32_t biallelic_only, vrx_cellvcf** out) {
+    VRX_REQUIRE(out, "vrx_cellvcf_create: null argument");
+    VRX_REQUIRE(n_sample >= 1, "vrx_cellvcf_create: n_sample >= 1");
+    if (int e = vrx_use_device("vrx_cellvcf_create", device)) return e;
+    struct Del {
+        void operator()(vrx_cellvcf* h) const { vrx_cellvcf_destroy(h); }
+    };
+    std::unique_ptr<vrx_cellvcf, Del> h(new vrx_cellvcf());
+    h->device = device;
+    h->n_sample = n_sample;
+    h->biallelic_only = biallelic_only != 0;
+    VRX_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    VRX_HIP(h->ctl.alloc(4));
+    VRX_HIP(h->fmt.alloc(VRX_CELLVCF_FORMAT_MAX + 1));
+    VRX_HIP(hipMemsetAsync(h->ctl.p, 0, 4 * sizeof(uint32_t), h->stream));
+    VRX_HIP(hipStreamSynchronize(h->stream));
+    *out = h.release();
+    return VRX_OK;
+}
+
+extern "C" int vrx_cellvcf_format(vrx_cellvcf* h, const char* fmt, int32_t fmt_len, int32_t key0, int32_t key1) {
+    VRX_REQUIRE(h && fmt, "vrx_cellvcf_format: null argument");
+    VRX_REQUIRE(fmt_len >= 1 && fmt_len <= VRX_CELLVCF_FORMAT_MAX, "vrx_cellvcf_format: FORMAT has 1 ... %d bytes",
+                VRX_CELLVCF_FORMAT_MAX);
+    int32_t n_fmt = 1;
+    for (int32_t k = 0; k < fmt_len; ++k) n_fmt += fmt[k] == ':';
+    VRX_REQUIRE(key0 >= 0 && key0 < n_fmt && key1 >= 0 && key1 < n_fmt, "vrx_cellvcf_format: a key outside FORMAT's %d names",
+                n_fmt);
+    VRX_HIP(hipSetDevice(h->device));
+    VRX_HIP(hipMemcpyAsync(h->fmt.p, fmt, (size_t)fmt_len, hipMemcpyHostToDevice, h->stream));
+    VRX_HIP(hipStreamSynchronize(h->stream));
+    h->fmt_len = (uint32_t)fmt_len;
+    h->n_fmt = n_fmt;
+    h->key0 = key0;
+    h->key1 = key1;
+    return VRX_OK;
+}
+
+extern "C" int vrx_cellvcf_slab(vrx_cellvcf* h, const char* text, int64_t n_bytes, int64_t* info, double* seconds) {
+    VRX_REQUIRE(h && info, "vrx_cellvcf_slab: null argument");
+    VRX_REQUIRE(n_bytes >= 0 && n_bytes < ((int64_t)1 << 31) - 64, "vrx_cellvcf_slab: a slab holds fewer than 2^31 - 64 bytes");
+    VRX_REQUIRE(n_bytes == 0 || text, "vrx_cellvcf_slab: null text");
+    VRX_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    info[0] = info[1] = info[2] = info[3] = 0;
+    if (seconds) seconds[0] = seconds[1] = 0.0;
+    h->n = (uint32_t)n_bytes;
+    h->n_lines = 0;
+    h->n_rows = h->n_entries = 0;
+    if (n_bytes == 0) return VRX_OK;
+    const size_t n = (size_t)n_bytes;
+    const size_t n_pad = (n + VRX_VCF_MARK_BYTES - 1) / VRX_VCF_MARK_BYTES * VRX_VCF_MARK_BYTES;
+    auto t0 = std::chrono::steady_clock::now();
+    VRX_HIP(vrx_vcf_reserve(h->text, n_pad + 2 * VRX_VCF_MARK_BYTES));
+    VRX_HIP(vrx_vcf_reserve(h->flag, n_pad + VRX_VCF_MARK_BYTES));
+    VRX_HIP(hipMemcpyAsync(h->text.p, text, n, hipMemcpyHostToDevice, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    if (seconds) seconds[0] = seconds_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    // 1. line starts
+    uint32_t ctl[4] = {0, 0, 0, 0};
+    VRX_HIP(hipMemcpyAsync(h->ctl.p, ctl, sizeof ctl, hipMemcpyHostToDevice, s));
+    const size_t per_block = (size_t)VRX_VCF_BLOCK * VRX_VCF_MARK_BYTES;
+    vrx_vcf_mark<<<(unsigned)((n + per_block - 1) / per_block), VRX_VCF_BLOCK, 0, s>>>(h->text.p, (uint32_t)n, h->flag.p,
+                                                                                        h->ctl.p, h->ctl.p + 1);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(hipMemcpyAsync(ctl, h->ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    const size_t L = ctl[0];
+    if (L * 9 > n + 1) ctl[1] |= VRX_VCF_ST_SHORT;  // (as in vrx_vcf_slab)
+    if (ctl[1]) {
+        info[3] = ctl[1];
+        if (seconds) seconds[1] = seconds_since(t0);
+        return VRX_OK;
+    }
+    h->n_lines = (uint32_t)L;
+    VRX_HIP(vrx_vcf_reserve(h->lstart, L));
+    VRX_HIP(vrx_vcf_reserve(h->kept, L));
+    VRX_HIP(vrx_vcf_reserve(h->ord, L));
+    VRX_HIP(vrx_vcf_reserve(h->nseg, L + 1));
+    VRX_HIP(vrx_vcf_reserve(h->segbase, L + 1));
+    VRX_HIP(vrx_vcf_reserve(h->lineflag, L));
+    VRX_HIP(vrx_vcf_reserve(h->off, L * VRX_CELLVCF_OFFS));
+    size_t t1 = 0, t2 = 0, t3 = 0;
+    hipcub::CountingInputIterator<uint32_t> bytes_it(0);
+    VRX_HIP(hipcub::DeviceSelect::Flagged(nullptr, t1, bytes_it, h->flag.p, h->lstart.p, h->ctl.p + 2, (int)n, s));
+    VRX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, t2, h->kept.p, h->ord.p, (int)L, s));
+    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, h->nseg.p, h->segbase.p, (int)(L + 1), s));
+    VRX_HIP(vrx_vcf_reserve(h->tmp, std::max(t1, std::max(t2, t3))));
+    VRX_HIP(hipcub::DeviceSelect::Flagged(h->tmp.p, t1, bytes_it, h->flag.p, h->lstart.p, h->ctl.p + 2, (int)n, s));
+    // 2. per line
+    VrxCellLinesArgs gl;
+    gl.text = h->text.p;
+    gl.n = (uint32_t)n;
+    gl.lstart = h->lstart.p;
+    gl.n_lines = (uint32_t)L;
+    gl.biallelic_only = h->biallelic_only;
+    gl.fmt = h->fmt.p;
+    gl.fmt_len = h->fmt_len;
+    gl.kept = h->kept.p;
+    gl.nseg = h->nseg.p;
+    gl.off = h->off.p;
+    gl.status = h->ctl.p + 1;
+    VRX_HIP(hipMemsetAsync(h->nseg.p + L, 0, sizeof(int32_t), s));
+    VRX_HIP(hipMemsetAsync(h->lineflag.p, 0, L * sizeof(int32_t), s));
+    vrx_cellvcf_lines<<<(unsigned)((L + VRX_VCF_WAVES - 1) / VRX_VCF_WAVES), VRX_VCF_BLOCK, 0, s>>>(gl);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(hipcub::DeviceScan::InclusiveSum(h->tmp.p, t2, h->kept.p, h->ord.p, (int)L, s));
+    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(h->tmp.p, t3, h->nseg.p, h->segbase.p, (int)(L + 1), s));
+    int32_t n_kept = 0, n_seg = 0;
+    VRX_HIP(hipMemcpyAsync(ctl, h->ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(&n_kept, h->ord.p + (L - 1), sizeof n_kept, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(&n_seg, h->segbase.p + L, sizeof n_seg, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    if (ctl[1]) {
+        h->n_lines = 0;  // (nothing for vrx_cellvcf_rows)
+        info[3] = ctl[1];
+        if (seconds) seconds[1] = seconds_since(t0);
+        return VRX_OK;
+    }
+    // 3. count pass over the segments, 4. scans
+    const size_t G = (size_t)n_seg;
+    VRX_HIP(vrx_vcf_reserve(h->seg_tabs, G + 1));
+    VRX_HIP(vrx_vcf_reserve(h->seg_entries, G + 1));
+    VRX_HIP(vrx_vcf_reserve(h->tab0, G + 1));
+    VRX_HIP(vrx_vcf_reserve(h->ent0, G + 1));
+    VrxCellSegArgs gs;
+    gs.text = h->text.p;
+    gs.off = h->off.p;
+    gs.segbase = h->segbase.p;
+    gs.n_lines = (uint32_t)L;
+    gs.n_seg = (uint32_t)G;
+    gs.n_fmt = (uint32_t)h->n_fmt;
+    gs.key0 = h->key0;
+    gs.key1 = h->key1;
+    gs.seg_tabs = h->seg_tabs.p;
+    gs.seg_entries = h->seg_entries.p;
+    gs.tab0 = h->tab0.p;
+    gs.ent0 = h->ent0.p;
+    gs.cell = gs.v0 = gs.v1 = nullptr;
+    gs.lineflag = h->lineflag.p;
+    gs.status = h->ctl.p + 1;
+    const unsigned seg_blocks = (unsigned)((G + VRX_VCF_WAVES - 1) / VRX_VCF_WAVES);
+    VRX_HIP(hipMemsetAsync(h->seg_tabs.p + G, 0, sizeof(int32_t), s));
+    VRX_HIP(hipMemsetAsync(h->seg_entries.p + G, 0, sizeof(int32_t), s));
+    if (G > 0) {
+        vrx_cellvcf_count<<<seg_blocks, VRX_VCF_BLOCK, 0, s>>>(gs);
+        VRX_HIP(hipGetLastError());
+    }
+    size_t t4 = 0;
+    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t4, h->seg_tabs.p, h->tab0.p, (int)(G + 1), s));
+    VRX_HIP(vrx_vcf_reserve(h->tmp, t4));
+    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(h->tmp.p, t4, h->seg_tabs.p, h->tab0.p, (int)(G + 1), s));
+    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(h->tmp.p, t4, h->seg_entries.p, h->ent0.p, (int)(G + 1), s));
+    int32_t n_ent = 0;
+    VRX_HIP(hipMemcpyAsync(&n_ent, h->ent0.p + G, sizeof n_ent, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    // 5. emit pass, then the kept lines as rows
+    const size_t E = (size_t)n_ent, R = (size_t)n_kept;
+    VRX_HIP(vrx_vcf_reserve(h->cell, E + 1));
+    VRX_HIP(vrx_vcf_reserve(h->v0, E + 1));
+    VRX_HIP(vrx_vcf_reserve(h->v1, E + 1));
+    VRX_HIP(vrx_vcf_reserve(h->indptr, R + 1));
+    VRX_HIP(vrx_vcf_reserve(h->rflag, R + 1));
+    VRX_HIP(vrx_vcf_reserve(h->span, (R + 1) * 2));
+    VRX_HIP(vrx_vcf_reserve(h->roff, (R + 1) * VRX_CELLVCF_OFFS));
+    gs.cell = h->cell.p;
+    gs.v0 = h->v0.p;
+    gs.v1 = h->v1.p;
+    if (G > 0 && E > 0) {
+        vrx_cellvcf_emit<<<seg_blocks, VRX_VCF_BLOCK, 0, s>>>(gs);
+        VRX_HIP(hipGetLastError());
+    }
+    VrxCellRowsArgs gr;
+    gr.n = (uint32_t)n;
+    gr.n_lines = (uint32_t)L;
+    gr.n_seg = (uint32_t)G;
+    gr.n_sample = h->n_sample;
+    gr.lstart = h->lstart.p;
+    gr.kept = h->kept.p;
+    gr.ord = h->ord.p;
+    gr.segbase = h->segbase.p;
+    gr.tab0 = h->tab0.p;
+    gr.ent0 = h->ent0.p;
+    gr.off = h->off.p;
+    gr.lineflag = h->lineflag.p;
+    gr.indptr = h->indptr.p;
+    gr.flag = h->rflag.p;
+    gr.span = h->span.p;
+    gr.roff = h->roff.p;
+    gr.status = h->ctl.p + 1;
+    gr.n_flagged = h->ctl.p + 3;
+    vrx_cellvcf_rows<<<(unsigned)((L + VRX_VCF_BLOCK - 1) / VRX_VCF_BLOCK), VRX_VCF_BLOCK, 0, s>>>(gr);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(hipMemcpyAsync(ctl, h->ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    if (seconds) seconds[1] = seconds_since(t0);
+    h->n_rows = n_kept;
+    h->n_entries = n_ent;
+    info[0] = n_kept;
+    info[1] = n_ent;
+    info[2] = ctl[3];
+    info[3] = ctl[1];
+    return VRX_OK;
+}
+
+extern "C" int vrx_cellvcf_rows(vrx_cellvcf* h, int64_t* indptr, int32_t* cell, int32_t* v0, int32_t* v1, int32_t* flag,
+                                int64_t* span, int32_t* off, double* seconds) {
+    VRX_REQUIRE(h, "vrx_cellvcf_rows: null handle");
+    if (seconds) seconds[0] = 0.0;
+    VRX_REQUIRE(indptr, "vrx_cellvcf_rows: null output");
+    const size_t R = (size_t)h->n_rows, E = (size_t)h->n_entries;
+    VRX_REQUIRE(R == 0 || (flag && span && off), "vrx_cellvcf_rows: null output");
+    VRX_REQUIRE(E == 0 || (cell && v0 && v1), "vrx_cellvcf_rows: null output");
+    if (h->n_lines == 0) {  // an empty slab, or one that ended with a status
+        indptr[0] = 0;
+        return VRX_OK;
+    }
+    VRX_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    auto t0 = std::chrono::steady_clock::now();
+    VRX_HIP(hipMemcpyAsync(indptr, h->indptr.p, (R + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (E > 0) {
+        VRX_HIP(hipMemcpyAsync(cell, h->cell.p, E * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipMemcpyAsync(v0, h->v0.p, E * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipMemcpyAsync(v1, h->v1.p, E * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    if (R > 0) {
+        VRX_HIP(hipMemcpyAsync(flag, h->rflag.p, R * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipMemcpyAsync(span, h->span.p, R * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipMemcpyAsync(off, h->roff.p, R * VRX_CELLVCF_OFFS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    VRX_HIP(hipStreamSynchronize(s));
+    if (seconds) seconds[0] = seconds_since(t0);
     return VRX_OK;
 }

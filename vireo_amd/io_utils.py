@@ -2,20 +2,24 @@
 
 Own implementation of vireoSNP/utils/io_utils.py: read_cellSNP (:42-59), read_vartrix
 (:62-88), match_donor_VCF (:10-39) and write_donor_id (:91-170: donor_ids.tsv,
-summary.tsv, prob_singlet/doublet.tsv.gz, _log.txt).  Output text is formatted exactly like
+summary.tsv, prob_singlet/doublet.tsv.gz, _log.txt); read_cellVCF is the cell VCF of
+``vireo -c cells.vcf.gz`` (vireo.py:112-117) read on the GPU (csrc/vrx_cellvcf.h).  Output text is formatted exactly like
 the reference's so that downstream tools (and users' grep) keep working.
 """
 import gzip
+import os
 import shutil
+import time
 from itertools import combinations
 
 import ctypes as C
 
 import numpy as np
-from scipy.sparse import coo_matrix, csc_matrix
+from scipy.sparse import coo_matrix, csc_matrix, csr_matrix
 
 from . import _lib
-from .vcf_utils import _labels_blob, load_VCF, match_SNPs
+from .vcf_utils import (_DonorText, _SLAB_BYTES, _SLAB_LIMIT, _VCF_STATUS, _labels_blob, _sparse_geno, load_VCF,
+                        match_SNPs, read_sparse_GeneINFO)
 
 
 def _read_mtx_arrays(path, n_threads=0):
@@ -101,6 +105,203 @@ def read_vartrix(alt_mtx, ref_mtx, cell_file, vcf_file=None):
     return dat
 
 
+_CELL_STATUS = _VCF_STATUS + ((64, "a kept line whose FORMAT differs from the first kept line's"),
+                              (128, "a kept line whose sample-field count is not the #CHROM line's"),
+                              (256, "an entry with fewer subfields than FORMAT has names"))
+_STR_SPACE = " \t\n\r\x0b\x0c\x1c\x1d\x1e\x1f"                     # what str.rstrip() removes, ASCII
+_CELL_FORMAT_MAX = 255
+
+
+def _cell_reason(status):
+    return "; ".join(text for bit, text in _CELL_STATUS if status & bit)
+
+
+def _cell_host(vcf_file, biallelic_only, keys, axes, reason):
+    """read_cellVCF as the composition it replaces: load_VCF, read_sparse_GeneINFO"""
+    t0 = time.perf_counter()
+    vcf = load_VCF(vcf_file, biallelic_only=biallelic_only)
+    dat = read_sparse_GeneINFO(vcf['GenoINFO'], keys=keys, axes=axes)
+    for k in ('samples', 'variants', 'FixedINFO', 'contigs', 'comments', 'n_SNP_tagged'):
+        dat[k] = vcf[k]
+    sec = dict(inflate=0.0, upload=0.0, kernels=0.0, download=0.0, host=time.perf_counter() - t0)
+    dat.update(path='host', reason=reason, n_lines=len(vcf['variants']), n_repaired=0, seconds=sec)
+    return dat
+
+
+def _first_kept_format(slab, biallelic_only):
+    """-> (FORMAT bytes of the slab's first kept line or None when it keeps none, why the host path is due or None):
+    the one line of a cell VCF that is split here before the device sees the file"""
+    pos, n = 0, len(slab)
+    while pos < n:
+        end = slab.find(b"\n", pos)
+        end = n if end < 0 else end
+        f = bytes(slab[pos:end]).decode("latin-1").rstrip(_STR_SPACE).split("\t", 9)
+        pos = end + 1
+        if f[0].startswith("#"):
+            return None, _cell_reason(8)
+        if len(f) < 9:
+            return None, _cell_reason(16)
+        if biallelic_only and (len(f[3]) > 1 or len(f[4]) > 1):
+            continue
+        return f[8].encode("latin-1"), None
+    return None, None
+
+
+def _cell_repair(lines, format_list):
+    """the sparse layout (vcf_utils._sparse_geno) of every flagged line, one line at a time: raises the IndexError
+    that load_VCF raises on a short entry"""
+    out = []
+    for raw in lines:
+        f = raw.decode("ascii").rstrip().split("\t")
+        out.append(_sparse_geno([f[9:]], [f[8].split(":")], format_list)[0])
+    return out
+
+
+def read_cellVCF(vcf_file, biallelic_only=True, keys=('AD', 'DP'), axes=(-1, -1), device=None, slab_bytes=None,
+                 force_host=False):
+    """cellSNP's cells.vcf.gz -> the dict the ``vireo`` command takes from ``load_VCF(vcf_file, biallelic_only)``
+    (vcf_utils.py:80-159, parse_sample_info :12-57) and ``read_sparse_GeneINFO`` (:192-205): one float64 CSR matrix
+    (variants x cells) per name in ``keys``, samples, variants, FixedINFO, contigs, comments and n_SNP_tagged, with the
+    same index dtypes, explicit zeros and entry order, from one pass over the text on the GPU (``vrx_cellvcf_*``,
+    csrc/vrx_cellvcf.h).  The host inflates the file and feeds it in slabs of whole lines (``slab_bytes``, default
+    256 MiB); the device finds the lines, the filter, the entries among the sample fields, their cells and the two
+    values; lines with a value outside its grammar ('.' or 1-9 digits after the last comma) come back flagged and
+    their values are parsed here by the host functions; variants and FixedINFO are sliced from the text at the
+    offsets the device returns.  Also returned: path 'device' | 'host', reason, n_lines (kept lines), n_repaired,
+    seconds dict(inflate, upload, kernels, download, host).  The host path, the composition above, is taken with
+    ``force_host`` or VIREO_CELL_VCF=host, for keys / axes other than two keys with axis -1, and for files whose
+    lines the device cannot vouch for (``reason`` says which).  Without ``force_host`` there is no fallback for a
+    missing GPU."""
+    keys, axes = list(keys), list(axes)
+
+    def host(reason):
+        return _cell_host(vcf_file, biallelic_only, keys, axes, reason)
+
+    if force_host or os.environ.get("VIREO_CELL_VCF") == "host":
+        return host("forced")
+    if len(keys) != 2 or axes != [-1, -1]:
+        return host("the device reads two keys with axis -1")
+    _lib.require_gpu()
+    from .counts import default_device
+    L = _lib.lib()
+    device = default_device() if device is None else int(device)
+    slab_bytes = _SLAB_BYTES if slab_bytes is None else int(slab_bytes)
+    if not 1 <= slab_bytes <= _SLAB_LIMIT:
+        raise ValueError("slab_bytes must lie in 1 ... %d" % _SLAB_LIMIT)
+    t_all = time.perf_counter()
+    sec = dict(inflate=0.0, upload=0.0, kernels=0.0, download=0.0, host=0.0)
+    text = _DonorText(vcf_file, sec)
+    handle = C.c_void_p()
+    try:
+        head = text.header()
+        for raw in head:                                          # the '#' lines as load_VCF's text layer sees them
+            core = raw[:-2] if raw.endswith(b"\r\n") else raw.rstrip(b"\n")
+            if b"\r" in core or (raw and max(raw) >= 0x80):
+                return host(_cell_reason(32))
+        fixed, fkeys, contigs, comments, samples = {}, [], [], [], []
+        for raw in head:
+            line = raw.decode("ascii").rstrip()
+            if line.startswith("##contig="):
+                contigs.append(line)
+            if line.startswith("#CHROM"):
+                cols = line[1:].split("\t")
+                fkeys = cols[:8]
+                fixed = {k: [] for k in fkeys}
+                samples = cols[9:]
+            else:
+                comments.append(line)
+        S = len(samples)
+        if S == 0:
+            return host("no sample columns")
+        _lib.check(L.vrx_cellvcf_create(device, S, int(bool(biallelic_only)), C.byref(handle)))
+        info = np.zeros(4, dtype=np.int64)
+        t2 = np.zeros(2)
+        fmt = format_list = None
+        variants, repair = [], []
+        p_indptr, p_cell, p_v0, p_v1 = [], [], [], []
+        n_entries = 0
+        for slab in text.slabs(slab_bytes):
+            if len(slab) > _SLAB_LIMIT:
+                return host("a line of 2 GiB")
+            if fmt is None:
+                fmt, why = _first_kept_format(slab, biallelic_only)
+                if why is not None:
+                    return host(why)
+                if fmt is not None:
+                    format_list = fmt.decode("latin-1").split(":")
+                    if not 1 <= len(fmt) <= _CELL_FORMAT_MAX:
+                        return host("a FORMAT of %d bytes" % len(fmt))
+                    if keys[0] not in format_list or keys[1] not in format_list:
+                        return host("FORMAT does not name the keys")
+                    _lib.check(L.vrx_cellvcf_format(handle, fmt, len(fmt), format_list.index(keys[0]),
+                                                    format_list.index(keys[1])))
+            raw = (C.c_char * len(slab)).from_buffer(slab)
+            _lib.check(L.vrx_cellvcf_slab(handle, raw, len(slab), info.ctypes.data_as(_lib._I64), _lib.dptr(t2)))
+            del raw
+            sec['upload'] += t2[0]
+            sec['kernels'] += t2[1]
+            if info[3]:
+                return host(_cell_reason(int(info[3])))
+            R, E = int(info[0]), int(info[1])
+            if R == 0:
+                continue
+            indptr, flag = np.empty(R + 1, np.int64), np.empty(R, np.int32)
+            span, off = np.empty((R, 2), np.int64), np.empty((R, 10), np.int32)
+            cell, v0, v1 = np.empty(E, np.int32), np.empty(E, np.int32), np.empty(E, np.int32)
+            _lib.check(L.vrx_cellvcf_rows(handle, indptr.ctypes.data_as(_lib._I64), cell.ctypes.data_as(_lib._I32),
+                                          v0.ctypes.data_as(_lib._I32), v1.ctypes.data_as(_lib._I32),
+                                          flag.ctypes.data_as(_lib._I32), span.ctypes.data_as(_lib._I64),
+                                          off.ctypes.data_as(_lib._I32), _lib.dptr(t2)))
+            sec['download'] += t2[0]
+            assert indptr[0] == 0 and indptr[R] == E
+            for r in np.flatnonzero(flag):                        # the text of a flagged line outlives its slab
+                repair.append((len(variants) + int(r), bytes(slab[span[r, 0]:span[r, 1]])))
+            start, tab7 = span[:, 0].tolist(), off[:, 7].tolist()
+            for r in range(R):                                    # CHROM ... INFO: the text in front of the eighth tab
+                f = slab[start[r]:tab7[r]].decode("ascii").split("\t")
+                for k, v in zip(fkeys, f):
+                    fixed[k].append(v)
+                variants.append("_".join((f[0], f[1], f[3], f[4])))
+            p_indptr.append(indptr[:-1] + n_entries)
+            p_cell.append(cell)
+            p_v0.append(v0)
+            p_v1.append(v1)
+            n_entries += E
+    finally:
+        text.close()
+        if handle:
+            L.vrx_cellvcf_destroy(handle)
+
+    n_var = len(variants)
+    if n_var == 0:
+        return host("no kept lines")
+    indptr = np.concatenate(p_indptr + [np.array([n_entries], dtype=np.int64)])
+    indices = np.concatenate(p_cell).astype(np.int64)
+    data = [np.concatenate(p).astype(np.float64) for p in (p_v0, p_v1)]
+    # the host functions on the flagged lines, in the order in which the composition meets them: the sparse layout of
+    # every line (where load_VCF would raise), the tag warning, then the values one key at a time (where
+    # read_sparse_GeneINFO would)
+    try:
+        layouts = _cell_repair([raw for _, raw in repair], format_list)
+    except IndexError:
+        return host("a flagged line with a short entry")
+    for (r, _), geno in zip(repair, layouts):
+        if geno['indices'] != indices[indptr[r]:indptr[r + 1]].tolist():
+            return host("a flagged line the host reads differently")
+    if n_entries < 0.1 * n_var:
+        print('[vireo] Warning: too few variants with tags!',
+              '\t'.join(k + ": " + str(n_entries) for k in format_list))
+    for key, values in zip(keys, data):
+        for (r, _), geno in zip(repair, layouts):
+            values[indptr[r]:indptr[r + 1]] = read_sparse_GeneINFO(geno, keys=[key], axes=[-1])[key].data
+    dat = {key: csr_matrix((values, indices, indptr), shape=(n_var, S)) for key, values in zip(keys, data)}
+    sec['host'] = time.perf_counter() - t_all - sec['inflate'] - sec['upload'] - sec['kernels'] - sec['download']
+    dat.update(samples=samples, variants=variants, FixedINFO=fixed, contigs=contigs, comments=comments,
+               n_SNP_tagged=np.full(len(format_list), n_entries, dtype=np.int64), path='device', reason=None,
+               n_lines=n_var, n_repaired=len(repair), seconds=sec)
+    return dat
+
+
 def match_donor_VCF(cell_dat, donor_vcf):
     """keep the variants present in both the cell data and the donor VCF, in cell order
     (io_utils.py:10-39)."""
@@ -128,7 +329,6 @@ def match_donor_VCF(cell_dat, donor_vcf):
 def _gzip_file(path):
     with open(path, "rb") as src, gzip.open(path + ".gz", "wb") as dst:
         shutil.copyfileobj(src, dst)
-    import os
     os.remove(path)
 
 

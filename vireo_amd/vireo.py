@@ -5,8 +5,9 @@ registered as ``vireo`` in setup.py:53-55):
 
     python -m vireo_amd.vireo -c CELL_DATA -N n_donor -o OUT_DIR [-d DONOR_VCF] ...
 
-The model fits run on the GPU (vireo_amd.vireo_wrap); loading and writing text files is
-host work.  ``--callAmbientRNAs`` (vireo.py:79-81) runs the per-cell ambient-RNA EM on the GPU
+The model fits run on the GPU (vireo_amd.vireo_wrap), and so do the passes over the text of a
+cell VCF (read_cellVCF) and of the donor VCF (load_donor_GPb); the other text files are host
+work.  ``--callAmbientRNAs`` (vireo.py:79-81) runs the per-cell ambient-RNA EM on the GPU
 and writes prop_ambient.tsv.  Not carried over: the genotype-distance figure (``--noPlot`` is
 accepted and is the only behaviour).
 """
@@ -17,13 +18,12 @@ from optparse import OptionParser, OptionGroup
 
 import numpy as np
 
-from . import __version__
+from . import __version__, _lib
 from .counts import device_counts
 from . import launch
 from .dist import LocalComm, env_rank_world, make_comm
-from .io_utils import match_donor_VCF, read_cellSNP, read_vartrix, write_donor_id
-from .vcf_utils import (GenoINFO_maker, load_VCF, load_donor_GPb, parse_donor_GPb, read_sparse_GeneINFO,
-                        write_VCF)
+from .io_utils import match_donor_VCF, read_cellSNP, read_cellVCF, read_vartrix, write_donor_id
+from .vcf_utils import GenoINFO_maker, load_VCF, load_donor_GPb, parse_donor_GPb, write_VCF
 from .vireo_base import optimal_match
 from .vireo_wrap import vireo_wrap
 
@@ -92,6 +92,14 @@ def build_parser():
     return parser
 
 
+def _device_visible():
+    """a HIP device this process can use; a library that is not built, or a host-only build of it, has none"""
+    try:
+        return _lib.device_count() > 0
+    except (AttributeError, _lib.VrxError):
+        return False
+
+
 def load_cells(options):
     """cellSNP folder, cell VCF or vartrix triplet (vireo.py:108-133)"""
     if options.cell_data is None and options.vartrix_data is None:
@@ -110,12 +118,21 @@ def load_cells(options):
         print("[vireo] Loading cell folder ...")
         return read_cellSNP(options.cell_data)
     print("[vireo] Loading cell VCF file ...")
-    vcf = load_VCF(options.cell_data, biallelic_only=True)
-    dat = read_sparse_GeneINFO(vcf['GenoINFO'], keys=['AD', 'DP'])
-    for k in ('samples', 'variants', 'FixedINFO', 'contigs', 'comments'):
-        dat[k] = vcf[k]
-    return dat
+    # the lines, the filter and the sparse AD / DP entries in one pass over the text on the GPU (VIREO_CELL_VCF=host:
+    # by load_VCF and read_sparse_GeneINFO, which read_cellVCF composes).  Loading cell data has never needed a GPU
+    # (the fits do, and say so): where none is visible the host functions run, and CELL_LOAD says why
+    no_gpu = not _device_visible()
+    got = read_cellVCF(options.cell_data, biallelic_only=True, keys=['AD', 'DP'], force_host=no_gpu)
+    CELL_LOAD.clear()
+    CELL_LOAD.update({k: got[k] for k in ('path', 'reason', 'seconds', 'n_lines', 'n_repaired')})
+    if no_gpu:
+        CELL_LOAD['reason'] = "no HIP device is visible"
+    return {k: got[k] for k in ('AD', 'DP', 'samples', 'variants', 'FixedINFO', 'contigs', 'comments')}
 
+
+# how the last cell VCF was read (load_cells): path 'device' | 'host', reason, seconds, n_lines, n_repaired of
+# read_cellVCF; nothing of it is printed
+CELL_LOAD = {}
 
 # how the last donor VCF was read (resolve_donors): path 'device' | 'host', reason, seconds, n_lines, n_tagged,
 # n_repaired of load_donor_GPb; nothing of it is printed
