@@ -1,4 +1,5 @@
-"""One EM update in extended precision, with the error unit of every output.  TEST INFRASTRUCTURE ONLY.
+"""One EM update or post-fit step in extended precision, with the error unit of every output.
+TEST INFRASTRUCTURE ONLY.
 
 A restatement of the single updates of the reference (vireoSNP 0.5.9; the lines are cited per
 function, relative to the reference tree) in ``np.longdouble`` (eps 1.1e-19): SciPy's sparse
@@ -17,11 +18,17 @@ float64 rounding of that output, an absolute number per element:
   p_j dz_j), at most 2 max|dz| relative, plus the rounding of the result);
 * a ratio (beta_mu): the relative units of numerator and denominator added.
 
+The steps on a fitted model (``cell_loglik``, ``doublet``, ``donor_reads``) and one variant's own
+mixture (``varmix_row``, a chain whose intermediate state cannot be read back: there the rounding
+of one stage is carried into the next as a unit) follow the same conventions; their cases are in
+tests/exact_postfit.py.
+
 ``distance`` expresses a float64 result in these units; ``held`` is the rule the tests assert.
 """
 import mpmath
 import numpy as np
 from scipy.sparse import csc_matrix
+from scipy.special import polygamma
 
 LD = np.longdouble
 EPS = 2.0 ** -53
@@ -240,6 +247,108 @@ def bmm_elbo_parts(L, ID, mu, sm, ID_prior, p1, p2):
     return {"LB_p": (np.sum(t), EPS * np.sum(np.abs(t))),
             "KL_ID": _rel_entr(ID, ID_prior, ID.shape[1]),
             "KL_theta": _beta_kl(s1, s2, p1, p2)}
+
+
+# ------------------------------------------------------------------------------------
+# the steps on a fitted model (vireoSNP/utils/vireo_doublet.py, vireoSNP/vireo.py:240-241)
+# ------------------------------------------------------------------------------------
+def cell_loglik(C, GT, psi1, psi2, psis, ID_prior):
+    """vireo_doublet.py:53-68 against a given (n_var, n_col, n_class) genotype table: the 3 n_class
+    transposed products, regrouped as in ``vireo_loglik``, and the posterior with ``ID_prior``
+    (None: uniform; else 1 or n_cell rows).  psi*: the caller's float64 tables, (1 | n_var, n_class)."""
+    GT = ld(GT)
+    d = [ld(x)[:, None, :] for x in (psi1, psi2, psis)]
+    W = [np.sum(GT * x, axis=2) for x in d]
+    Wabs = [np.sum(np.abs(GT) * np.abs(x), axis=2) for x in d]
+    L = C.ADt @ W[0] + C.BDt @ W[1] - C.DPt @ W[2]
+    unit = EPS * (C.ADt @ Wabs[0] + C.BDt @ Wabs[1] + C.DPt @ Wabs[2])
+    p, u = softmax(L, unit, _log_prior(ID_prior, GT.shape[1]))
+    return {"logLik": (L, unit), "prob": (p, u)}
+
+
+def doublet_table(GT):
+    """add_doublet_GT (vireo_doublet.py:105-136) in long double: the singlet columns padded with
+    zero mixed classes, then every donor pair (itertools.combinations order) over the T same and
+    the T (T - 1) / 2 mixed classes, normalised over the classes"""
+    GT = ld(GT)
+    N, K, T = GT.shape
+    a, b = np.triu_indices(K, 1)             # (row-major: the order of combinations)
+    g1, g2 = np.triu_indices(T, 1)
+    P, Q = GT[:, a, :], GT[:, b, :]
+    both = np.concatenate([P * Q, P[:, :, g1] * Q[:, :, g2] + P[:, :, g2] * Q[:, :, g1]], axis=2)
+    both = both / both.sum(axis=2, keepdims=True)
+    single = np.concatenate([GT, np.zeros((N, K, g1.size), dtype=LD)], axis=2)
+    return np.concatenate([single, both], axis=1)
+
+
+def doublet(C, GT, psi1, psi2, psis, prior_both):
+    """predict_doublet's logLik_ID and posterior (vireo_doublet.py:11-68) from the fitted GT_prob,
+    the digamma tables of add_doublet_theta's classes and the prior of all K + K (K - 1) / 2 columns
+    (None: uniform)"""
+    return cell_loglik(C, doublet_table(GT), psi1, psi2, psis, prior_both)
+
+
+def donor_reads(C, ID):
+    """AD @ ID_prob and DP @ ID_prob (vireo.py:240-241)"""
+    ID = ld(ID)
+    absID = np.abs(ID)
+    return {"AD_reads": (C.AD @ ID, EPS * (C.AD @ absID)), "DP_reads": (C.DP @ ID, EPS * (C.DP @ absID))}
+
+
+# ------------------------------------------------------------------------------------
+# one variant's own mixture (BinomMixtureVB._fit_BV on a 1 x n_cell row, bmm_model.py:178-201)
+# ------------------------------------------------------------------------------------
+def varmix_row(ad, dp, K, n_iter):
+    """The protocol of tests/varmix_np.fit_row on the covered cells of one row: the deterministic
+    start, then ``n_iter`` iterations of theta -> logits -> softmax -> ELBO.  -> (list of
+    {ELBO, beta_mu, beta_sum, size} per iteration, elbo_one), every entry (value, unit).
+
+    No intermediate state of a fit can be read back, so what one stage rounds is carried into the
+    next as a unit: u(ID_ik) = ID_ik (2 max_k unit(L_ik) + EPS) (the softmax's rule; 3 EPS ID for the
+    start values, three roundings), into size_k as sum_i u(ID_ik), into the sums of the next theta
+    as sum_i a_i u(ID_ik), and from those sums into the logits as a_i psi'(s1_k) u(s1_k) + ... (on a
+    row with a few cells of 1e6 reads the float64 restatement is 870 units out in ``size`` without
+    this last term: the deep cells' rounding moves a component's shapes, and those every cell's
+    logits)."""
+    ad, dp = np.asarray(ad), np.asarray(dp)
+    cov = dp > 0
+    a, d = ld(ad[cov]), ld(dp[cov])
+    b = d - a
+    f = a / d
+    c = ld(np.arange(K)) / LD(K - 1)
+    ID = np.maximum(LD(0), 1 - np.abs(f[:, None] - c[None, :]) * LD(K - 1)) + LD(1) / 64
+    ID = ID / ID.sum(axis=1, keepdims=True)
+    ID = ID / ID.sum(axis=1, keepdims=True)          # set_initial normalises once more (bmm_model.py:80-81)
+    uID = 3 * EPS * ID
+    out = []
+    for _ in range(n_iter):
+        s1, s2 = 1 + a @ ID, 1 + b @ ID              # update_theta_size (:133-144)
+        u1 = EPS * s1 + a @ uID
+        u2 = EPS * s2 + b @ uID
+        mu = s1 / (s1 + s2)
+        d1, d2, ds = psi(s1), psi(s2), psi(s1 + s2)
+        L = a[:, None] * d1 + b[:, None] * d2 - d[:, None] * ds      # get_E_logLik (:118-130)
+        uL = EPS * (a[:, None] * np.abs(d1) + b[:, None] * np.abs(d2) + d[:, None] * np.abs(ds))
+        # (what the sums carry moves the digammas: psi'(s) u(s), a float64 trigamma is plenty for a unit)
+        t1, t2, ts = (ld(polygamma(1, np.asarray(x, dtype=np.float64))) for x in (s1, s2, s1 + s2))
+        uL = uL + a[:, None] * (t1 * u1) + b[:, None] * (t2 * u2) + d[:, None] * (ts * (u1 + u2))
+        ID, uID = softmax(L, uL, -np.log(LD(K)))     # update_ID_prob (:147-154)
+        lb = L * ID
+        m = ID > 0
+        ent = np.zeros(ID.shape, dtype=LD)
+        ent[m] = ID[m] * np.log(ID[m] * K)
+        kl, ukl = _beta_kl(s1, s2, 1.0, 1.0)
+        out.append({"ELBO": (np.sum(lb) - np.sum(ent) - kl,
+                             EPS * (np.sum(np.abs(lb)) + np.sum(np.abs(ent))) + ukl),
+                    "beta_mu": (mu, mu * (u1 / s1 + (u1 + u2) / (s1 + s2))),
+                    "beta_sum": (s1 + s2, u1 + u2),
+                    "size": (ID.sum(axis=0), EPS * ID.sum(axis=0) + uID.sum(axis=0))})
+    ta, tb = a.sum(), b.sum()                        # exact integers
+    s1, s2 = np.array([1 + ta]), np.array([1 + tb])
+    terms = [ta * psi(s1)[0], tb * psi(s2)[0], -(ta + tb) * psi(s1 + s2)[0]]
+    kl, ukl = _beta_kl(s1, s2, 1.0, 1.0)
+    one = (sum(terms) - kl, EPS * sum(abs(t) for t in terms) + ukl)
+    return out, one
 
 
 # ------------------------------------------------------------------------------------
