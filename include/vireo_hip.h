@@ -304,6 +304,9 @@ int vrx_bulk_fit_cohort(vrx_bulk* b, double* psi_io /* n_sample x n_donor */, do
  * its own theta and counts (LikRatio_test for a whole cohort in one pass per eight vectors). */
 int vrx_bulk_loglik_cohort(vrx_bulk* b, int64_t n_psi, const double* psi /* n_sample x n_psi x n_donor */,
                            const double* theta /* n_sample x n_gt */, double* out /* n_sample x n_psi */);
+/* Variants per tile and workgroups of the four passes, as the handle launches them: T, n_wg (fit), T_ll,
+ * n_wg_ll (log-likelihood), T_co, n_wg_co, T_co_ll, n_wg_co_ll (the cohort's).  Reads the handle only. */
+int vrx_bulk_info(const vrx_bulk* b, int32_t out[8]);
 
 /* ---- donor matching (vrx_match.h) -----------------------------------------------------------
  * The genotype distance between every donor of X and every donor of Z,

@@ -21,7 +21,9 @@ float64 rounding of that output, an absolute number per element:
 The steps on a fitted model (``cell_loglik``, ``doublet``, ``donor_reads``) and one variant's own
 mixture (``varmix_row``, a chain whose intermediate state cannot be read back: there the rounding
 of one stage is carried into the next as a unit) follow the same conventions; their cases are in
-tests/exact_postfit.py.
+tests/exact_postfit.py.  One update of the bulk donor-abundance EM and its log-likelihood
+(``bulk_update``, ``bulk_loglik``) carry their stages' units the same way; their cases are in
+tests/exact_bulk.py.
 
 ``distance`` expresses a float64 result in these units; ``held`` is the rule the tests assert.
 """
@@ -349,6 +351,78 @@ def varmix_row(ad, dp, K, n_iter):
     kl, ukl = _beta_kl(s1, s2, 1.0, 1.0)
     one = (sum(terms) - kl, EPS * sum(abs(t) for t in terms) + ukl)
     return out, one
+
+
+# ------------------------------------------------------------------------------------
+# bulk donor abundance (vireoSNP/utils/vireo_bulk.py:75-96; the factored form of csrc/vrx_bulk.h)
+# ------------------------------------------------------------------------------------
+def _bulk_rates(GT, theta):
+    """tm[n, k] = sum_g P[n, k, g] theta_g and 1 - tm, each with its unit (a sum; one more rounding
+    for the complement, whose cancellation where tm -> 1 belongs to the formula)"""
+    P, th = np.asarray(GT, dtype=np.float64), ld(theta)      # (a genotype class at a time: no long-double copy)
+    tm = sum(P[:, :, g] * th[g] for g in range(P.shape[2]))
+    utm = EPS * sum(np.abs(P[:, :, g]) * np.abs(th[g]) for g in range(P.shape[2]))
+    om = 1 - tm
+    return P, tm, utm, om, utm + EPS * np.abs(om)
+
+
+def _bulk_fold(x, P):
+    """sum_nk x[n, k] P[n, k, g] per class g"""
+    return np.array([(x * P[:, :, g]).sum() for g in range(P.shape[2])], dtype=LD)
+
+
+def bulk_update(AD, BD, GT, psi, theta):
+    """One EM update of VireoBulk.fit (vireo_bulk.py:77-91) from float64 (psi, theta), taken as exact:
+    -> {"psi": (psi', unit), "theta": (theta', unit)}.
+
+    No intermediate can be read back, so every stage carries the unit of the stage it reads:
+    u(tm) into t1 = sum_k tm_k psi_k and t0; u(t1) / t1 and u(tm_k) into every term
+    x1_nk = (AD_n / t1_n) tm_nk psi_k (three roundings of its own: the division and two products),
+    likewise x0; the terms' units into psi_raw_k = sum_n x1 + x0, s1_g = sum_nk x1 P and s2_g, each
+    also a sum of its own (EPS sum|terms|); psi' = raw / sum raw and theta' = s1 / (s1 + s2) are ratios.
+    Written without a division by tm, raw or s1: a donor of psi_k = 0 keeps psi'_k = 0 with unit 0."""
+    a, b, psi = ld(AD), ld(BD), ld(psi)
+    P, tm, utm, om, uom = _bulk_rates(GT, theta)
+    q1, q0 = tm * psi, om * psi
+    t1, t0 = q1.sum(axis=1), q0.sum(axis=1)
+    ut1 = EPS * np.abs(q1).sum(axis=1) + (utm * psi).sum(axis=1)
+    ut0 = EPS * np.abs(q0).sum(axis=1) + (uom * psi).sum(axis=1)
+    w1, w0 = a / t1, b / t0
+    x1, x0 = w1[:, None] * q1, w0[:, None] * q0
+    ux1 = x1 * (ut1 / t1 + 3 * EPS)[:, None] + w1[:, None] * psi * utm
+    ux0 = x0 * (ut0 / t0 + 3 * EPS)[:, None] + w0[:, None] * psi * uom
+    raw = (x1 + x0).sum(axis=0)
+    uraw = EPS * raw + (ux1 + ux0).sum(axis=0)
+    s1, s2 = _bulk_fold(x1, P), _bulk_fold(x0, P)
+    u1, u2 = EPS * s1 + _bulk_fold(ux1, P), EPS * s2 + _bulk_fold(ux0, P)
+    tot = raw.sum()
+    utot = EPS * tot + uraw.sum()
+    new_psi = raw / tot
+    new_theta = s1 / (s1 + s2)
+    return {"psi": (new_psi, uraw / tot + new_psi * utot / tot),
+            "theta": (new_theta, u1 / (s1 + s2) + new_theta * (u1 + u2) / (s1 + s2))}
+
+
+def bulk_loglik(AD, BD, GT, psi, theta):
+    """sum_n AD_n log t1_n + BD_n log(1 - t1_n), t1 = GT . theta . psi (vireo_bulk.py:94-96, :152-158),
+    for one psi (K,) or several (Q, K) -> (value, unit), scalars or (Q,).
+
+    A sum of its 2 N terms, which also carries what t1 carries: d log t1 = u(t1) / t1 and
+    d log(1 - t1) = (u(t1) + EPS (1 - t1)) / (1 - t1), the rounding of the complement included.  Both
+    sides form log(1 - t1), so its cancellation where t1 -> 1 (and the absolute rounding of 1 - t1
+    where t1 -> 0) is the formula's and stands in the unit.  The exact side takes log1p(-t1)."""
+    a, b = ld(AD)[:, None], ld(BD)[:, None]
+    psi = ld(psi)
+    one = psi.ndim == 1
+    Q = np.atleast_2d(psi).T                        # (K, Q)
+    _, tm, utm, _, _ = _bulk_rates(GT, theta)
+    t1 = tm @ Q
+    ut1 = EPS * (np.abs(tm) @ np.abs(Q)) + utm @ np.abs(Q)
+    la, lb = a * np.log(t1), b * np.log1p(-t1)
+    value = (la + lb).sum(axis=0)
+    carried = a * ut1 / t1 + b * (ut1 + EPS * (1 - t1)) / (1 - t1)
+    unit = EPS * (np.abs(la) + np.abs(lb)).sum(axis=0) + carried.sum(axis=0)
+    return (value[0], unit[0]) if one else (value, unit)
 
 
 # ------------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ from tests import gold
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COHORT_ABI = {"vrx_bulk_set_cohort": 4, "vrx_bulk_cohort_chunk": 0, "vrx_bulk_fit_cohort": 11,
-              "vrx_bulk_loglik_cohort": 5}
+              "vrx_bulk_loglik_cohort": 5, "vrx_bulk_info": 2}
 
 
 @pytest.fixture(scope="module")

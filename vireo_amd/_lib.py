@@ -87,6 +87,7 @@ SIGNATURES = {
     "vrx_bulk_fit_cohort": (C.c_int, [_P, _D, _D, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, _D, _I32,
                                       _D]),
     "vrx_bulk_loglik_cohort": (C.c_int, [_P, C.c_int64, _D, _D, _D]),
+    "vrx_bulk_info": (C.c_int, [_P, _I32]),
     "vrx_geno_dist": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _D, _D, C.c_int64, _D, _D]),
     "vrx_barcode_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint8), _D,
                                      C.POINTER(_P)]),

@@ -230,6 +230,13 @@ extern "C" int vrx_bulk_loglik(vrx_bulk* b, int64_t n_psi, const double* psi, co
 
 extern "C" int32_t vrx_bulk_cohort_chunk(void) { return VRX_BULK_COHORT; }
 
+extern "C" int vrx_bulk_info(const vrx_bulk* b, int32_t out[8]) {
+    VRX_REQUIRE(b && out, "vrx_bulk_info: null argument");
+    const int v[8] = {b->T, b->n_wg, b->T_ll, b->n_wg_ll, b->T_co, b->n_wg_co, b->T_co_ll, b->n_wg_co_ll};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return VRX_OK;
+}
+
 extern "C" int vrx_bulk_set_cohort(vrx_bulk* b, int64_t n_sample, const double* AD, const double* DP) {
     VRX_REQUIRE(b && AD && DP, "vrx_bulk_set_cohort: null argument");
     VRX_REQUIRE(n_sample >= 1 && n_sample <= (1 << 16), "vrx_bulk_set_cohort: 1 <= n_sample <= 65536");

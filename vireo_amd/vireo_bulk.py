@@ -113,6 +113,14 @@ class BulkData:
     def handle(self):
         return self._h
 
+    def info(self):
+        """variants per tile and workgroups of the four passes, as the handle launches them: T, n_wg (fit),
+        T_ll, n_wg_ll (log-likelihood), T_co, n_wg_co, T_co_ll, n_wg_co_ll (the cohort's)"""
+        out = np.zeros(8, dtype=np.int32)
+        _lib.check(_lib.lib().vrx_bulk_info(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return dict(zip(("T", "n_wg", "T_ll", "n_wg_ll", "T_co", "n_wg_co", "T_co_ll", "n_wg_co_ll"),
+                        (int(x) for x in out)))
+
     def set_counts(self, AD, DP):
         """another sample on the same genotypes: GT_prob stays on the device"""
         AD, DP, _ = _check_inputs(AD, DP)
