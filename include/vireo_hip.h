@@ -258,6 +258,10 @@ int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double* theta, co
                         const double* psi_init /* n_cell x n_donor */, int32_t min_iter, int32_t max_iter,
                         double epsilon, double* psi /* n_cell x n_donor */, double* var /* n_cell x n_donor */,
                         double* llr /* n_cell */, int32_t* n_iter /* n_cell */, double* ms3);
+/* What vrx_problem_ambient launches at n_donor under the environment as it is (VIREO_AMBIENT_LDS): cap, the
+ * most selected entries of a cell whose theta rows stay in LDS (a longer cell reads them from global memory),
+ * and the LDS bytes of one cell's wave.  Reads nothing of the device. */
+int vrx_ambient_info(int64_t n_donor, int32_t* cap, int64_t* lds_bytes);
 
 /* ---- bulk donor abundance (vrx_bulk.h) ---------------------------------------------------
  * A bulk sample's per-variant counts and the donors' genotype probabilities, resident on the

@@ -23,7 +23,8 @@ mixture (``varmix_row``, a chain whose intermediate state cannot be read back: t
 of one stage is carried into the next as a unit) follow the same conventions; their cases are in
 tests/exact_postfit.py.  One update of the bulk donor-abundance EM and its log-likelihood
 (``bulk_update``, ``bulk_loglik``) carry their stages' units the same way; their cases are in
-tests/exact_bulk.py.
+tests/exact_bulk.py.  So do the per-cell ambient EM at a forced length and the ELBO gain of a variant
+(``ambient_cell``, ``elbo_gain``); their cases are in tests/exact_ambient.py.
 
 ``distance`` expresses a float64 result in these units; ``held`` is the rule the tests assert.
 """
@@ -423,6 +424,108 @@ def bulk_loglik(AD, BD, GT, psi, theta):
     carried = a * ut1 / t1 + b * (ut1 + EPS * (1 - t1)) / (1 - t1)
     unit = EPS * (np.abs(la) + np.abs(lb)).sum(axis=0) + carried.sum(axis=0)
     return (value[0], unit[0]) if one else (value, unit)
+
+
+# ------------------------------------------------------------------------------------
+# ambient RNA (vireoSNP/utils/vireo_doublet.py:139-210, variant_select.py:66-106; the factored form of
+# csrc/vrx_ambient.h)
+# ------------------------------------------------------------------------------------
+def _amb_loglik(a, b, t1, ut1):
+    """sum_e a log t1 + b log(1 - t1) with what t1 carries, as ``bulk_loglik``: the cancellation of
+    1 - t1 is the formula's and stands in the unit; the exact side takes log1p(-t1)"""
+    la, lb = a * np.log(t1), b * np.log1p(-t1)
+    carried = a * ut1 / t1 + b * (ut1 + EPS * (1 - t1)) / (1 - t1)
+    return (la + lb).sum(), EPS * (np.abs(la) + np.abs(lb)).sum() + carried.sum()
+
+
+def ambient_cell(a, b, th, psi0, n_updates):
+    """One cell of the ambient EM by the header formulas of csrc/vrx_ambient.h, exactly ``n_updates``
+    updates psi_k <- psi_k r_k / sum_j psi_j r_j from psi0 and no stop rule: what the device returns when
+    min_iter = max_iter = n_updates and epsilon = 0.  a, b (n_e,): the counts of the cell's selected
+    entries, th (n_e, K) their theta rows, all float64 or integer and taken as exact.
+    -> {"psi": psi after n_updates updates, "var": 1 / Fisher information at that psi,
+        "llr": L(psi after n_updates - 1 updates) - L0}, each (value, unit); L0 is the one-donor
+    log-likelihood at the first maximum of the final psi.  NaN throughout without selected counts.
+
+    No intermediate can be read back, so every stage carries the unit of the stage it reads:
+    u(t1) = EPS t1 + th . u(psi), u(t0) likewise with one more rounding for 1 - th; the weights a / t1 and
+    b / t0 carry u(t) / t + EPS relative; r_k is a sum of its own (EPS sum|terms|) plus the weights' carry;
+    psi r, its sum and the ratio add their relative units, into the next update's u(psi).  Written without
+    a division by psi or r: a component of exactly 0 stays 0 with unit 0.  The Fisher sums carry twice the
+    relative unit of t1 and of 1 - t1 (three roundings a term: the square, the division, the product), var
+    that of a ratio, llr u(L) + u(L0) and its own rounding."""
+    a, b, th, psi = ld(a), ld(b), ld(th), ld(psi0)
+    K = th.shape[1]
+    if a.sum() + b.sum() == 0:
+        nan = np.full(K, np.nan, dtype=LD)
+        return {"psi": (nan, nan.copy()), "var": (nan.copy(), nan.copy()), "llr": (LD(np.nan), LD(np.nan))}
+    om = 1 - th
+    upsi = np.zeros(K, dtype=LD)
+    L = uL = None
+    for _ in range(n_updates):
+        t1, t0 = th @ psi, om @ psi
+        ut1 = EPS * t1 + th @ upsi
+        ut0 = 2 * EPS * t0 + om @ upsi
+        L, uL = _amb_loglik(a, b, t1, ut1)              # of the psi this update starts from
+        x1, x0 = th * (a / t1)[:, None], om * (b / t0)[:, None]
+        r = (x1 + x0).sum(axis=0)
+        ur = EPS * (x1 + x0).sum(axis=0) + (x1 * (ut1 / t1 + EPS)[:, None] + x0 * (ut0 / t0 + EPS)[:, None]).sum(axis=0)
+        q = psi * r
+        uq = upsi * r + psi * ur + EPS * q
+        tot = q.sum()
+        utot = EPS * tot + uq.sum()
+        psi = q / tot
+        upsi = uq / tot + psi * (utot / tot + EPS)
+    t1 = th @ psi
+    ut1 = EPS * t1 + th @ upsi
+    c1 = 1 - t1
+    uc1 = ut1 + EPS * c1
+    f1, f0 = a / (t1 * t1), b / (c1 * c1)
+    uf = f1 * (2 * ut1 / t1 + 3 * EPS) + f0 * (2 * uc1 / c1 + 3 * EPS)
+    th2 = th * th
+    fisher = th2.T @ (f1 + f0)
+    ufisher = EPS * fisher + th2.T @ uf
+    var = 1 / fisher
+    tm = th[:, int(np.argmax(psi))]                     # exact inputs: a sum, and the rounding of 1 - tm
+    la, lb = a * np.log(tm), b * np.log1p(-tm)
+    L0, uL0 = (la + lb).sum(), EPS * (np.abs(la) + np.abs(lb) + b).sum()
+    llr = L - L0
+    return {"psi": (psi, upsi), "var": (var, var * (ufisher / fisher + EPS)),
+            "llr": (llr, uL + uL0 + EPS * np.abs(llr))}
+
+
+def elbo_gain(C, ID, pseudocount):
+    """variant_ELBO_gain (variant_select.py:66-106) from ``donor_reads(C, ID)`` with its units:
+    logsumexp_k t(AD@ID, DP@ID)[:, k] - t(row sums), t = s1 psi(s1) + s2 psi(s2) - ss psi(ss) with
+    s1 = ad + pc, s2 = (dp - ad) + pc, ss = dp + 2 pc -> {"gain": (value, unit)} per variant.
+
+    A term's unit: the rounding of its three products and the carry (|psi(s)| + s psi'(s)) u(s) of each
+    shape (a float64 trigamma is plenty for a unit), u(s) the unit of the reads it is formed of and the
+    rounding of forming it.  The logsumexp moves by at most its largest term's unit (d lse = sum_k p_k d t_k)
+    and rounds its own sum, logarithm and result; the one-donor term has exact integer row sums."""
+    reads = donor_reads(C, ID)
+    (A, uA), (D, uD) = reads["AD_reads"], reads["DP_reads"]
+    pc = LD(pseudocount)
+
+    def term(ad, uad, dp, udp):
+        bd = dp - ad
+        s = (ad + pc, bd + pc, dp + 2 * pc)
+        us = (uad + EPS * s[0], uad + udp + EPS * (np.abs(bd) + s[1]), udp + EPS * s[2])
+        d = [psi(x) for x in s]
+        tri = [ld(polygamma(1, np.asarray(x, dtype=np.float64))) for x in s]
+        prod = [x * y for x, y in zip(s, d)]
+        unit = EPS * sum(np.abs(x) for x in prod)
+        unit = unit + sum((np.abs(y) + x * z) * u for x, y, z, u in zip(s, d, tri, us))
+        return prod[0] + prod[1] - prod[2], unit
+
+    T, uT = term(A, uA, D, uD)
+    mx = T.max(axis=1)
+    lse = mx + np.log(np.exp(T - mx[:, None]).sum(axis=1))
+    ulse = uT.max(axis=1) + EPS * (np.abs(lse) + 1)
+    zero = np.zeros(C.shape[0], dtype=LD)
+    one, uone = term(np.asarray(C.AD.sum(axis=1)).ravel(), zero, np.asarray(C.DP.sum(axis=1)).ravel(), zero)
+    gain = lse - one
+    return {"gain": (gain, ulse + uone + EPS * np.abs(gain))}
 
 
 # ------------------------------------------------------------------------------------

@@ -22,7 +22,6 @@ Shapes come from `draw_case` of tests/test_gpu_fuzz.py (empty rows, one long row
 up to 5000); the ambient problems with exact entry counts are built entry by entry.
 """
 import copy
-import ctypes as C
 import math
 
 import numpy as np
@@ -31,6 +30,8 @@ from scipy.sparse import csc_matrix
 
 from oracle import vireo_oracle as O
 from tests import ambient_np as A
+from tests.exact_ambient import amb_cap, amb_lds_bytes, built_ambient_problem, run_ambient
+from tests.exact_ambient import id_prob as _id_prob
 from tests.test_gpu_fuzz import draw_case
 
 pytestmark = pytest.mark.gpu
@@ -190,64 +191,7 @@ def test_wrap_with_a_four_class_genotype_prior(va):
 
 
 # =============================================================================== ambient EM
-def amb_lds_bytes(K, cap):
-    """vrx_amb_lds_bytes (vrx_ambient.h): psi[K] | r[K] | w1[64] | w0[64] | cap theta rows of stride K | 1
-    doubles, then 64 row numbers"""
-    return (2 * K + 128 + cap * (K | 1)) * 8 + 64 * 4
-
-
-def amb_cap(K, budget):
-    """the most entries whose theta rows a cell keeps in LDS under VIREO_AMBIENT_LDS = budget"""
-    fixed = amb_lds_bytes(K, 0)
-    return (budget - fixed) // ((K | 1) * 8) if budget > fixed else 0
-
-
-def run_ambient(counts, K, theta, sel, psi0, min_iter, max_iter, eps):
-    from vireo_amd import _lib
-    from vireo_amd._lib import dptr, f64
-    M = counts.n_cell
-    theta, psi0 = f64(theta), f64(psi0)
-    assert theta.shape == (counts.n_var, K) and psi0.shape == (M, K)
-    psi, var = np.full((M, K), -7.0), np.full((M, K), -7.0)
-    llr, n_iter = np.full(M, -7.0), np.full(M, -7, np.int32)
-    mask = np.ascontiguousarray(sel, dtype=np.uint8)
-    _lib.check(_lib.lib().vrx_problem_ambient(
-        counts.handle, K, dptr(theta), mask.ctypes.data_as(C.POINTER(C.c_uint8)), dptr(psi0), min_iter, max_iter,
-        eps, dptr(psi), dptr(var), dptr(llr), n_iter.ctypes.data_as(C.POINTER(C.c_int32)), None))
-    return psi, var, llr, n_iter
-
-
-def built_ambient_problem(seed, K, targets, n_background, bg_max, top, empty_selection=False):
-    """(N x M) counts in merged CSC form: cell i < len(targets) has exactly targets[i] entries on selected
-    variants (and a few on others), then `n_background` cells with 0 .. bg_max entries anywhere.
-    -> shape, colptr, rowidx, ad, dp, sel, theta, psi0"""
-    rng = np.random.default_rng(7000 + seed)
-    N = 640
-    sel = rng.random(N) < 0.55
-    sel[:max(max(targets, default=0), bg_max) + 8] = True         # (enough selected variants for every target)
-    rng.shuffle(sel)
-    on, off = np.flatnonzero(sel), np.flatnonzero(~sel)
-    GT = rng.dirichlet(np.ones(3) * 0.3, (N, K))
-    theta = np.tensordot(GT, np.array([0.01, 0.5, 0.99]), axes=(2, 0))
-    cols = []
-    for n in targets:
-        rows = np.concatenate([rng.choice(on, n, replace=False),
-                               rng.choice(off, int(rng.integers(0, min(30, off.size))), replace=False)])
-        cols.append(np.sort(rows))
-    for _ in range(n_background):
-        cols.append(np.sort(rng.choice(N, int(rng.integers(0, bg_max + 1)), replace=False)))
-    M = len(cols)
-    colptr = np.concatenate([[0], np.cumsum([c.size for c in cols])]).astype(np.int64)
-    rowidx = np.concatenate(cols).astype(np.int32) if colptr[-1] else np.zeros(0, np.int32)
-    dp = rng.integers(1, top + 1, rowidx.size).astype(np.int32)
-    donor = np.repeat(rng.integers(0, K, M), np.diff(colptr))
-    ad = rng.binomial(dp, theta[rowidx, donor]).astype(np.int32)
-    if empty_selection:
-        sel = np.zeros(N, bool)
-    psi0 = rng.dirichlet(np.ones(K), M)
-    return (N, M), colptr, rowidx, ad, dp, sel, theta, psi0
-
-
+# (amb_lds_bytes, amb_cap, run_ambient, built_ambient_problem: tests/exact_ambient.py)
 # K, entries per constructed cell, small cap (cells with cap - 1, cap, cap + 1 entries are added; None: no
 # such budget), (min_iter, max_iter, eps), VIREO_ENTRY_FMT, largest count, all-zero selection.
 # Cells never have more entries than an LDS budget below 64 KiB can cache (59 at K = 130, 121 at K = 64 / 65).
@@ -386,24 +330,6 @@ GAIN_CASES = [
     (270, 16, 0.5, "0", "zeros"), (220, 3, 1e-3, "1", "random"), (236, 20, 10.0, "0", "onehot"),
     (206, 2, 0.5, "1", "onehot"), (234, 33, 0.5, "0", "zeros"),
 ]
-
-
-def _id_prob(rng, M, K, kind):
-    soft = rng.dirichlet(np.ones(K) * 0.5, M) if K > 1 else rng.random((M, 1))
-    if kind == "random":
-        return soft
-    if kind == "zeros":              # exact zeros: a donor nobody is assigned to, cells without a donor
-        soft[:, rng.integers(K)] = 0.0
-        soft[rng.random(M) < 0.1] = 0.0
-        return soft
-    ID = np.zeros((M, K))            # exact zeros and ones, rows within 1e-9 of one-hot, a few soft ones
-    ID[np.arange(M), rng.integers(0, K, M)] = 1.0
-    near = rng.random(M) < 0.2
-    if K > 1:
-        ID[near] = ID[near] * (1 - 1e-9) + (1 - ID[near]) * 1e-9 / (K - 1)
-    some = rng.random(M) < 0.1
-    ID[some] = soft[some]
-    return ID
 
 
 def _exact_gain(AD, DP, ID, rows, pc):

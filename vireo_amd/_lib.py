@@ -76,6 +76,7 @@ SIGNATURES = {
     "vrx_problem_elbo_gain": (C.c_int, [_P, C.c_int64, _D, C.c_double, _D]),
     "vrx_problem_ambient": (C.c_int, [_P, C.c_int64, _D, C.POINTER(C.c_uint8), _D, C.c_int32, C.c_int32,
                                       C.c_double, _D, _D, _D, _I32, _D]),
+    "vrx_ambient_info": (C.c_int, [C.c_int64, _I32, _I64]),
     "vrx_bulk_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, _D, _D, _D, C.POINTER(_P)]),
     "vrx_bulk_destroy": (None, [_P]),
     "vrx_bulk_set_counts": (C.c_int, [_P, _D, _D]),

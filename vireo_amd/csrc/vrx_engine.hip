@@ -3438,6 +3438,27 @@ static int amb_compact(vrx_problem* p, const int32_t* d_rank, DevBuf<int64_t>& s
     return VRX_OK;
 }
 
+// theta rows of a cell's entries stay in LDS up to this budget per wave (VIREO_AMBIENT_LDS bytes):
+// the most entries a cell may have to be cached, and the LDS of one wave
+static void amb_plan(int K, int& cap, size_t& lds) {
+    const size_t budget = (size_t)std::max(env_int("VIREO_AMBIENT_LDS", 16384), 0);
+    const size_t fixed = vrx_amb_lds_bytes(K, 0);
+    cap = budget > fixed ? (int)std::min<size_t>((budget - fixed) / ((size_t)(K | 1) * sizeof(double)), INT32_MAX)
+                         : 0;
+    lds = vrx_amb_lds_bytes(K, cap);
+}
+
+extern "C" int vrx_ambient_info(int64_t n_donor, int32_t* cap_out, int64_t* lds_bytes_out) {
+    VRX_REQUIRE(cap_out && lds_bytes_out, "vrx_ambient_info: null argument");
+    VRX_REQUIRE(n_donor >= 1 && n_donor <= 4096, "vrx_ambient_info: n_donor must be 1..4096");
+    int cap = 0;
+    size_t lds = 0;
+    amb_plan((int)n_donor, cap, lds);
+    *cap_out = cap;
+    *lds_bytes_out = (int64_t)lds;
+    return VRX_OK;
+}
+
 extern "C" int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double* theta,
                                    const uint8_t* selected, const double* psi_init, int32_t min_iter,
                                    int32_t max_iter, double epsilon, double* psi, double* var,
@@ -3486,12 +3507,9 @@ extern "C" int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double
                                              : amb_compact<VRX_FMT_WIDE>(p, d_rank.p, sptr, ev, ea, eb);
     if (rc) return rc;
     VRX_HIP(hipEventRecord(ev_t[1], s));
-    // theta rows of a cell's entries stay in LDS up to this budget per wave (VIREO_AMBIENT_LDS bytes)
-    const size_t budget = (size_t)std::max(env_int("VIREO_AMBIENT_LDS", 16384), 0);
-    const size_t fixed = vrx_amb_lds_bytes(K, 0);
-    const int cap = budget > fixed ? (int)std::min<size_t>((budget - fixed) / ((size_t)(K | 1) * sizeof(double)), INT32_MAX)
-                                   : 0;
-    const size_t lds = vrx_amb_lds_bytes(K, cap);
+    int cap = 0;
+    size_t lds = 0;
+    amb_plan(K, cap, lds);
     VRX_REQUIRE(lds <= 64 * 1024, "vrx_problem_ambient: %zu bytes of LDS per cell (n_donor too large)", lds);
     vrx_amb_em<<<(unsigned)M, 64, lds, s>>>(K, sptr.p, ev.p, ea.p, eb.p, d_theta.p, d_psi0.p, min_iter, max_iter,
                                             epsilon, cap, d_psi.p, d_var.p, d_llr.p, d_it.p);
