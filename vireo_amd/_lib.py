@@ -6,6 +6,7 @@ every compute entry point raises.  Build the library with
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -183,6 +184,47 @@ def lib():
 def check(rc):
     if rc != 0:
         raise VrxError("libvireo_hip: %s (code %d)" % (lib().vrx_last_error().decode(), rc))
+
+
+def _release(destroy, ptr, *keep):
+    destroy(ptr)
+
+
+class Handle:
+    """Owner of one library handle; the lifetime rule of every wrapper ("Handle lifetime").
+
+    ``create(out)`` calls ``vrx_X_create(..., out)`` and returns its status, ``destroy`` is ``vrx_X_destroy``.
+    The handle is destroyed once: by ``close()``, which may be called again, when the owner is collected, or at
+    exit.  The objects in ``keep`` outlive it (a model reads its problem while it is destroyed).  After
+    ``close()`` the pointer is gone: ``ptr`` raises instead of handing freed memory to the library.  Wrapper
+    classes derive from it; a handle that lives for one call is a ``with`` block."""
+
+    def __init__(self, name, create, destroy, keep=()):
+        self._name = name
+        ptr = C.c_void_p()
+        check(create(C.byref(ptr)))
+        self._ptr = ptr
+        self._fin = weakref.finalize(self, _release, destroy, ptr, *keep)
+
+    @property
+    def ptr(self):
+        """The ctypes pointer of the live handle."""
+        if getattr(self, "_ptr", None) is None:
+            raise VrxError("%s is closed" % getattr(self, "_name", type(self).__name__))
+        return self._ptr
+
+    _h = ptr
+
+    def close(self):
+        self._ptr = None
+        if hasattr(self, "_fin"):
+            self._fin()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def device_count():

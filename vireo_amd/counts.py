@@ -109,7 +109,7 @@ def balance_policy(balance=None, expected_iterations=None, nnz=None):
     return expected_iterations is not None and expected_iterations >= need
 
 
-class DeviceCounts:
+class DeviceCounts(_lib.Handle):
     """(AD, DP) on one GPU, in both orientations (C handle ``vrx_problem``)."""
 
     def __init__(self, AD, DP, device=None, _merged=None, balance=None, expected_iterations=None):
@@ -126,16 +126,15 @@ class DeviceCounts:
         self.shape = (self.n_var, self.n_cell)
         self.nnz = int(rowidx.size)
         self.device = device
-        self._h = C.c_void_p()
         flags = _lib.PROBLEM_BALANCED if balance_policy(balance, expected_iterations, self.nnz) else 0
-        _lib.check(_lib.lib().vrx_problem_create2(
+        L = _lib.lib()
+        super().__init__("DeviceCounts", lambda out: L.vrx_problem_create2(
             device, self.n_var, self.n_cell, self.nnz,
             colptr.ctypes.data_as(C.POINTER(C.c_int64)),
             rowidx.ctypes.data_as(C.POINTER(C.c_int32)),
             ad.ctypes.data_as(C.POINTER(C.c_int32)),
-            dp.ctypes.data_as(C.POINTER(C.c_int32)), flags, C.byref(self._h)))
+            dp.ctypes.data_as(C.POINTER(C.c_int32)), flags, out), L.vrx_problem_destroy)
         self._binom = None
-        self._fin = weakref.finalize(self, _lib.lib().vrx_problem_destroy, self._h)
 
     @classmethod
     def from_merged(cls, shape, colptr, rowidx, ad, dp, device=None, balance=None, expected_iterations=None):
@@ -195,9 +194,6 @@ class DeviceCounts:
         _lib.check(_lib.lib().vrx_problem_donor_reads(self._h, ID.shape[1], _lib.dptr(ID),
                                                       _lib.dptr(A), _lib.dptr(D)))
         return A, D
-
-    def close(self):
-        self._fin()
 
 
 # (AD, DP) -> DeviceCounts.  vireo_wrap calls fit() n_init+1 times on the same matrices

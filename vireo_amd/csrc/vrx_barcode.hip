@@ -1,35 +1,40 @@
 // Barcode selection: the vrx_barcode_* entries of include/vireo_hip.h on the kernels of vrx_barcode.h and
 // hipCUB.  A handle owns its stream, events and buffers; nothing here touches a vrx_problem or a vrx_model.
 #include <algorithm>
-#include <memory>
 
-#include "vrx_common.h"
+#include "vrx_handle.h"
 #include "vrx_barcode.h"
 
-struct vrx_barcode {
-    int device = 0;
+struct vrx_barcode : VrxQueue {  // ev: 0, 1, 2 around the entropy pass and the ties, 3, 4 around the median
     int64_t N = 0;      // variants
     size_t stride = 0;  // bytes between the donors' rows of GT
     int K = 0, NC = 0;
     bool has_vc = false, have_round = false;
     int64_t n_kept = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     DevBuf<uint8_t> GT, flag, flag2, tmp;
     DevBuf<double> vc, ent, keys, sorted, table, part, scal;
     DevBuf<int32_t> state, tidx, kidx, ctl;  // state: order [K] | bnd [K + 1]
-    size_t tmp_bytes = 0;
 };
 
-extern "C" void vrx_barcode_destroy(vrx_barcode* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    for (hipEvent_t e : b->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
-    delete b;
+// The three hipCUB calls of a round over n items, on b->tmp, which vrx_barcode_create sizes for n_var items.
+static hipError_t bc_select_tied(vrx_barcode* b, int n, VrxCub mode = VRX_CUB_RUN) {
+    return vrx_cub(b->tmp,
+                   VRX_CUB_CALL(DeviceSelect::Flagged, hipcub::CountingInputIterator<int32_t>(0), b->flag.p, b->tidx.p,
+                                b->ctl.p + VRX_BC_TIED, n, b->stream),
+                   mode);
 }
+static hipError_t bc_sort_keys(vrx_barcode* b, int n, VrxCub mode = VRX_CUB_RUN) {
+    return vrx_cub(b->tmp, VRX_CUB_CALL(DeviceRadixSort::SortKeys, b->keys.p, b->sorted.p, n, 0, 64, b->stream),
+                   mode);
+}
+static hipError_t bc_select_kept(vrx_barcode* b, int n, VrxCub mode = VRX_CUB_RUN) {
+    return vrx_cub(b->tmp,
+                   VRX_CUB_CALL(DeviceSelect::Flagged, b->tidx.p, b->flag2.p, b->kidx.p, b->ctl.p + VRX_BC_KEPT, n,
+                                b->stream),
+                   mode);
+}
+
+extern "C" void vrx_barcode_destroy(vrx_barcode* b) { vrx_destroy(b); }
 
 extern "C" int vrx_barcode_create(int device, int64_t n_var, int64_t n_donor, int64_t n_cat, const uint8_t* GT,
                                   const double* var_count, vrx_barcode** out) {
@@ -38,20 +43,14 @@ extern "C" int vrx_barcode_create(int device, int64_t n_var, int64_t n_donor, in
     VRX_REQUIRE(n_donor >= 1 && n_donor <= VRX_BC_MAX_DONORS, "vrx_barcode_create: 1 <= n_donor <= %d",
                 VRX_BC_MAX_DONORS);
     VRX_REQUIRE(n_cat >= 1 && n_cat <= VRX_BC_MAX_CAT, "vrx_barcode_create: 1 <= categories <= %d", VRX_BC_MAX_CAT);
-    if (int e = vrx_use_device("vrx_barcode_create", device)) return e;
-    struct Del {
-        void operator()(vrx_barcode* b) const { vrx_barcode_destroy(b); }
-    };
-    std::unique_ptr<vrx_barcode, Del> b(new vrx_barcode());
-    b->device = device;
+    VrxOwned<vrx_barcode> b(new vrx_barcode());
+    VRX_TRY(b->open("vrx_barcode_create", device, 5));
     b->N = n_var;
     b->K = (int)n_donor;
     b->NC = n_cat <= 3 ? 3 : VRX_BC_MAX_CAT;
     b->stride = ((size_t)n_var + 255) & ~(size_t)255;
     b->has_vc = var_count != nullptr;
     const size_t N = (size_t)n_var;
-    VRX_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : b->ev) VRX_HIP(hipEventCreate(&e));
     hipStream_t s = b->stream;
     VRX_HIP(b->GT.alloc(b->stride * (size_t)b->K));
     VRX_HIP(hipMemsetAsync(b->GT.p, 0, b->stride * (size_t)b->K, s));
@@ -70,17 +69,13 @@ extern "C" int vrx_barcode_create(int device, int64_t n_var, int64_t n_donor, in
     VRX_HIP(b->scal.alloc(VRX_BC_SCALARS));
     VRX_HIP(b->ctl.alloc(VRX_BC_CTL_WORDS));
     VRX_HIP(b->state.alloc((size_t)(2 * b->K + 1)));
-    // the temporary storage of the largest of the three hipCUB calls of a round
-    size_t t1 = 0, t2 = 0, t3 = 0;
-    VRX_HIP(hipcub::DeviceSelect::Flagged(nullptr, t1, hipcub::CountingInputIterator<int32_t>(0), b->flag.p, b->tidx.p,
-                                          b->ctl.p + VRX_BC_TIED, (int)n_var, s));
+    // the temporary storage of the largest of the three hipCUB calls of a round (a round over fewer items that
+    // should ever ask for more grows it)
+    VRX_HIP(bc_select_tied(b.get(), (int)n_var, VRX_CUB_SIZE));
     if (var_count) {
-        VRX_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, t2, b->keys.p, b->sorted.p, (int)n_var, 0, 64, s));
-        VRX_HIP(hipcub::DeviceSelect::Flagged(nullptr, t3, b->tidx.p, b->flag2.p, b->kidx.p, b->ctl.p + VRX_BC_KEPT,
-                                              (int)n_var, s));
+        VRX_HIP(bc_sort_keys(b.get(), (int)n_var, VRX_CUB_SIZE));
+        VRX_HIP(bc_select_kept(b.get(), (int)n_var, VRX_CUB_SIZE));
     }
-    b->tmp_bytes = std::max(std::max(t1, t2), std::max(t3, (size_t)256));
-    VRX_HIP(b->tmp.alloc(b->tmp_bytes));
     VRX_HIP(hipStreamSynchronize(s));  // (the caller's arrays may die at return)
     *out = b.release();
     return VRX_OK;
@@ -107,7 +102,7 @@ extern "C" int vrx_barcode_round(vrx_barcode* b, const int32_t* order, const int
         for (int c = 0; c < n_class; ++c)
             VRX_REQUIRE(bnd[c] < bnd[c + 1], "vrx_barcode_round: class boundaries must increase");
     }
-    VRX_HIP(hipSetDevice(b->device));
+    VRX_TRY(b->use());
     hipStream_t s = b->stream;
     b->have_round = false;
     const size_t n_tab = (size_t)(2 * half_width + 1) * (size_t)(K + 1);
@@ -133,21 +128,16 @@ extern "C" int vrx_barcode_round(vrx_barcode* b, const int32_t* order, const int
     vrx_barcode_max2<<<1, VRX_BC_BLOCK, 0, s>>>(n_part, b->part.p, b->scal.p);
     vrx_barcode_flag<<<n_blk, VRX_BC_BLOCK, 0, s>>>(N, b->ent.p, b->scal.p, b->flag.p);
     VRX_HIP(hipGetLastError());
-    size_t tb = b->tmp_bytes;
-    VRX_HIP(hipcub::DeviceSelect::Flagged(b->tmp.p, tb, hipcub::CountingInputIterator<int32_t>(0), b->flag.p,
-                                          b->tidx.p, b->ctl.p + VRX_BC_TIED, (int)N, s));
+    VRX_HIP(bc_select_tied(b, (int)N, VRX_CUB_SIZED));  // (n_var items, as sized)
     VRX_HIP(hipEventRecord(b->ev[2], s));
     int32_t hctl[VRX_BC_CTL_WORDS] = {};
     double hmax = 0.0;
     VRX_HIP(hipMemcpyAsync(hctl, b->ctl.p, sizeof hctl, hipMemcpyDeviceToHost, s));
     VRX_HIP(hipMemcpyAsync(&hmax, b->scal.p + VRX_BC_MAX, sizeof(double), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
-    float t = 0.f;
-    double ms_ent = 0.0, ms_rest = 0.0;
-    VRX_HIP(hipEventElapsedTime(&t, b->ev[0], b->ev[1]));
-    ms_ent = t;
-    VRX_HIP(hipEventElapsedTime(&t, b->ev[1], b->ev[2]));
-    ms_rest = t;
+    double ms_ent = 0.0, ms_rest = 0.0, t = 0.0;
+    VRX_TRY(b->ms(0, 1, &ms_ent));
+    VRX_TRY(b->ms(1, 2, &ms_rest));
     counts3[0] = hctl[VRX_BC_TIED];
     counts3[1] = 0;
     counts3[2] = hctl[VRX_BC_OUTSIDE];
@@ -169,29 +159,16 @@ extern "C" int vrx_barcode_round(vrx_barcode* b, const int32_t* order, const int
         VRX_HIP(hipEventRecord(b->ev[3], s));
         vrx_barcode_gather<<<t_blk, VRX_BC_BLOCK, 0, s>>>(b->ctl.p, b->tidx.p, b->vc.p, b->keys.p);
         VRX_HIP(hipGetLastError());
-        // (the temporary storage was sized for n_var items; should fewer items ever ask for more, grow it)
-        size_t q1 = 0, q2 = 0;
-        VRX_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, q1, b->keys.p, b->sorted.p, n_tied, 0, 64, s));
-        VRX_HIP(hipcub::DeviceSelect::Flagged(nullptr, q2, b->tidx.p, b->flag2.p, b->kidx.p, b->ctl.p + VRX_BC_KEPT,
-                                              n_tied, s));
-        if (std::max(q1, q2) > b->tmp_bytes) {
-            VRX_HIP(hipStreamSynchronize(s));
-            b->tmp_bytes = std::max(q1, q2);
-            VRX_HIP(b->tmp.alloc(b->tmp_bytes));
-        }
-        tb = b->tmp_bytes;
-        VRX_HIP(hipcub::DeviceRadixSort::SortKeys(b->tmp.p, tb, b->keys.p, b->sorted.p, n_tied, 0, 64, s));
+        VRX_HIP(bc_sort_keys(b, n_tied));
         vrx_barcode_median<<<1, 1, 0, s>>>(b->ctl.p, b->sorted.p, b->scal.p);
         vrx_barcode_flag_ge<<<t_blk, VRX_BC_BLOCK, 0, s>>>(b->ctl.p, b->keys.p, b->scal.p, b->flag2.p);
         VRX_HIP(hipGetLastError());
-        tb = b->tmp_bytes;
-        VRX_HIP(hipcub::DeviceSelect::Flagged(b->tmp.p, tb, b->tidx.p, b->flag2.p, b->kidx.p, b->ctl.p + VRX_BC_KEPT,
-                                              n_tied, s));
+        VRX_HIP(bc_select_kept(b, n_tied));
         VRX_HIP(hipEventRecord(b->ev[4], s));
         int32_t kept = 0;
         VRX_HIP(hipMemcpyAsync(&kept, b->ctl.p + VRX_BC_KEPT, sizeof kept, hipMemcpyDeviceToHost, s));
         VRX_HIP(hipStreamSynchronize(s));
-        VRX_HIP(hipEventElapsedTime(&t, b->ev[3], b->ev[4]));
+        VRX_TRY(b->ms(3, 4, &t));
         if (ms2) ms2[1] = ms_rest + t;
         n_kept = kept;
     }
@@ -206,7 +183,7 @@ extern "C" int vrx_barcode_pick(vrx_barcode* b, int64_t r, int64_t* index_out, d
     VRX_REQUIRE(b->have_round, "vrx_barcode_pick: no finished round");
     VRX_REQUIRE(r >= 0 && r < b->n_kept, "vrx_barcode_pick: r = %lld is not one of the %lld survivors", (long long)r,
                 (long long)b->n_kept);
-    VRX_HIP(hipSetDevice(b->device));
+    VRX_TRY(b->use());
     hipStream_t s = b->stream;
     int32_t idx = -1;
     VRX_HIP(hipMemcpyAsync(&idx, (b->has_vc ? b->kidx.p : b->tidx.p) + r, sizeof idx, hipMemcpyDeviceToHost, s));
@@ -221,7 +198,7 @@ extern "C" int vrx_barcode_pick(vrx_barcode* b, int64_t r, int64_t* index_out, d
 extern "C" int vrx_barcode_entropies(vrx_barcode* b, double* out) {
     VRX_REQUIRE(b && out, "vrx_barcode_entropies: null argument");
     VRX_REQUIRE(b->have_round, "vrx_barcode_entropies: no finished round");
-    VRX_HIP(hipSetDevice(b->device));
+    VRX_TRY(b->use());
     VRX_HIP(hipMemcpyAsync(out, b->ent.p, (size_t)b->N * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     VRX_HIP(hipStreamSynchronize(b->stream));
     return VRX_OK;

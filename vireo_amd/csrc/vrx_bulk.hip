@@ -1,20 +1,17 @@
 // Bulk donor abundance: the vrx_bulk_* entries of include/vireo_hip.h on the kernels of vrx_bulk.h.
 // A handle owns its stream, events and buffers; nothing here touches a vrx_problem or a vrx_model.
 #include <algorithm>
-#include <memory>
 
-#include "vrx_common.h"
+#include "vrx_handle.h"
 #include "vrx_bulk.h"
 
-struct vrx_bulk {
-    int device = 0, n_cu = 0;
+struct vrx_bulk : VrxQueue {  // ev: 0, 1 bracket the passes of a fit
+    int n_cu = 0;
     int64_t N = 0;
     int K = 0, G = 0;
     int T = 0, n_wg = 0;       // the fit pass: variants per tile, workgroups
     int T_ll = 0, n_wg_ll = 0; // the log-likelihood pass
     size_t lds = 0, lds_ll = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
     DevBuf<double> P;
     DevBuf<double2> AB;  // (AD, BD) per variant
     DevBuf<double> par;     // psi[K] | theta[G]
@@ -58,15 +55,7 @@ static int bulk_upload_counts(vrx_bulk* b, const double* AD, const double* DP) {
     return VRX_OK;
 }
 
-extern "C" void vrx_bulk_destroy(vrx_bulk* b) {
-    if (!b) return;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    if (b->t0) (void)hipEventDestroy(b->t0);
-    if (b->t1) (void)hipEventDestroy(b->t1);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
-    delete b;
-}
+extern "C" void vrx_bulk_destroy(vrx_bulk* b) { vrx_destroy(b); }
 
 extern "C" int vrx_bulk_create(int device, int64_t n_var, int64_t n_donor, int64_t n_gt, const double* GT_prob,
                                const double* AD, const double* DP, vrx_bulk** out) {
@@ -74,12 +63,8 @@ extern "C" int vrx_bulk_create(int device, int64_t n_var, int64_t n_donor, int64
     VRX_REQUIRE(n_var >= 1 && n_var < ((int64_t)1 << 31) - 512 && n_donor >= 1 && n_gt >= 2,
                 "vrx_bulk_create: 1 <= n_var < 2^31 - 512, n_donor >= 1, n_gt >= 2");
     VRX_REQUIRE(n_donor * n_gt <= (1 << 20), "vrx_bulk_create: n_donor x n_gt too large");
-    if (int e = vrx_use_device("vrx_bulk_create", device)) return e;
-    struct Del {
-        void operator()(vrx_bulk* b) const { vrx_bulk_destroy(b); }
-    };
-    std::unique_ptr<vrx_bulk, Del> b(new vrx_bulk());
-    b->device = device;
+    VrxOwned<vrx_bulk> b(new vrx_bulk());
+    VRX_TRY(b->open("vrx_bulk_create", device, 2));
     b->N = n_var;
     b->K = (int)n_donor;
     b->G = (int)n_gt;
@@ -112,12 +97,8 @@ extern "C" int vrx_bulk_create(int device, int64_t n_var, int64_t n_donor, int64
     b->lds_co_ll = vrx_bulk_cohort_ll_lds_doubles(vrx_bulk_shape(b->K, b->G, b->T_co_ll)) * sizeof(double);
     b->n_wg_co = grid(b->T_co, b->lds_co);
     b->n_wg_co_ll = grid(b->T_co_ll, b->lds_co_ll);
-    VRX_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    VRX_HIP(hipEventCreate(&b->t0));
-    VRX_HIP(hipEventCreate(&b->t1));
     VRX_HIP(b->P.upload(GT_prob, (size_t)(n_var * n_donor * n_gt), b->stream));
-    int rc = bulk_upload_counts(b.get(), AD, DP);
-    if (rc) return rc;
+    VRX_TRY(bulk_upload_counts(b.get(), AD, DP));
     VRX_HIP(b->par.alloc((size_t)(b->K + b->G)));
     VRX_HIP(b->part.alloc(std::max((size_t)b->n_wg * (b->K + 2 * b->G + 1), (size_t)b->n_wg_ll * VRX_BULK_Q)));
     VRX_HIP(b->psis.alloc((size_t)VRX_BULK_Q * b->K));
@@ -129,7 +110,7 @@ extern "C" int vrx_bulk_create(int device, int64_t n_var, int64_t n_donor, int64
 
 extern "C" int vrx_bulk_set_counts(vrx_bulk* b, const double* AD, const double* DP) {
     VRX_REQUIRE(b && AD && DP, "vrx_bulk_set_counts: null argument");
-    VRX_HIP(hipSetDevice(b->device));
+    VRX_TRY(b->use());
     return bulk_upload_counts(b, AD, DP);
 }
 
@@ -137,7 +118,7 @@ extern "C" int vrx_bulk_set_counts(vrx_bulk* b, const double* AD, const double* 
 // of a pass); the host enqueues a batch of passes, then reads the n_ctl control words at d_ctl into hctl.
 // The first batch reaches the first pass the rule can fire after; a kernel launched behind the stop
 // returns at once.  enqueue() launches one pass on the handle's stream; stopped() says after a batch
-// whether hctl holds every stop word set, which ends the loop (as does pass max_iter).  t0 and t1
+// whether hctl holds every stop word set, which ends the loop (as does pass max_iter).  The events 0 and 1
 // bracket the passes.
 template <class Enqueue, class Stopped>
 static int bulk_run_passes(vrx_bulk* b, int32_t max_iter, int32_t min_iter, const int32_t* d_ctl, int32_t* hctl,
@@ -147,13 +128,13 @@ static int bulk_run_passes(vrx_bulk* b, int32_t max_iter, int32_t min_iter, cons
     const int64_t n_pass = (int64_t)max_iter + 1;  // pass p closes iteration p - 1
     int64_t next = 0;
     bool stop = false;
-    VRX_HIP(hipEventRecord(b->t0, s));
+    VRX_HIP(hipEventRecord(b->ev[0], s));
     while (next < n_pass && !stop) {
         const int64_t first = std::max<int64_t>((int64_t)std::max(min_iter, 0) + 3, batch);
         const int64_t upto = std::min(n_pass, next == 0 ? first : next + batch);
         for (; next < upto; ++next) enqueue();
         VRX_HIP(hipGetLastError());
-        VRX_HIP(hipEventRecord(b->t1, s));
+        VRX_HIP(hipEventRecord(b->ev[1], s));
         VRX_HIP(hipMemcpyAsync(hctl, d_ctl, n_ctl * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         VRX_HIP(hipStreamSynchronize(s));
         stop = stopped();
@@ -166,7 +147,7 @@ extern "C" int vrx_bulk_fit(vrx_bulk* b, double* psi_io, double* theta_io, int32
                             int32_t* last_it, double* ms_out) {
     VRX_REQUIRE(b && psi_io && theta_io && logLik_trace && last_it, "vrx_bulk_fit: null argument");
     VRX_REQUIRE(max_iter >= 1, "vrx_bulk_fit: max_iter must be >= 1");
-    VRX_HIP(hipSetDevice(b->device));
+    VRX_TRY(b->use());
     hipStream_t s = b->stream;
     const int K = b->K, G = b->G, W = K + 2 * G + 1;
     if (b->trace.n < (size_t)max_iter) VRX_HIP(b->trace.alloc((size_t)max_iter));
@@ -196,18 +177,13 @@ extern "C" int vrx_bulk_fit(vrx_bulk* b, double* psi_io, double* theta_io, int32
     VRX_HIP(hipMemcpyAsync(psi_io, b->par.p, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipMemcpyAsync(theta_io, b->par.p + K, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
-    if (ms_out) {
-        float ms = 0.f;
-        VRX_HIP(hipEventElapsedTime(&ms, b->t0, b->t1));
-        *ms_out = ms;
-    }
-    return VRX_OK;
+    return b->ms(0, 1, ms_out);
 }
 
 extern "C" int vrx_bulk_loglik(vrx_bulk* b, int64_t n_psi, const double* psi, const double* theta, double* out) {
     VRX_REQUIRE(b && psi && theta && out, "vrx_bulk_loglik: null argument");
     VRX_REQUIRE(n_psi >= 1, "vrx_bulk_loglik: n_psi must be >= 1");
-    VRX_HIP(hipSetDevice(b->device));
+    VRX_TRY(b->use());
     hipStream_t s = b->stream;
     const int K = b->K, G = b->G;
     VRX_HIP(hipMemcpyAsync(b->par.p + K, theta, (size_t)G * sizeof(double), hipMemcpyHostToDevice, s));
@@ -244,7 +220,7 @@ extern "C" int vrx_bulk_set_cohort(vrx_bulk* b, int64_t n_sample, const double* 
                 "vrx_bulk_set_cohort: n_donor x n_gt = %d x %d needs %zu bytes of LDS per workgroup for a chunk of "
                 "%d samples (limit %zu)",
                 b->K, b->G, std::max(b->lds_co, b->lds_co_ll), VRX_BULK_COHORT, b->lds_max);
-    VRX_HIP(hipSetDevice(b->device));
+    VRX_TRY(b->use());
     const size_t S = (size_t)n_sample, N = (size_t)b->N;
     const size_t n_chunk = (S + VRX_BULK_COHORT - 1) / VRX_BULK_COHORT;
     b->n_sample = 0;  // (no cohort while this one is half built)
@@ -268,7 +244,7 @@ extern "C" int vrx_bulk_fit_cohort(vrx_bulk* b, double* psi_io, double* theta_io
     VRX_REQUIRE(b && psi_io && theta_io && logLik_trace && last_it, "vrx_bulk_fit_cohort: null argument");
     VRX_REQUIRE(b->n_sample >= 1, "vrx_bulk_fit_cohort: no cohort set (vrx_bulk_set_cohort)");
     VRX_REQUIRE(max_iter >= 1, "vrx_bulk_fit_cohort: max_iter must be >= 1");
-    VRX_HIP(hipSetDevice(b->device));
+    VRX_TRY(b->use());
     hipStream_t s = b->stream;
     const int K = b->K, G = b->G, S = (int)b->n_sample;
     const int n_chunk = (S + VRX_BULK_COHORT - 1) / VRX_BULK_COHORT;
@@ -317,12 +293,7 @@ extern "C" int vrx_bulk_fit_cohort(vrx_bulk* b, double* psi_io, double* theta_io
         std::copy(src, src + K, psi_io + (size_t)i * K);
         std::copy(src + K, src + K + G, theta_io + (size_t)i * G);
     }
-    if (ms_out) {
-        float ms = 0.f;
-        VRX_HIP(hipEventElapsedTime(&ms, b->t0, b->t1));
-        *ms_out = ms;
-    }
-    return VRX_OK;
+    return b->ms(0, 1, ms_out);
 }
 
 extern "C" int vrx_bulk_loglik_cohort(vrx_bulk* b, int64_t n_psi, const double* psi, const double* theta,
@@ -330,7 +301,7 @@ extern "C" int vrx_bulk_loglik_cohort(vrx_bulk* b, int64_t n_psi, const double* 
     VRX_REQUIRE(b && psi && theta && out, "vrx_bulk_loglik_cohort: null argument");
     VRX_REQUIRE(b->n_sample >= 1, "vrx_bulk_loglik_cohort: no cohort set (vrx_bulk_set_cohort)");
     VRX_REQUIRE(n_psi >= 1 && n_psi <= (1 << 20), "vrx_bulk_loglik_cohort: 1 <= n_psi <= 2^20");
-    VRX_HIP(hipSetDevice(b->device));
+    VRX_TRY(b->use());
     hipStream_t s = b->stream;
     const int K = b->K, G = b->G, S = (int)b->n_sample;
     const int n_chunk = (S + VRX_BULK_COHORT - 1) / VRX_BULK_COHORT;

@@ -9,7 +9,7 @@
 #include <cstring>
 #include <mutex>
 
-#include "vrx_common.h"
+#include "vrx_handle.h"
 
 namespace {
 struct RcclApi {
@@ -79,11 +79,13 @@ const char* rccl_detail() {
         }                                                                                     \
     } while (0)
 
-struct vrx_comm {
-    int device = 0, rank = 0, world = 1;
+struct vrx_comm : VrxQueue {
+    int rank = 0, world = 1;
     ncclComm_t comm = nullptr;
-    hipStream_t stream = nullptr;
     DevBuf<double> send, recv;
+    ~vrx_comm() {  // (vrx_destroy has drained and closed the stream)
+        if (comm) g_api.CommDestroy(comm);
+    }
 };
 
 static_assert(sizeof(ncclUniqueId) == VRX_UNIQUE_ID_BYTES, "ncclUniqueId size");
@@ -102,9 +104,8 @@ extern "C" int vrx_comm_create(int device, int rank, int world, const uint8_t* i
     *out = nullptr;
     VRX_REQUIRE(world >= 1 && rank >= 0 && rank < world, "vrx_comm_create: bad rank/world");
     if (!load_rccl()) return VRX_ERR_COMM;
-    VRX_HIP(hipSetDevice(device));
-    vrx_comm* c = new vrx_comm();
-    c->device = device;
+    VrxOwned<vrx_comm> c(new vrx_comm());
+    VRX_TRY(c->open("vrx_comm_create", device, 0));
     c->rank = rank;
     c->world = world;
     ncclUniqueId u;
@@ -113,35 +114,18 @@ extern "C" int vrx_comm_create(int device, int rank, int world, const uint8_t* i
     if (r != ncclSuccess) {
         vrx_set_error("ncclCommInitRank(rank %d of %d, device %d) failed: %s%s%s", rank, world, device,
                       g_api.GetErrorString(r), rccl_detail()[0] ? " -- " : "", rccl_detail());
-        delete c;
         return VRX_ERR_COMM;
     }
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        vrx_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
-        g_api.CommDestroy(c->comm);
-        delete c;
-        return VRX_ERR_HIP;
-    }
-    *out = c;
+    *out = c.release();
     return VRX_OK;
 }
 
-extern "C" void vrx_comm_destroy(vrx_comm* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) {
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipStreamDestroy(c->stream);
-    }
-    if (c->comm) g_api.CommDestroy(c->comm);
-    delete c;
-}
+extern "C" void vrx_comm_destroy(vrx_comm* c) { vrx_destroy(c); }
 
 extern "C" int vrx_comm_allgather_f64(vrx_comm* c, const double* local, int64_t n_local,
                                       double* out) {
     VRX_REQUIRE(c && local && out && n_local >= 1, "vrx_comm_allgather_f64: bad argument");
-    VRX_HIP(hipSetDevice(c->device));
+    VRX_TRY(c->use());
     if (c->send.n < (size_t)n_local) VRX_HIP(c->send.alloc((size_t)n_local));
     if (c->recv.n < (size_t)(n_local * c->world)) VRX_HIP(c->recv.alloc((size_t)(n_local * c->world)));
     VRX_HIP(hipMemcpyAsync(c->send.p, local, (size_t)n_local * sizeof(double), hipMemcpyHostToDevice,
@@ -155,7 +139,7 @@ extern "C" int vrx_comm_allgather_f64(vrx_comm* c, const double* local, int64_t 
 
 extern "C" int vrx_comm_barrier(vrx_comm* c) {
     VRX_REQUIRE(c, "vrx_comm_barrier: null comm");
-    VRX_HIP(hipSetDevice(c->device));
+    VRX_TRY(c->use());
     if (c->send.n < 1) VRX_HIP(c->send.alloc(1));
     VRX_HIP(hipMemsetAsync(c->send.p, 0, sizeof(double), c->stream));
     VRX_NCCL(g_api.AllReduce(c->send.p, c->send.p, 1, ncclDouble, ncclSum, c->comm, c->stream));
@@ -165,7 +149,7 @@ extern "C" int vrx_comm_barrier(vrx_comm* c) {
 
 extern "C" int vrx_comm_bcast_f64(vrx_comm* c, double* buf, int64_t n, int root) {
     VRX_REQUIRE(c && buf && n >= 1 && root >= 0 && root < c->world, "vrx_comm_bcast_f64: bad argument");
-    VRX_HIP(hipSetDevice(c->device));
+    VRX_TRY(c->use());
     if (c->recv.n < (size_t)n) VRX_HIP(c->recv.alloc((size_t)n));
     if (c->rank == root)
         VRX_HIP(hipMemcpyAsync(c->recv.p, buf, (size_t)n * sizeof(double), hipMemcpyHostToDevice,
@@ -202,7 +186,7 @@ extern "C" int vrx_comm_bcast_model(vrx_comm* c, vrx_model* m, int root) {
     if (rc) return rc;
     VRX_REQUIRE(b.device == c->device, "vrx_comm_bcast_model: the model lives on device %d, the communicator on %d",
                 b.device, c->device);
-    VRX_HIP(hipSetDevice(c->device));
+    VRX_TRY(c->use());
     VRX_NCCL(g_api.GroupStart());
     for (int i = 0; i < 4; ++i)
         if (b.n[i] > 0) {

@@ -12,7 +12,7 @@
 #include <cstring>
 #include <memory>
 
-#include "vrx_common.h"
+#include "vrx_handle.h"
 #include "vrx_kernels.h"
 #include "vrx_build.h"
 #include "vrx_ambient.h"
@@ -3421,11 +3421,8 @@ static int amb_compact(vrx_problem* p, const int32_t* d_rank, DevBuf<int64_t>& s
     VRX_HIP(hipMemsetAsync(sptr.p, 0, sizeof(int64_t), s));
     vrx_amb_count<FMT><<<nb, 64 * VRX_AMB_CELLS, 0, s>>>(M, p->cell_ptr.p, p->by_cell.ent.p, d_rank, sptr.p + 1);
     VRX_HIP(hipGetLastError());
-    size_t tmp_bytes = 0;
-    VRX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, sptr.p + 1, sptr.p + 1, (size_t)M, s));
     DevBuf<char> tmp;
-    VRX_HIP(tmp.alloc(tmp_bytes));
-    VRX_HIP(hipcub::DeviceScan::InclusiveSum(tmp.p, tmp_bytes, sptr.p + 1, sptr.p + 1, (size_t)M, s));
+    VRX_HIP(vrx_cub(tmp, VRX_CUB_CALL(DeviceScan::InclusiveSum, sptr.p + 1, sptr.p + 1, (size_t)M, s)));
     int64_t total = 0;
     VRX_HIP(hipMemcpyAsync(&total, sptr.p + M, sizeof total, hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
@@ -3481,15 +3478,8 @@ extern "C" int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double
         if (selected[v]) th_sel.insert(th_sel.end(), theta + v * K, theta + (v + 1) * K);
     }
     if (th_sel.empty()) th_sel.assign((size_t)K, 0.5);
-    hipEvent_t ev_t[4] = {};
-    struct EventGuard {
-        hipEvent_t* e;
-        ~EventGuard() {
-            for (int i = 0; i < 4; ++i)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } eg{ev_t};
-    for (auto& e : ev_t) VRX_HIP(hipEventCreate(&e));
+    VrxQueue timer;  // four events on the problem's stream
+    VRX_TRY(timer.events(4));
     DevBuf<int32_t> d_rank, ev, ea, eb;
     DevBuf<double> d_theta, d_psi0, d_psi, d_var, d_llr;
     DevBuf<int32_t> d_it;
@@ -3501,12 +3491,12 @@ extern "C" int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double
     VRX_HIP(d_var.alloc((size_t)(M * K)));
     VRX_HIP(d_llr.alloc((size_t)M));
     VRX_HIP(d_it.alloc((size_t)M));
-    VRX_HIP(hipEventRecord(ev_t[0], s));
+    VRX_HIP(hipEventRecord(timer.ev[0], s));
     int rc = p->by_cell.fmt == VRX_FMT_P32   ? amb_compact<VRX_FMT_P32>(p, d_rank.p, sptr, ev, ea, eb)
              : p->by_cell.fmt == VRX_FMT_P64 ? amb_compact<VRX_FMT_P64>(p, d_rank.p, sptr, ev, ea, eb)
                                              : amb_compact<VRX_FMT_WIDE>(p, d_rank.p, sptr, ev, ea, eb);
     if (rc) return rc;
-    VRX_HIP(hipEventRecord(ev_t[1], s));
+    VRX_HIP(hipEventRecord(timer.ev[1], s));
     int cap = 0;
     size_t lds = 0;
     amb_plan(K, cap, lds);
@@ -3514,19 +3504,14 @@ extern "C" int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double
     vrx_amb_em<<<(unsigned)M, 64, lds, s>>>(K, sptr.p, ev.p, ea.p, eb.p, d_theta.p, d_psi0.p, min_iter, max_iter,
                                             epsilon, cap, d_psi.p, d_var.p, d_llr.p, d_it.p);
     VRX_HIP(hipGetLastError());
-    VRX_HIP(hipEventRecord(ev_t[2], s));
+    VRX_HIP(hipEventRecord(timer.ev[2], s));
     VRX_HIP(hipMemcpyAsync(psi, d_psi.p, (size_t)(M * K) * sizeof(double), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipMemcpyAsync(var, d_var.p, (size_t)(M * K) * sizeof(double), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipMemcpyAsync(llr, d_llr.p, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipMemcpyAsync(n_iter, d_it.p, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipEventRecord(ev_t[3], s));
+    VRX_HIP(hipEventRecord(timer.ev[3], s));
     VRX_HIP(hipStreamSynchronize(s));
-    if (ms3) {
-        float t;
-        for (int i = 0; i < 3; ++i) {
-            VRX_HIP(hipEventElapsedTime(&t, ev_t[i], ev_t[i + 1]));
-            ms3[i] = t;
-        }
-    }
+    if (ms3)
+        for (int i = 0; i < 3; ++i) VRX_TRY(timer.ms(i, i + 1, &ms3[i]));
     return VRX_OK;
 }

@@ -2,18 +2,14 @@
 // include/vireo_hip.h on the kernels of vrx_genematch.h.  A handle owns its stream, events and buffers; nothing
 // here touches a vrx_problem or a vrx_model.
 #include <algorithm>
-#include <memory>
 
 #include <hipcub/hipcub.hpp>
 
-#include "vrx_common.h"
+#include "vrx_handle.h"
 #include "vrx_genematch.h"
 
-struct vrx_genematch {
-    int device = 0;
+struct vrx_genematch : VrxQueue {  // ev: 0, 1 bracket the kernels of a call
     int64_t n_chrom = 0, n_gene = 0, n_snp = 0, total = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
     DevBuf<int32_t> chrom_ptr, gene, grow;  // gene: (start, stop) pairs
     DevBuf<int32_t> code, pos, perm, gap_m1, flag, thr, first, rows;
     DevBuf<uint8_t> single, multi, tmp;
@@ -24,15 +20,7 @@ struct vrx_genematch {
 extern "C" int32_t vrx_genematch_tile(void) { return VRX_GM_TILE; }
 extern "C" int32_t vrx_genematch_block(void) { return VRX_GM_BLOCK; }
 
-extern "C" void vrx_genematch_destroy(vrx_genematch* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+extern "C" void vrx_genematch_destroy(vrx_genematch* h) { vrx_destroy(h); }
 
 static const int64_t VRX_GM_MAX = ((int64_t)1 << 31) - 1024;
 
@@ -51,12 +39,8 @@ extern "C" int vrx_genematch_create(int device, int64_t n_chrom, int64_t n_gene,
     for (int64_t i = 0; i < n_gene; ++i)
         VRX_REQUIRE(start[i] >= 0 && stop[i] >= 0 && row[i] >= 0,
                     "vrx_genematch_create: gene %lld has a negative start, stop or row", (long long)i);
-    if (int e = vrx_use_device("vrx_genematch_create", device)) return e;
-    struct Del {
-        void operator()(vrx_genematch* h) const { vrx_genematch_destroy(h); }
-    };
-    std::unique_ptr<vrx_genematch, Del> h(new vrx_genematch());
-    h->device = device;
+    VrxOwned<vrx_genematch> h(new vrx_genematch());
+    VRX_TRY(h->open("vrx_genematch_create", device, 2));
     h->n_chrom = n_chrom;
     h->n_gene = n_gene;
     std::vector<int32_t> cp((size_t)n_chrom + 1), pairs((size_t)n_gene * 2);
@@ -65,23 +49,12 @@ extern "C" int vrx_genematch_create(int device, int64_t n_chrom, int64_t n_gene,
         pairs[(size_t)i * 2] = start[i];
         pairs[(size_t)i * 2 + 1] = stop[i];
     }
-    VRX_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : h->ev) VRX_HIP(hipEventCreate(&e));
     hipStream_t s = h->stream;
     VRX_HIP(h->chrom_ptr.upload(cp.data(), cp.size(), s));
     VRX_HIP(h->gene.upload(pairs.data(), pairs.size(), s));
     VRX_HIP(h->grow.upload(row, (size_t)n_gene, s));
     VRX_HIP(hipStreamSynchronize(s));  // (the host vectors die at return)
     *out = h.release();
-    return VRX_OK;
-}
-
-static int vrx_gm_elapsed(vrx_genematch* h, double* ms) {
-    if (ms) {
-        float t = 0.f;
-        VRX_HIP(hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
-        *ms = t;
-    }
     return VRX_OK;
 }
 
@@ -112,7 +85,7 @@ extern "C" int vrx_genematch_match(vrx_genematch* h, int64_t n_snp, const int32_
         h->total = 0;
         return VRX_OK;
     }
-    VRX_HIP(hipSetDevice(h->device));
+    VRX_TRY(h->use());
     hipStream_t s = h->stream;
     const size_t N = (size_t)n_snp;
     VRX_HIP(h->code.upload(code, N, s));
@@ -126,9 +99,8 @@ extern "C" int vrx_genematch_match(vrx_genematch* h, int64_t n_snp, const int32_
     VRX_HIP(h->thr.alloc(N));
     VRX_HIP(h->first.alloc(N));
     VRX_HIP(h->multi.alloc(N));
-    size_t tb = 0;
-    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, h->count.p, h->offset.p, N, s));
-    VRX_HIP(h->tmp.alloc(tb ? tb : 1));
+    auto scan_counts = VRX_CUB_CALL(DeviceScan::ExclusiveSum, h->count.p, h->offset.p, N, s);
+    VRX_HIP(vrx_cub(h->tmp, scan_counts, VRX_CUB_SIZE));  // (ahead of the timed region)
     VrxGmArgs& g = h->args;
     g.n_snp = n_snp;
     g.code = h->code.p;
@@ -151,7 +123,7 @@ extern "C" int vrx_genematch_match(vrx_genematch* h, int64_t n_snp, const int32_
     VRX_HIP(hipEventRecord(h->ev[0], s));
     vrx_gm_pass1<<<n_blk, VRX_GM_BLOCK, 0, s>>>(g);
     VRX_HIP(hipGetLastError());
-    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(h->tmp.p, tb, h->count.p, h->offset.p, N, s));
+    VRX_HIP(vrx_cub(h->tmp, scan_counts, VRX_CUB_SIZED));
     VRX_HIP(hipEventRecord(h->ev[1], s));
     VRX_HIP(hipMemcpyAsync(flag, h->flag.p, N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipMemcpyAsync(count, h->count.p, N * sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -159,7 +131,7 @@ extern "C" int vrx_genematch_match(vrx_genematch* h, int64_t n_snp, const int32_
     int64_t total = 0;
     for (size_t i = 0; i < N; ++i) total += count[i];
     h->total = total;
-    return vrx_gm_elapsed(h, ms);
+    return h->ms(0, 1, ms);
 }
 
 extern "C" int vrx_genematch_lists(vrx_genematch* h, int64_t total, int32_t* rows, double* ms) {
@@ -170,7 +142,7 @@ extern "C" int vrx_genematch_lists(vrx_genematch* h, int64_t total, int32_t* row
     VRX_REQUIRE(total == 0 || rows, "vrx_genematch_lists: null output");
     if (ms) *ms = 0.0;
     if (total == 0) return VRX_OK;
-    VRX_HIP(hipSetDevice(h->device));
+    VRX_TRY(h->use());
     hipStream_t s = h->stream;
     VRX_HIP(h->rows.alloc((size_t)total));
     h->args.rows = h->rows.p;
@@ -181,29 +153,18 @@ extern "C" int vrx_genematch_lists(vrx_genematch* h, int64_t total, int32_t* row
     VRX_HIP(hipEventRecord(h->ev[1], s));
     VRX_HIP(hipMemcpyAsync(rows, h->rows.p, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
-    return vrx_gm_elapsed(h, ms);
+    return h->ms(0, 1, ms);
 }
 
 // ---- gene counts ----------------------------------------------------------------------------------
 
-struct vrx_genecount {
-    int device = 0;
+struct vrx_genecount : VrxQueue {  // ev: 0, 1 bracket the kernels of create
     int64_t n_out = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
     DevBuf<uint64_t> out_key;
     DevBuf<int64_t> out_ad, out_dp;
 };
 
-extern "C" void vrx_genecount_destroy(vrx_genecount* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+extern "C" void vrx_genecount_destroy(vrx_genecount* h) { vrx_destroy(h); }
 
 static unsigned vrx_gc_blocks(int64_t n) { return (unsigned)((n + VRX_GC_BLOCK - 1) / VRX_GC_BLOCK); }
 
@@ -235,19 +196,14 @@ extern "C" int vrx_genecount_create(int device, int64_t n_var, int64_t n_cell, i
         VRX_REQUIRE(total < VRX_GM_MAX, "vrx_genecount_create: 2^31 - 1024 (entry, gene) pairs or more");
     }
     if (int e = vrx_use_device("vrx_genecount_create", device)) return e;
-    struct Del {
-        void operator()(vrx_genecount* h) const { vrx_genecount_destroy(h); }
-    };
-    std::unique_ptr<vrx_genecount, Del> h(new vrx_genecount());
-    h->device = device;
+    VrxOwned<vrx_genecount> h(new vrx_genecount());
     *n_out = 0;
     if (ms) *ms = 0.0;
-    if (total == 0) {
+    if (total == 0) {  // nothing to count: a handle without a stream
         *out = h.release();
         return VRX_OK;
     }
-    VRX_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : h->ev) VRX_HIP(hipEventCreate(&e));
+    VRX_TRY(h->open("vrx_genecount_create", device, 2));
     hipStream_t s = h->stream;
     const size_t E = (size_t)nnz, T = (size_t)total;
     DevBuf<int64_t> d_colptr, d_gptr, cnt, off;
@@ -270,26 +226,23 @@ extern "C" int vrx_genecount_create(int device, int64_t n_var, int64_t n_cell, i
     VRX_HIP(seg.alloc(T));
     int bits = 1;  // of the largest key, n_cell n_gene - 1 < 2^62
     while (bits < 64 && ((uint64_t)n_cell * (uint64_t)n_gene - 1) >> bits) ++bits;
-    size_t t1 = 0, t2 = 0, t3 = 0;
-    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, cnt.p, off.p, E, s));
-    VRX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t2, key.p, key2.p, val.p, val2.p, T, 0, bits, s));
-    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, head.p, seg.p, T, s));
-    const size_t tb = std::max(std::max(t1, t2), std::max(t3, (size_t)1));
-    VRX_HIP(tmp.alloc(tb));
+    auto scan_counts = VRX_CUB_CALL(DeviceScan::ExclusiveSum, cnt.p, off.p, E, s);
+    auto sort_pairs = VRX_CUB_CALL(DeviceRadixSort::SortPairs, key.p, key2.p, val.p, val2.p, T, 0, bits, s);
+    auto scan_heads = VRX_CUB_CALL(DeviceScan::ExclusiveSum, head.p, seg.p, T, s);
+    VRX_HIP(vrx_cub(tmp, scan_counts, VRX_CUB_SIZE));  // (all three ahead of the timed region)
+    VRX_HIP(vrx_cub(tmp, sort_pairs, VRX_CUB_SIZE));
+    VRX_HIP(vrx_cub(tmp, scan_heads, VRX_CUB_SIZE));
     VRX_HIP(hipEventRecord(h->ev[0], s));
     vrx_gc_count<<<vrx_gc_blocks(nnz), VRX_GC_BLOCK, 0, s>>>(nnz, d_row.p, d_gptr.p, cnt.p);
     VRX_HIP(hipGetLastError());
-    t1 = tb;
-    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, t1, cnt.p, off.p, E, s));
+    VRX_HIP(vrx_cub(tmp, scan_counts, VRX_CUB_SIZED));
     vrx_gc_emit<<<vrx_gc_blocks(nnz), VRX_GC_BLOCK, 0, s>>>(nnz, n_cell, n_gene, d_colptr.p, d_row.p, d_ad.p, d_dp.p,
                                                             d_gptr.p, d_gid.p, off.p, key.p, val.p);
     VRX_HIP(hipGetLastError());
-    t2 = tb;
-    VRX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, t2, key.p, key2.p, val.p, val2.p, T, 0, bits, s));
+    VRX_HIP(vrx_cub(tmp, sort_pairs, VRX_CUB_SIZED));
     vrx_gc_heads<<<vrx_gc_blocks(total), VRX_GC_BLOCK, 0, s>>>(total, key2.p, head.p);
     VRX_HIP(hipGetLastError());
-    t3 = tb;
-    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, t3, head.p, seg.p, T, s));
+    VRX_HIP(vrx_cub(tmp, scan_heads, VRX_CUB_SIZED));
     int32_t last[2] = {0, 0};
     VRX_HIP(hipMemcpyAsync(&last[0], seg.p + (T - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipMemcpyAsync(&last[1], head.p + (T - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -305,11 +258,7 @@ extern "C" int vrx_genecount_create(int device, int64_t n_var, int64_t n_cell, i
     VRX_HIP(hipGetLastError());
     VRX_HIP(hipEventRecord(h->ev[1], s));
     VRX_HIP(hipStreamSynchronize(s));
-    if (ms) {
-        float t = 0.f;
-        VRX_HIP(hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
-        *ms = t;
-    }
+    VRX_TRY(h->ms(0, 1, ms));
     h->n_out = n_seg;
     *n_out = n_seg;
     *out = h.release();
@@ -320,7 +269,7 @@ extern "C" int vrx_genecount_read(vrx_genecount* h, int64_t* key, int64_t* ad, i
     VRX_REQUIRE(h, "vrx_genecount_read: null handle");
     if (h->n_out == 0) return VRX_OK;
     VRX_REQUIRE(key && ad && dp, "vrx_genecount_read: null output");
-    VRX_HIP(hipSetDevice(h->device));
+    VRX_TRY(h->use());
     const size_t n = (size_t)h->n_out;
     VRX_HIP(hipMemcpyAsync(key, h->out_key.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     VRX_HIP(hipMemcpyAsync(ad, h->out_ad.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));

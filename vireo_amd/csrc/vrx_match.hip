@@ -2,20 +2,11 @@
 // stream, events and buffers; nothing here touches a vrx_problem or a vrx_model.
 #include <algorithm>
 
-#include "vrx_common.h"
+#include "vrx_handle.h"
 #include "vrx_match.h"
 
 // the stream and the two events of one vrx_geno_dist call (released on every return path)
-struct GenoCall {
-    hipStream_t stream = nullptr;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    ~GenoCall() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (t0) (void)hipEventDestroy(t0);
-        if (t1) (void)hipEventDestroy(t1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
+using GenoCall = VrxQueue;
 
 extern "C" int vrx_geno_dist(int device, int64_t n_var, int64_t k1, int64_t k2, int64_t n_gt, const double* X,
                              const double* Z, int64_t block_vars, double* D, double* ms_out) {
@@ -39,7 +30,8 @@ extern "C" int vrx_geno_dist(int device, int64_t n_var, int64_t k1, int64_t k2, 
                       (long long)k1, (long long)k2, (long long)n_gt, VRX_GENO_LDS);
         return VRX_ERR_UNSUPPORTED;
     }
-    if (int e = vrx_use_device("vrx_geno_dist", device)) return e;
+    GenoCall c;
+    VRX_TRY(c.open("vrx_geno_dist", device, 2));
     hipDeviceProp_t prop;
     VRX_HIP(hipGetDeviceProperties(&prop, device));
     // variants per slab: each operand's slab at most 256 MiB by default, and below 2^31 - 1 variants
@@ -52,10 +44,6 @@ extern "C" int vrx_geno_dist(int device, int64_t n_var, int64_t k1, int64_t k2, 
     // (at least 4 variant tiles per chunk where the slab has them: fewer partials to add)
     const int n_chunk = (int)std::max<int64_t>(1, std::min<int64_t>((n_vt + 3) / 4, resident / n_ij));
     const int64_t n_cell = k1 * k2;
-    GenoCall c;
-    VRX_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-    VRX_HIP(hipEventCreate(&c.t0));
-    VRX_HIP(hipEventCreate(&c.t1));
     DevBuf<double> dX, dZ, part, acc;
     VRX_HIP(dX.alloc((size_t)(bv * k1 * n_gt)));
     if (Z) VRX_HIP(dZ.alloc((size_t)(bv * k2 * n_gt)));
@@ -63,7 +51,7 @@ extern "C" int vrx_geno_dist(int device, int64_t n_var, int64_t k1, int64_t k2, 
     VRX_HIP(acc.alloc((size_t)n_cell));
     const double* pZ = Z ? dZ.p : dX.p;
     hipStream_t s = c.stream;
-    double ms = 0.0;
+    double ms = 0.0, t = 0.0;
     for (int64_t n0 = 0; n0 < n_var; n0 += bv) {
         const int64_t nv = std::min(bv, n_var - n0);
         const bool last = n0 + nv == n_var;
@@ -74,7 +62,7 @@ extern "C" int vrx_geno_dist(int device, int64_t n_var, int64_t k1, int64_t k2, 
                                    hipMemcpyHostToDevice, s));
         // (a short last slab keeps the grid: a chunk without variant tiles writes zeros)
         const dim3 grid((unsigned)n_chunk, (unsigned)n_ij);
-        VRX_HIP(hipEventRecord(c.t0, s));
+        VRX_HIP(hipEventRecord(c.ev[0], s));
         if (G == 3)
             vrx_geno_pass<3><<<grid, VRX_GENO_BLOCK, lds, s>>>((int)nv, (int)k1, (int)k2, h, dX.p, pZ, part.p);
         else
@@ -82,10 +70,9 @@ extern "C" int vrx_geno_dist(int device, int64_t n_var, int64_t k1, int64_t k2, 
         vrx_geno_sum<<<(unsigned)((n_cell + 63) / 64), 64 * VRX_GENO_SUM_RUNS, 0, s>>>(
             n_chunk, n_cell, part.p, acc.p, n0 == 0, last ? (double)n_var * (double)n_gt : 0.0);
         VRX_HIP(hipGetLastError());
-        VRX_HIP(hipEventRecord(c.t1, s));
+        VRX_HIP(hipEventRecord(c.ev[1], s));
         VRX_HIP(hipStreamSynchronize(s));  // (the next upload overwrites the slab)
-        float t = 0.f;
-        VRX_HIP(hipEventElapsedTime(&t, c.t0, c.t1));
+        VRX_TRY(c.ms(0, 1, &t));
         ms += t;
     }
     VRX_HIP(hipMemcpyAsync(D, acc.p, (size_t)n_cell * sizeof(double), hipMemcpyDeviceToHost, s));

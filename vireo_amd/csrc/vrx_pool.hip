@@ -3,17 +3,13 @@
 // nothing here touches a vrx_problem or a vrx_model.
 #include <algorithm>
 #include <climits>
-#include <memory>
 
-#include "vrx_common.h"
+#include "vrx_handle.h"
 #include "vrx_pool.h"
 
-struct vrx_pool {
-    int device = 0;
+struct vrx_pool : VrxQueue {  // ev: 0, 1 bracket the count pass and its scan, 2, 3 the emit pass
     int64_t n_var = 0, n_src = 0, n_pool = -1, total = 0;
     std::vector<int64_t> colptr;  // host copy: the lengths order the columns of a plan
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     DevBuf<int64_t> d_colptr, len, out, blk;
     DevBuf<int32_t> row, ad, dp, cols, src0, src1, orow, oad, odp, bad;
 };
@@ -21,15 +17,7 @@ struct vrx_pool {
 extern "C" int32_t vrx_pool_wave_limit(void) { return VRX_POOL_WAVE_LIMIT; }
 extern "C" int32_t vrx_pool_scan_block(void) { return VRX_POOL_SCAN_BLOCK; }
 
-extern "C" void vrx_pool_destroy(vrx_pool* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+extern "C" void vrx_pool_destroy(vrx_pool* h) { vrx_destroy(h); }
 
 static const int64_t VRX_POOL_MAX = ((int64_t)1 << 31) - 1024;
 
@@ -53,17 +41,11 @@ extern "C" int vrx_pool_create(int device, int64_t n_var, int64_t n_src, const i
             prev = rowidx[e];
         }
     }
-    if (int e = vrx_use_device("vrx_pool_create", device)) return e;
-    struct Del {
-        void operator()(vrx_pool* h) const { vrx_pool_destroy(h); }
-    };
-    std::unique_ptr<vrx_pool, Del> h(new vrx_pool());
-    h->device = device;
+    VrxOwned<vrx_pool> h(new vrx_pool());
+    VRX_TRY(h->open("vrx_pool_create", device, 4));
     h->n_var = n_var;
     h->n_src = n_src;
     h->colptr.assign(colptr, colptr + n_src + 1);
-    VRX_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : h->ev) VRX_HIP(hipEventCreate(&e));
     hipStream_t s = h->stream;
     VRX_HIP(h->d_colptr.upload(colptr, (size_t)n_src + 1, s));
     VRX_HIP(h->row.upload(rowidx, (size_t)nnz, s));
@@ -116,7 +98,7 @@ extern "C" int vrx_pool_run(vrx_pool* h, int64_t n_pool, const int32_t* src0, co
         h->n_pool = 0;
         return VRX_OK;
     }
-    VRX_HIP(hipSetDevice(h->device));
+    VRX_TRY(h->use());
     hipStream_t s = h->stream;
     VRX_HIP(h->cols.upload(cols.data(), P, s));
     VRX_HIP(h->src0.upload(src0, P, s));
@@ -173,7 +155,7 @@ extern "C" int vrx_pool_run(vrx_pool* h, int64_t n_pool, const int32_t* src0, co
     VRX_HIP(h->orow.alloc((size_t)total));
     VRX_HIP(h->oad.alloc((size_t)total));
     VRX_HIP(h->odp.alloc((size_t)total));
-    float t0 = 0.f, t1 = 0.f;
+    double t0 = 0.0, t1 = 0.0;
     if (total > 0) {
         g.orow = h->orow.p;
         g.oad = h->oad.p;
@@ -186,9 +168,9 @@ extern "C" int vrx_pool_run(vrx_pool* h, int64_t n_pool, const int32_t* src0, co
     int32_t first = INT32_MAX;
     VRX_HIP(hipMemcpyAsync(&first, h->bad.p, sizeof first, hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
-    VRX_HIP(hipEventElapsedTime(&t0, h->ev[0], h->ev[1]));
-    if (total > 0) VRX_HIP(hipEventElapsedTime(&t1, h->ev[2], h->ev[3]));
-    if (ms) *ms = (double)t0 + (double)t1;
+    VRX_TRY(h->ms(0, 1, &t0));
+    if (total > 0) VRX_TRY(h->ms(2, 3, &t1));
+    if (ms) *ms = t0 + t1;
     if (first != INT32_MAX) *bad = first;
     h->n_pool = n_pool;
     h->total = total;
@@ -200,7 +182,7 @@ extern "C" int vrx_pool_read(vrx_pool* h, int32_t* rowidx, int32_t* ad, int32_t*
     VRX_REQUIRE(h->n_pool >= 0, "vrx_pool_read: no vrx_pool_run before it");
     if (h->total == 0) return VRX_OK;
     VRX_REQUIRE(rowidx && ad && dp, "vrx_pool_read: null output");
-    VRX_HIP(hipSetDevice(h->device));
+    VRX_TRY(h->use());
     const size_t n = (size_t)h->total * sizeof(int32_t);
     VRX_HIP(hipMemcpyAsync(rowidx, h->orow.p, n, hipMemcpyDeviceToHost, h->stream));
     VRX_HIP(hipMemcpyAsync(ad, h->oad.p, n, hipMemcpyDeviceToHost, h->stream));

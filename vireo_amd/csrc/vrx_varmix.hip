@@ -1,17 +1,13 @@
 // Per-variant clone mixtures: the vrx_varmix_* entries of include/vireo_hip.h on the kernel of vrx_varmix.h.
 // A handle owns its stream, events and buffers; nothing here touches a vrx_problem or a vrx_model.
 #include <algorithm>
-#include <memory>
 #include <numeric>
 
-#include "vrx_common.h"
+#include "vrx_handle.h"
 #include "vrx_varmix.h"
 
-struct vrx_varmix {
-    int device = 0;
+struct vrx_varmix : VrxQueue {  // ev: 0, 1 bracket the fit kernel
     int64_t n_var = 0, nnz = 0, n_long = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
     DevBuf<int32_t> perm, len, pairs, n_iter, warn;
     DevBuf<int64_t> start;
     DevBuf<double> elbo, mu, sum, size, trace;  // elbo: K components | one component
@@ -20,15 +16,7 @@ struct vrx_varmix {
 
 extern "C" int32_t vrx_varmix_wave_rows(void) { return VRX_VM_WAVE_ROWS; }
 
-extern "C" void vrx_varmix_destroy(vrx_varmix* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
+extern "C" void vrx_varmix_destroy(vrx_varmix* h) { vrx_destroy(h); }
 
 extern "C" int vrx_varmix_create(int device, int64_t n_var, int64_t nnz, const int64_t* rowptr, const int32_t* ad,
                                  const int32_t* dp, vrx_varmix** out) {
@@ -45,12 +33,8 @@ extern "C" int vrx_varmix_create(int device, int64_t n_var, int64_t nnz, const i
         VRX_REQUIRE(dp[e] > 0 && ad[e] >= 0 && ad[e] <= dp[e],
                     "vrx_varmix_create: entry %lld has ad = %d, dp = %d (need 0 <= ad <= dp, dp > 0)", (long long)e,
                     (int)ad[e], (int)dp[e]);
-    if (int e = vrx_use_device("vrx_varmix_create", device)) return e;
-    struct Del {
-        void operator()(vrx_varmix* h) const { vrx_varmix_destroy(h); }
-    };
-    std::unique_ptr<vrx_varmix, Del> h(new vrx_varmix());
-    h->device = device;
+    VrxOwned<vrx_varmix> h(new vrx_varmix());
+    VRX_TRY(h->open("vrx_varmix_create", device, 2));
     h->n_var = n_var;
     h->nnz = nnz;
     // rows longest first (equal lengths in input order), each padded to whole pairs of entries
@@ -72,8 +56,6 @@ extern "C" int vrx_varmix_create(int device, int64_t n_var, int64_t nnz, const i
             pairs[(size_t)(start[v] + e) * 2] = ad[rowptr[v] + e];
             pairs[(size_t)(start[v] + e) * 2 + 1] = dp[rowptr[v] + e];
         }
-    VRX_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : h->ev) VRX_HIP(hipEventCreate(&e));
     hipStream_t s = h->stream;
     VRX_HIP(h->perm.upload(perm.data(), N, s));
     VRX_HIP(h->len.upload(len.data(), N, s));
@@ -116,7 +98,7 @@ extern "C" int vrx_varmix_fit(vrx_varmix* h, int32_t n_clone, int32_t max_iter, 
     VRX_REQUIRE(N == 0 || (elbo_k && elbo_one && n_iter && warn), "vrx_varmix_fit: null output");
     if (ms) *ms = 0.0;
     if (N == 0) return VRX_OK;
-    VRX_HIP(hipSetDevice(h->device));
+    VRX_TRY(h->use());
     hipStream_t s = h->stream;
     const size_t n_trace = trace ? N * (size_t)max_iter : 0;
     if (trace) {
@@ -167,10 +149,5 @@ extern "C" int vrx_varmix_fit(vrx_varmix* h, int32_t n_clone, int32_t max_iter, 
     if (size) VRX_HIP(hipMemcpyAsync(size, g.size, NK * sizeof(double), hipMemcpyDeviceToHost, s));
     if (trace) VRX_HIP(hipMemcpyAsync(trace, g.trace, n_trace * sizeof(double), hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
-    if (ms) {
-        float t = 0.f;
-        VRX_HIP(hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
-        *ms = t;
-    }
-    return VRX_OK;
+    return h->ms(0, 1, ms);
 }

@@ -3,11 +3,10 @@
 // A handle owns its stream and buffers; nothing here touches a vrx_problem or a vrx_model.
 #include <algorithm>
 #include <chrono>
-#include <memory>
 
 #include <hipcub/hipcub.hpp>
 
-#include "vrx_common.h"
+#include "vrx_handle.h"
 #include "vrx_cellvcf.h"
 #include "vrx_vcf.h"
 
@@ -19,13 +18,24 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 }
 }  // namespace
 
-struct vrx_vcf {
-    int device = 0;
+// The text front end of both readers: a slab of VCF text on the device and where its lines start.
+struct VcfText {
+    DevBuf<uint8_t> text, flag, tmp;  // tmp: the temporary storage of every hipCUB call of the handle
+    DevBuf<uint32_t> lstart, ctl;     // ctl: 0 lines of the slab, 1 status, 2 and 3 the reader's own counts
+    int create(hipStream_t s) {
+        VRX_HIP(ctl.alloc(4));
+        VRX_HIP(hipMemsetAsync(ctl.p, 0, 4 * sizeof(uint32_t), s));
+        return VRX_OK;
+    }
+    int lines(hipStream_t s, const char* host, size_t n, uint32_t status, uint32_t out_ctl[4], double* seconds,
+              std::chrono::steady_clock::time_point* t0);
+};
+
+struct vrx_vcf : VrxQueue {
     int32_t tag = 0, n_sample = 0, biallelic_only = 1, mode = -1;
     bool matching = false;
     int64_t n_ids = 0;
     uint32_t table_status = 0;
-    hipStream_t stream = nullptr;
     // cell table
     DevBuf<uint8_t> id_bytes;
     DevBuf<int64_t> id_off;
@@ -35,8 +45,8 @@ struct vrx_vcf {
     // slab
     uint32_t n = 0, n_lines = 0;
     int64_t n_matched = 0, line_base = 0, kept_total = 0;
-    DevBuf<uint8_t> text, flag, match, tmp;
-    DevBuf<uint32_t> lstart, ctl;  // ctl: 0 lines of the slab, 1 status, 2 matched, 3 tagged
+    VcfText in;  // its ctl: 2 matched, 3 tagged
+    DevBuf<uint8_t> match;
     DevBuf<int32_t> kept, tagged, ord, mlist;
     DevBuf<VrxVcfLine> rec;
     // rows
@@ -45,22 +55,9 @@ struct vrx_vcf {
     DevBuf<int32_t> rflag;
 };
 
-template <typename T>
-static hipError_t vrx_vcf_reserve(DevBuf<T>& b, size_t count) {
-    return b.n >= count ? hipSuccess : b.alloc(count + count / 8);
-}
-
 extern "C" int32_t vrx_vcf_chunk(void) { return VRX_VCF_CHUNK; }
 
-extern "C" void vrx_vcf_destroy(vrx_vcf* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipStreamDestroy(h->stream);
-    }
-    delete h;
-}
+extern "C" void vrx_vcf_destroy(vrx_vcf* h) { vrx_destroy(h); }
 
 extern "C" int vrx_vcf_create(int device, int32_t tag, int32_t n_sample, int32_t biallelic_only, int64_t n_ids,
                               const char* id_bytes, const int64_t* id_off, const double* pl_table, vrx_vcf** out) {
@@ -75,21 +72,15 @@ extern "C" int vrx_vcf_create(int device, int32_t tag, int32_t n_sample, int32_t
             VRX_REQUIRE(id_off[i] <= id_off[i + 1], "vrx_vcf_create: id_off decreases at id %lld", (long long)i);
         VRX_REQUIRE(id_off[n_ids] == 0 || id_bytes, "vrx_vcf_create: ids need their bytes");
     }
-    if (int e = vrx_use_device("vrx_vcf_create", device)) return e;
-    struct Del {
-        void operator()(vrx_vcf* h) const { vrx_vcf_destroy(h); }
-    };
-    std::unique_ptr<vrx_vcf, Del> h(new vrx_vcf());
-    h->device = device;
+    VrxOwned<vrx_vcf> h(new vrx_vcf());
+    VRX_TRY(h->open("vrx_vcf_create", device, 0));
     h->tag = tag;
     h->n_sample = n_sample;
     h->biallelic_only = biallelic_only != 0;
     h->matching = n_ids >= 0;
     h->n_ids = std::max<int64_t>(n_ids, 0);
-    VRX_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     hipStream_t s = h->stream;
-    VRX_HIP(h->ctl.alloc(4));
-    VRX_HIP(hipMemsetAsync(h->ctl.p, 0, 4 * sizeof(uint32_t), s));
+    VRX_TRY(h->in.create(s));
     if (pl_table) VRX_HIP(h->pl_table.upload(pl_table, VRX_VCF_PL_MAX + 1, s));
     const size_t N = (size_t)h->n_ids;
     if (N > 0) {
@@ -105,14 +96,12 @@ extern "C" int vrx_vcf_create(int device, int32_t tag, int32_t n_sample, int32_t
         const unsigned n_blk = (unsigned)((N + VRX_VCF_BLOCK - 1) / VRX_VCF_BLOCK);
         vrx_vcf_hash_ids<<<n_blk, VRX_VCF_BLOCK, 0, s>>>(h->id_bytes.p, h->id_off.p, (int64_t)N, hash_in.p, idx_in.p);
         VRX_HIP(hipGetLastError());
-        size_t tb = 0;
-        VRX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, hash_in.p, h->hash.p, idx_in.p, h->idx.p, (int)N, 0, 64, s));
-        VRX_HIP(vrx_vcf_reserve(h->tmp, tb));
-        VRX_HIP(hipcub::DeviceRadixSort::SortPairs(h->tmp.p, tb, hash_in.p, h->hash.p, idx_in.p, h->idx.p, (int)N, 0, 64, s));
+        VRX_HIP(vrx_cub(h->in.tmp, VRX_CUB_CALL(DeviceRadixSort::SortPairs, hash_in.p, h->hash.p, idx_in.p, h->idx.p,
+                                                (int)N, 0, 64, s)));
         vrx_vcf_table_check<<<n_blk, VRX_VCF_BLOCK, 0, s>>>(h->id_bytes.p, h->id_off.p, (int64_t)N, h->hash.p, h->idx.p,
-                                                            h->ctl.p + 1);
+                                                            h->in.ctl.p + 1);
         VRX_HIP(hipGetLastError());
-        VRX_HIP(hipMemcpyAsync(&h->table_status, h->ctl.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        VRX_HIP(hipMemcpyAsync(&h->table_status, h->in.ctl.p + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         VRX_HIP(hipStreamSynchronize(s));  // (the staging buffers die at return)
     }
     VRX_HIP(hipStreamSynchronize(s));
@@ -124,7 +113,7 @@ extern "C" int vrx_vcf_begin(vrx_vcf* h, int32_t mode, int32_t* status) {
     VRX_REQUIRE(h && status, "vrx_vcf_begin: null argument");
     VRX_REQUIRE(h->matching ? (mode >= 0 && mode <= 2) : mode == -1,
                 "vrx_vcf_begin: mode is 0, 1 or 2 with a cell table and -1 without");
-    VRX_HIP(hipSetDevice(h->device));
+    VRX_TRY(h->use());
     h->mode = mode;
     h->n = h->n_lines = 0;
     h->n_matched = h->line_base = h->kept_total = 0;
@@ -134,12 +123,46 @@ extern "C" int vrx_vcf_begin(vrx_vcf* h, int32_t mode, int32_t* status) {
     return VRX_OK;
 }
 
+// Uploads the n > 0 bytes (seconds[0]), marks the line starts with the status word seeded by `status`, reads
+// the control words back into ctl and, if the status is still 0, compacts the ctl[0] line starts into lstart.
+// With a status set nothing more is done and seconds[1] is closed; otherwise *t0 is where seconds[1] began.
+int VcfText::lines(hipStream_t s, const char* host, size_t n, uint32_t status, uint32_t out_ctl[4], double* seconds,
+                   std::chrono::steady_clock::time_point* t0) {
+    const size_t n_pad = (n + VRX_VCF_MARK_BYTES - 1) / VRX_VCF_MARK_BYTES * VRX_VCF_MARK_BYTES;
+    *t0 = std::chrono::steady_clock::now();
+    VRX_HIP(vrx_reserve(text, n_pad + 2 * VRX_VCF_MARK_BYTES));
+    VRX_HIP(vrx_reserve(flag, n_pad + VRX_VCF_MARK_BYTES));
+    VRX_HIP(hipMemcpyAsync(text.p, host, n, hipMemcpyHostToDevice, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    if (seconds) seconds[0] = seconds_since(*t0);
+    *t0 = std::chrono::steady_clock::now();
+    const uint32_t seed[4] = {0, status, 0, 0};
+    VRX_HIP(hipMemcpyAsync(ctl.p, seed, sizeof seed, hipMemcpyHostToDevice, s));
+    const size_t per_block = (size_t)VRX_VCF_BLOCK * VRX_VCF_MARK_BYTES;
+    vrx_vcf_mark<<<(unsigned)((n + per_block - 1) / per_block), VRX_VCF_BLOCK, 0, s>>>(text.p, (uint32_t)n, flag.p,
+                                                                                        ctl.p, ctl.p + 1);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(hipMemcpyAsync(out_ctl, ctl.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    const size_t L = out_ctl[0];
+    // a line that load_VCF can index has 8 tabs and a line end, the last one may lack the line end
+    if (L * 9 > n + 1) out_ctl[1] |= VRX_VCF_ST_SHORT;
+    if (out_ctl[1]) {
+        if (seconds) seconds[1] = seconds_since(*t0);
+        return VRX_OK;
+    }
+    VRX_HIP(vrx_reserve(lstart, L));
+    VRX_HIP(vrx_cub(tmp, VRX_CUB_CALL(DeviceSelect::Flagged, hipcub::CountingInputIterator<uint32_t>(0), flag.p,
+                                      lstart.p, ctl.p + 2, (int)n, s)));
+    return VRX_OK;
+}
+
 extern "C" int vrx_vcf_slab(vrx_vcf* h, const char* text, int64_t n_bytes, int64_t* info, double* seconds) {
     VRX_REQUIRE(h && info, "vrx_vcf_slab: null argument");
     VRX_REQUIRE(h->mode >= -1 && (h->mode >= 0) == h->matching, "vrx_vcf_slab: vrx_vcf_begin first");
     VRX_REQUIRE(n_bytes >= 0 && n_bytes < ((int64_t)1 << 31) - 64, "vrx_vcf_slab: a slab holds fewer than 2^31 - 64 bytes");
     VRX_REQUIRE(n_bytes == 0 || text, "vrx_vcf_slab: null text");
-    VRX_HIP(hipSetDevice(h->device));
+    VRX_TRY(h->use());
     hipStream_t s = h->stream;
     info[0] = info[1] = info[2] = 0;
     info[3] = (int64_t)h->table_status;
@@ -150,52 +173,25 @@ extern "C" int vrx_vcf_slab(vrx_vcf* h, const char* text, int64_t n_bytes, int64
     h->n_matched = 0;
     if (n_bytes == 0) return VRX_OK;
     const size_t n = (size_t)n_bytes;
-    const size_t n_pad = (n + VRX_VCF_MARK_BYTES - 1) / VRX_VCF_MARK_BYTES * VRX_VCF_MARK_BYTES;
-    auto t0 = std::chrono::steady_clock::now();
-    VRX_HIP(vrx_vcf_reserve(h->text, n_pad + 2 * VRX_VCF_MARK_BYTES));
-    VRX_HIP(vrx_vcf_reserve(h->flag, n_pad + VRX_VCF_MARK_BYTES));
-    VRX_HIP(hipMemcpyAsync(h->text.p, text, n, hipMemcpyHostToDevice, s));
-    VRX_HIP(hipStreamSynchronize(s));
-    if (seconds) seconds[0] = seconds_since(t0);
-    t0 = std::chrono::steady_clock::now();
-    uint32_t ctl[4] = {0, h->table_status, 0, 0};
-    VRX_HIP(hipMemcpyAsync(h->ctl.p, ctl, sizeof ctl, hipMemcpyHostToDevice, s));
-    const size_t per_block = (size_t)VRX_VCF_BLOCK * VRX_VCF_MARK_BYTES;
-    vrx_vcf_mark<<<(unsigned)((n + per_block - 1) / per_block), VRX_VCF_BLOCK, 0, s>>>(h->text.p, (uint32_t)n, h->flag.p,
-                                                                                        h->ctl.p, h->ctl.p + 1);
-    VRX_HIP(hipGetLastError());
-    VRX_HIP(hipMemcpyAsync(ctl, h->ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipStreamSynchronize(s));
-    const size_t L = ctl[0];
-    // a line that load_VCF can index has 8 tabs and a line end, the last one may lack the line end
-    if (L * 9 > n + 1) ctl[1] |= VRX_VCF_ST_SHORT;
+    uint32_t ctl[4];
+    std::chrono::steady_clock::time_point t0;
+    VRX_TRY(h->in.lines(s, text, n, h->table_status, ctl, seconds, &t0));
     if (ctl[1]) {  // the caller takes the host path: nothing more to do here
         info[3] = ctl[1];
-        if (seconds) seconds[1] = seconds_since(t0);
         return VRX_OK;
     }
+    const size_t L = ctl[0];
     h->n_lines = (uint32_t)L;
-    VRX_HIP(vrx_vcf_reserve(h->lstart, L));
-    VRX_HIP(vrx_vcf_reserve(h->kept, L));
-    VRX_HIP(vrx_vcf_reserve(h->tagged, L));
-    VRX_HIP(vrx_vcf_reserve(h->ord, L));
-    VRX_HIP(vrx_vcf_reserve(h->mlist, L));
-    VRX_HIP(vrx_vcf_reserve(h->match, L));
-    VRX_HIP(vrx_vcf_reserve(h->rec, L));
-    size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0;
-    hipcub::CountingInputIterator<uint32_t> bytes_it(0);
-    hipcub::CountingInputIterator<int32_t> lines_it(0);
-    VRX_HIP(hipcub::DeviceSelect::Flagged(nullptr, t1, bytes_it, h->flag.p, h->lstart.p, h->ctl.p + 2, (int)n, s));
-    VRX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, t2, h->kept.p, h->ord.p, (int)L, s));
-    VRX_HIP(hipcub::DeviceSelect::Flagged(nullptr, t3, lines_it, h->match.p, h->mlist.p, h->ctl.p + 2, (int)L, s));
-    VRX_HIP(hipcub::DeviceReduce::Sum(nullptr, t4, h->tagged.p, reinterpret_cast<int32_t*>(h->ctl.p + 3), (int)L, s));
-    const size_t tb = std::max(std::max(t1, t2), std::max(t3, t4));
-    VRX_HIP(vrx_vcf_reserve(h->tmp, tb));
-    VRX_HIP(hipcub::DeviceSelect::Flagged(h->tmp.p, t1, bytes_it, h->flag.p, h->lstart.p, h->ctl.p + 2, (int)n, s));
+    VRX_HIP(vrx_reserve(h->kept, L));
+    VRX_HIP(vrx_reserve(h->tagged, L));
+    VRX_HIP(vrx_reserve(h->ord, L));
+    VRX_HIP(vrx_reserve(h->mlist, L));
+    VRX_HIP(vrx_reserve(h->match, L));
+    VRX_HIP(vrx_reserve(h->rec, L));
     VrxVcfLinesArgs g;
-    g.text = h->text.p;
+    g.text = h->in.text.p;
     g.n = (uint32_t)n;
-    g.lstart = h->lstart.p;
+    g.lstart = h->in.lstart.p;
     g.n_lines = (uint32_t)L;
     g.tag = h->tag;
     g.biallelic_only = h->biallelic_only;
@@ -210,14 +206,16 @@ extern "C" int vrx_vcf_slab(vrx_vcf* h, const char* text, int64_t n_bytes, int64
     g.tagged = h->tagged.p;
     g.match = h->match.p;
     g.rec = h->rec.p;
-    g.status = h->ctl.p + 1;
+    g.status = h->in.ctl.p + 1;
     vrx_vcf_lines<<<(unsigned)((L + VRX_VCF_WAVES - 1) / VRX_VCF_WAVES), VRX_VCF_BLOCK, 0, s>>>(g);
     VRX_HIP(hipGetLastError());
-    VRX_HIP(hipcub::DeviceScan::InclusiveSum(h->tmp.p, t2, h->kept.p, h->ord.p, (int)L, s));
-    VRX_HIP(hipcub::DeviceSelect::Flagged(h->tmp.p, t3, lines_it, h->match.p, h->mlist.p, h->ctl.p + 2, (int)L, s));
-    VRX_HIP(hipcub::DeviceReduce::Sum(h->tmp.p, t4, h->tagged.p, reinterpret_cast<int32_t*>(h->ctl.p + 3), (int)L, s));
+    VRX_HIP(vrx_cub(h->in.tmp, VRX_CUB_CALL(DeviceScan::InclusiveSum, h->kept.p, h->ord.p, (int)L, s)));
+    VRX_HIP(vrx_cub(h->in.tmp, VRX_CUB_CALL(DeviceSelect::Flagged, hipcub::CountingInputIterator<int32_t>(0), h->match.p,
+                                            h->mlist.p, h->in.ctl.p + 2, (int)L, s)));
+    VRX_HIP(vrx_cub(h->in.tmp, VRX_CUB_CALL(DeviceReduce::Sum, h->tagged.p, reinterpret_cast<int32_t*>(h->in.ctl.p + 3),
+                                            (int)L, s)));
     int32_t n_kept = 0;
-    VRX_HIP(hipMemcpyAsync(ctl, h->ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(ctl, h->in.ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
     VRX_HIP(hipMemcpyAsync(&n_kept, h->ord.p + (L - 1), sizeof n_kept, hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
     if (seconds) seconds[1] = seconds_since(t0);
@@ -237,20 +235,20 @@ extern "C" int vrx_vcf_rows(vrx_vcf* h, double* gpb, int64_t* slot, int64_t* lin
     const int64_t M = h->n_matched;
     if (M == 0) return VRX_OK;
     VRX_REQUIRE(gpb && slot && line && flag && span, "vrx_vcf_rows: null output");
-    VRX_HIP(hipSetDevice(h->device));
+    VRX_TRY(h->use());
     hipStream_t s = h->stream;
     const size_t row = (size_t)h->n_sample * 3;
     const int64_t cap = std::min<int64_t>(M, std::max<size_t>(1, kRowBatchBytes / (row * sizeof(double))));
-    VRX_HIP(vrx_vcf_reserve(h->gpb, (size_t)cap * row));
-    VRX_HIP(vrx_vcf_reserve(h->slot, (size_t)cap));
-    VRX_HIP(vrx_vcf_reserve(h->ordinal, (size_t)cap));
-    VRX_HIP(vrx_vcf_reserve(h->rflag, (size_t)cap));
-    VRX_HIP(vrx_vcf_reserve(h->span, (size_t)cap * 2));
+    VRX_HIP(vrx_reserve(h->gpb, (size_t)cap * row));
+    VRX_HIP(vrx_reserve(h->slot, (size_t)cap));
+    VRX_HIP(vrx_reserve(h->ordinal, (size_t)cap));
+    VRX_HIP(vrx_reserve(h->rflag, (size_t)cap));
+    VRX_HIP(vrx_reserve(h->span, (size_t)cap * 2));
     VrxVcfRowsArgs g;
-    g.text = h->text.p;
+    g.text = h->in.text.p;
     g.n = h->n;
     g.n_lines = h->n_lines;
-    g.lstart = h->lstart.p;
+    g.lstart = h->in.lstart.p;
     g.rec = h->rec.p;
     g.ord = h->ord.p;
     g.mlist = h->mlist.p;
@@ -287,18 +285,16 @@ extern "C" int vrx_vcf_rows(vrx_vcf* h, double* gpb, int64_t* slot, int64_t* lin
 }
 
 // ---- cell VCF text: the vrx_cellvcf_* entries on the kernels of vrx_cellvcf.h ------------------------------------
-struct vrx_cellvcf {
-    int device = 0;
+struct vrx_cellvcf : VrxQueue {
     int32_t n_sample = 0, biallelic_only = 1;
     int32_t n_fmt = 0, key0 = 0, key1 = 0;
     uint32_t fmt_len = 0;
-    hipStream_t stream = nullptr;
     DevBuf<uint8_t> fmt;
     // slab
     uint32_t n = 0, n_lines = 0;
     int64_t n_rows = 0, n_entries = 0;
-    DevBuf<uint8_t> text, flag, tmp;
-    DevBuf<uint32_t> lstart, ctl, off;  // ctl: 0 lines of the slab, 1 status, 2 (select count), 3 flagged lines
+    VcfText in;  // its ctl: 2 (select count), 3 flagged lines
+    DevBuf<uint32_t> off;
     DevBuf<int32_t> kept, ord, nseg, segbase, seg_tabs, seg_entries, tab0, ent0, lineflag;
     // rows
     DevBuf<int32_t> cell, v0, v1, rflag, roff;
@@ -307,31 +303,17 @@ struct vrx_cellvcf {
 
 extern "C" int32_t vrx_cellvcf_segment(void) { return VRX_CELLVCF_SEGMENT; }
 
-extern "C" void vrx_cellvcf_destroy(vrx_cellvcf* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipStreamDestroy(h->stream);
-    }
-    delete h;
-}
+extern "C" void vrx_cellvcf_destroy(vrx_cellvcf* h) { vrx_destroy(h); }
 
 extern "C" int vrx_cellvcf_create(int device, int32_t n_sample, int32_t biallelic_only, vrx_cellvcf** out) {
     VRX_REQUIRE(out, "vrx_cellvcf_create: null argument");
     VRX_REQUIRE(n_sample >= 1, "vrx_cellvcf_create: n_sample >= 1");
-    if (int e = vrx_use_device("vrx_cellvcf_create", device)) return e;
-    struct Del {
-        void operator()(vrx_cellvcf* h) const { vrx_cellvcf_destroy(h); }
-    };
-    std::unique_ptr<vrx_cellvcf, Del> h(new vrx_cellvcf());
-    h->device = device;
+    VrxOwned<vrx_cellvcf> h(new vrx_cellvcf());
+    VRX_TRY(h->open("vrx_cellvcf_create", device, 0));
     h->n_sample = n_sample;
     h->biallelic_only = biallelic_only != 0;
-    VRX_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    VRX_HIP(h->ctl.alloc(4));
+    VRX_TRY(h->in.create(h->stream));
     VRX_HIP(h->fmt.alloc(VRX_CELLVCF_FORMAT_MAX + 1));
-    VRX_HIP(hipMemsetAsync(h->ctl.p, 0, 4 * sizeof(uint32_t), h->stream));
     VRX_HIP(hipStreamSynchronize(h->stream));
     *out = h.release();
     return VRX_OK;
@@ -345,7 +327,7 @@ extern "C" int vrx_cellvcf_format(vrx_cellvcf* h, const char* fmt, int32_t fmt_l
     for (int32_t k = 0; k < fmt_len; ++k) n_fmt += fmt[k] == ':';
     VRX_REQUIRE(key0 >= 0 && key0 < n_fmt && key1 >= 0 && key1 < n_fmt, "vrx_cellvcf_format: a key outside FORMAT's %d names",
                 n_fmt);
-    VRX_HIP(hipSetDevice(h->device));
+    VRX_TRY(h->use());
     VRX_HIP(hipMemcpyAsync(h->fmt.p, fmt, (size_t)fmt_len, hipMemcpyHostToDevice, h->stream));
     VRX_HIP(hipStreamSynchronize(h->stream));
     h->fmt_len = (uint32_t)fmt_len;
@@ -359,7 +341,7 @@ extern "C" int vrx_cellvcf_slab(vrx_cellvcf* h, const char* text, int64_t n_byte
     VRX_REQUIRE(h && info, "vrx_cellvcf_slab: null argument");
     VRX_REQUIRE(n_bytes >= 0 && n_bytes < ((int64_t)1 << 31) - 64, "vrx_cellvcf_slab: a slab holds fewer than 2^31 - 64 bytes");
     VRX_REQUIRE(n_bytes == 0 || text, "vrx_cellvcf_slab: null text");
-    VRX_HIP(hipSetDevice(h->device));
+    VRX_TRY(h->use());
     hipStream_t s = h->stream;
     info[0] = info[1] = info[2] = info[3] = 0;
     if (seconds) seconds[0] = seconds[1] = 0.0;
@@ -367,51 +349,28 @@ extern "C" int vrx_cellvcf_slab(vrx_cellvcf* h, const char* text, int64_t n_byte
     h->n_lines = 0;
     h->n_rows = h->n_entries = 0;
     if (n_bytes == 0) return VRX_OK;
-    const size_t n = (size_t)n_bytes;
-    const size_t n_pad = (n + VRX_VCF_MARK_BYTES - 1) / VRX_VCF_MARK_BYTES * VRX_VCF_MARK_BYTES;
-    auto t0 = std::chrono::steady_clock::now();
-    VRX_HIP(vrx_vcf_reserve(h->text, n_pad + 2 * VRX_VCF_MARK_BYTES));
-    VRX_HIP(vrx_vcf_reserve(h->flag, n_pad + VRX_VCF_MARK_BYTES));
-    VRX_HIP(hipMemcpyAsync(h->text.p, text, n, hipMemcpyHostToDevice, s));
-    VRX_HIP(hipStreamSynchronize(s));
-    if (seconds) seconds[0] = seconds_since(t0);
-    t0 = std::chrono::steady_clock::now();
     // 1. line starts
-    uint32_t ctl[4] = {0, 0, 0, 0};
-    VRX_HIP(hipMemcpyAsync(h->ctl.p, ctl, sizeof ctl, hipMemcpyHostToDevice, s));
-    const size_t per_block = (size_t)VRX_VCF_BLOCK * VRX_VCF_MARK_BYTES;
-    vrx_vcf_mark<<<(unsigned)((n + per_block - 1) / per_block), VRX_VCF_BLOCK, 0, s>>>(h->text.p, (uint32_t)n, h->flag.p,
-                                                                                        h->ctl.p, h->ctl.p + 1);
-    VRX_HIP(hipGetLastError());
-    VRX_HIP(hipMemcpyAsync(ctl, h->ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
-    VRX_HIP(hipStreamSynchronize(s));
-    const size_t L = ctl[0];
-    if (L * 9 > n + 1) ctl[1] |= VRX_VCF_ST_SHORT;  // (as in vrx_vcf_slab)
+    const size_t n = (size_t)n_bytes;
+    uint32_t ctl[4];
+    std::chrono::steady_clock::time_point t0;
+    VRX_TRY(h->in.lines(s, text, n, 0, ctl, seconds, &t0));
     if (ctl[1]) {
         info[3] = ctl[1];
-        if (seconds) seconds[1] = seconds_since(t0);
         return VRX_OK;
     }
+    const size_t L = ctl[0];
     h->n_lines = (uint32_t)L;
-    VRX_HIP(vrx_vcf_reserve(h->lstart, L));
-    VRX_HIP(vrx_vcf_reserve(h->kept, L));
-    VRX_HIP(vrx_vcf_reserve(h->ord, L));
-    VRX_HIP(vrx_vcf_reserve(h->nseg, L + 1));
-    VRX_HIP(vrx_vcf_reserve(h->segbase, L + 1));
-    VRX_HIP(vrx_vcf_reserve(h->lineflag, L));
-    VRX_HIP(vrx_vcf_reserve(h->off, L * VRX_CELLVCF_OFFS));
-    size_t t1 = 0, t2 = 0, t3 = 0;
-    hipcub::CountingInputIterator<uint32_t> bytes_it(0);
-    VRX_HIP(hipcub::DeviceSelect::Flagged(nullptr, t1, bytes_it, h->flag.p, h->lstart.p, h->ctl.p + 2, (int)n, s));
-    VRX_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, t2, h->kept.p, h->ord.p, (int)L, s));
-    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, h->nseg.p, h->segbase.p, (int)(L + 1), s));
-    VRX_HIP(vrx_vcf_reserve(h->tmp, std::max(t1, std::max(t2, t3))));
-    VRX_HIP(hipcub::DeviceSelect::Flagged(h->tmp.p, t1, bytes_it, h->flag.p, h->lstart.p, h->ctl.p + 2, (int)n, s));
+    VRX_HIP(vrx_reserve(h->kept, L));
+    VRX_HIP(vrx_reserve(h->ord, L));
+    VRX_HIP(vrx_reserve(h->nseg, L + 1));
+    VRX_HIP(vrx_reserve(h->segbase, L + 1));
+    VRX_HIP(vrx_reserve(h->lineflag, L));
+    VRX_HIP(vrx_reserve(h->off, L * VRX_CELLVCF_OFFS));
     // 2. per line
     VrxCellLinesArgs gl;
-    gl.text = h->text.p;
+    gl.text = h->in.text.p;
     gl.n = (uint32_t)n;
-    gl.lstart = h->lstart.p;
+    gl.lstart = h->in.lstart.p;
     gl.n_lines = (uint32_t)L;
     gl.biallelic_only = h->biallelic_only;
     gl.fmt = h->fmt.p;
@@ -419,15 +378,15 @@ extern "C" int vrx_cellvcf_slab(vrx_cellvcf* h, const char* text, int64_t n_byte
     gl.kept = h->kept.p;
     gl.nseg = h->nseg.p;
     gl.off = h->off.p;
-    gl.status = h->ctl.p + 1;
+    gl.status = h->in.ctl.p + 1;
     VRX_HIP(hipMemsetAsync(h->nseg.p + L, 0, sizeof(int32_t), s));
     VRX_HIP(hipMemsetAsync(h->lineflag.p, 0, L * sizeof(int32_t), s));
     vrx_cellvcf_lines<<<(unsigned)((L + VRX_VCF_WAVES - 1) / VRX_VCF_WAVES), VRX_VCF_BLOCK, 0, s>>>(gl);
     VRX_HIP(hipGetLastError());
-    VRX_HIP(hipcub::DeviceScan::InclusiveSum(h->tmp.p, t2, h->kept.p, h->ord.p, (int)L, s));
-    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(h->tmp.p, t3, h->nseg.p, h->segbase.p, (int)(L + 1), s));
+    VRX_HIP(vrx_cub(h->in.tmp, VRX_CUB_CALL(DeviceScan::InclusiveSum, h->kept.p, h->ord.p, (int)L, s)));
+    VRX_HIP(vrx_cub(h->in.tmp, VRX_CUB_CALL(DeviceScan::ExclusiveSum, h->nseg.p, h->segbase.p, (int)(L + 1), s)));
     int32_t n_kept = 0, n_seg = 0;
-    VRX_HIP(hipMemcpyAsync(ctl, h->ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(ctl, h->in.ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
     VRX_HIP(hipMemcpyAsync(&n_kept, h->ord.p + (L - 1), sizeof n_kept, hipMemcpyDeviceToHost, s));
     VRX_HIP(hipMemcpyAsync(&n_seg, h->segbase.p + L, sizeof n_seg, hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
@@ -439,12 +398,12 @@ extern "C" int vrx_cellvcf_slab(vrx_cellvcf* h, const char* text, int64_t n_byte
     }
     // 3. count pass over the segments, 4. scans
     const size_t G = (size_t)n_seg;
-    VRX_HIP(vrx_vcf_reserve(h->seg_tabs, G + 1));
-    VRX_HIP(vrx_vcf_reserve(h->seg_entries, G + 1));
-    VRX_HIP(vrx_vcf_reserve(h->tab0, G + 1));
-    VRX_HIP(vrx_vcf_reserve(h->ent0, G + 1));
+    VRX_HIP(vrx_reserve(h->seg_tabs, G + 1));
+    VRX_HIP(vrx_reserve(h->seg_entries, G + 1));
+    VRX_HIP(vrx_reserve(h->tab0, G + 1));
+    VRX_HIP(vrx_reserve(h->ent0, G + 1));
     VrxCellSegArgs gs;
-    gs.text = h->text.p;
+    gs.text = h->in.text.p;
     gs.off = h->off.p;
     gs.segbase = h->segbase.p;
     gs.n_lines = (uint32_t)L;
@@ -458,7 +417,7 @@ extern "C" int vrx_cellvcf_slab(vrx_cellvcf* h, const char* text, int64_t n_byte
     gs.ent0 = h->ent0.p;
     gs.cell = gs.v0 = gs.v1 = nullptr;
     gs.lineflag = h->lineflag.p;
-    gs.status = h->ctl.p + 1;
+    gs.status = h->in.ctl.p + 1;
     const unsigned seg_blocks = (unsigned)((G + VRX_VCF_WAVES - 1) / VRX_VCF_WAVES);
     VRX_HIP(hipMemsetAsync(h->seg_tabs.p + G, 0, sizeof(int32_t), s));
     VRX_HIP(hipMemsetAsync(h->seg_entries.p + G, 0, sizeof(int32_t), s));
@@ -466,23 +425,20 @@ extern "C" int vrx_cellvcf_slab(vrx_cellvcf* h, const char* text, int64_t n_byte
         vrx_cellvcf_count<<<seg_blocks, VRX_VCF_BLOCK, 0, s>>>(gs);
         VRX_HIP(hipGetLastError());
     }
-    size_t t4 = 0;
-    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t4, h->seg_tabs.p, h->tab0.p, (int)(G + 1), s));
-    VRX_HIP(vrx_vcf_reserve(h->tmp, t4));
-    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(h->tmp.p, t4, h->seg_tabs.p, h->tab0.p, (int)(G + 1), s));
-    VRX_HIP(hipcub::DeviceScan::ExclusiveSum(h->tmp.p, t4, h->seg_entries.p, h->ent0.p, (int)(G + 1), s));
+    VRX_HIP(vrx_cub(h->in.tmp, VRX_CUB_CALL(DeviceScan::ExclusiveSum, h->seg_tabs.p, h->tab0.p, (int)(G + 1), s)));
+    VRX_HIP(vrx_cub(h->in.tmp, VRX_CUB_CALL(DeviceScan::ExclusiveSum, h->seg_entries.p, h->ent0.p, (int)(G + 1), s)));
     int32_t n_ent = 0;
     VRX_HIP(hipMemcpyAsync(&n_ent, h->ent0.p + G, sizeof n_ent, hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
     // 5. emit pass, then the kept lines as rows
     const size_t E = (size_t)n_ent, R = (size_t)n_kept;
-    VRX_HIP(vrx_vcf_reserve(h->cell, E + 1));
-    VRX_HIP(vrx_vcf_reserve(h->v0, E + 1));
-    VRX_HIP(vrx_vcf_reserve(h->v1, E + 1));
-    VRX_HIP(vrx_vcf_reserve(h->indptr, R + 1));
-    VRX_HIP(vrx_vcf_reserve(h->rflag, R + 1));
-    VRX_HIP(vrx_vcf_reserve(h->span, (R + 1) * 2));
-    VRX_HIP(vrx_vcf_reserve(h->roff, (R + 1) * VRX_CELLVCF_OFFS));
+    VRX_HIP(vrx_reserve(h->cell, E + 1));
+    VRX_HIP(vrx_reserve(h->v0, E + 1));
+    VRX_HIP(vrx_reserve(h->v1, E + 1));
+    VRX_HIP(vrx_reserve(h->indptr, R + 1));
+    VRX_HIP(vrx_reserve(h->rflag, R + 1));
+    VRX_HIP(vrx_reserve(h->span, (R + 1) * 2));
+    VRX_HIP(vrx_reserve(h->roff, (R + 1) * VRX_CELLVCF_OFFS));
     gs.cell = h->cell.p;
     gs.v0 = h->v0.p;
     gs.v1 = h->v1.p;
@@ -495,7 +451,7 @@ extern "C" int vrx_cellvcf_slab(vrx_cellvcf* h, const char* text, int64_t n_byte
     gr.n_lines = (uint32_t)L;
     gr.n_seg = (uint32_t)G;
     gr.n_sample = h->n_sample;
-    gr.lstart = h->lstart.p;
+    gr.lstart = h->in.lstart.p;
     gr.kept = h->kept.p;
     gr.ord = h->ord.p;
     gr.segbase = h->segbase.p;
@@ -507,11 +463,11 @@ extern "C" int vrx_cellvcf_slab(vrx_cellvcf* h, const char* text, int64_t n_byte
     gr.flag = h->rflag.p;
     gr.span = h->span.p;
     gr.roff = h->roff.p;
-    gr.status = h->ctl.p + 1;
-    gr.n_flagged = h->ctl.p + 3;
+    gr.status = h->in.ctl.p + 1;
+    gr.n_flagged = h->in.ctl.p + 3;
     vrx_cellvcf_rows<<<(unsigned)((L + VRX_VCF_BLOCK - 1) / VRX_VCF_BLOCK), VRX_VCF_BLOCK, 0, s>>>(gr);
     VRX_HIP(hipGetLastError());
-    VRX_HIP(hipMemcpyAsync(ctl, h->ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipMemcpyAsync(ctl, h->in.ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
     VRX_HIP(hipStreamSynchronize(s));
     if (seconds) seconds[1] = seconds_since(t0);
     h->n_rows = n_kept;
@@ -535,7 +491,7 @@ extern "C" int vrx_cellvcf_rows(vrx_cellvcf* h, int64_t* indptr, int32_t* cell, 
         indptr[0] = 0;
         return VRX_OK;
     }
-    VRX_HIP(hipSetDevice(h->device));
+    VRX_TRY(h->use());
     hipStream_t s = h->stream;
     auto t0 = std::chrono::steady_clock::now();
     VRX_HIP(hipMemcpyAsync(indptr, h->indptr.p, (R + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, s));

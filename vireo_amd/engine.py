@@ -4,7 +4,6 @@ Everything numeric happens in libvireo_hip.so; this class only moves the referen
 NumPy attributes across the C ABI.
 """
 import ctypes as C
-import weakref
 
 import numpy as np
 
@@ -27,11 +26,7 @@ def _prior_rows(P, full_rows):
     return f64(P), full_rows
 
 
-def _destroy_model(handle, counts):
-    _lib.lib().vrx_model_destroy(handle)
-
-
-class DeviceModel:
+class DeviceModel(_lib.Handle):
     def __init__(self, counts, kind, n_donor, n_gt=3, learn_gt=True, learn_theta=True,
                  ase_mode=False, fix_beta_sum=False, n_batch=1):
         self.counts = counts            # keeps the vrx_problem alive
@@ -46,14 +41,11 @@ class DeviceModel:
         cfg = _lib.ModelCfg(kind=kind, n_donor=self.K, n_gt=self.T, learn_gt=int(bool(learn_gt)),
                             learn_theta=int(bool(learn_theta)), ase_mode=int(bool(ase_mode)),
                             fix_beta_sum=int(bool(fix_beta_sum)), n_batch=self.R)
-        self._h = C.c_void_p()
-        _lib.check(_lib.lib().vrx_model_create(counts.handle, C.byref(cfg), C.byref(self._h)))
+        L = _lib.lib()
         # vrx_model_destroy reads its vrx_problem (device, stream): the finaliser holds ``counts``, so
         # that a garbage-collection pass that frees both in one go cannot destroy the problem first
-        self._fin = weakref.finalize(self, _destroy_model, self._h, counts)
-
-    def close(self):
-        self._fin()
+        super().__init__(type(self).__name__, lambda out: L.vrx_model_create(counts.handle, C.byref(cfg), out),
+                         L.vrx_model_destroy, keep=(counts,))
 
     # ---- state / priors ---------------------------------------------------------------
     def _check(self, a, shape, name):

@@ -134,26 +134,22 @@ def match_prepared(p, device=None, timing=None):
     from .counts import default_device
     _lib.require_gpu()
     L = _lib.lib()
-    h = C.c_void_p()
-    _lib.check(L.vrx_genematch_create(
-        default_device() if device is None else device, p["n_code"], p["start"].size,
-        p["chrom_ptr"].ctypes.data_as(_I64P), p["start"].ctypes.data_as(_I32P), p["stop"].ctypes.data_as(_I32P),
-        p["row"].ctypes.data_as(_I32P), C.byref(h)))
-    try:
+    with _lib.Handle("the gene table", lambda out: L.vrx_genematch_create(
+            default_device() if device is None else device, p["n_code"], p["start"].size,
+            p["chrom_ptr"].ctypes.data_as(_I64P), p["start"].ctypes.data_as(_I32P), p["stop"].ctypes.data_as(_I32P),
+            p["row"].ctypes.data_as(_I32P), out), L.vrx_genematch_destroy) as h:
         n = p["n_snp"]
         flag = np.zeros(n, dtype=np.int32)
         count = np.zeros(n, dtype=np.int64)
         ms1, ms2 = C.c_double(0.0), C.c_double(0.0)
         _lib.check(L.vrx_genematch_match(
-            h, n, p["code"].ctypes.data_as(_I32P), p["pos"].ctypes.data_as(_I32P), p["perm"].ctypes.data_as(_I32P),
+            h.ptr, n, p["code"].ctypes.data_as(_I32P), p["pos"].ctypes.data_as(_I32P), p["perm"].ctypes.data_as(_I32P),
             p["gap_m1"].size, p["gap_m1"].ctypes.data_as(_I32P), p["single"].ctypes.data_as(C.POINTER(C.c_uint8)),
             flag.ctypes.data_as(_I32P), count.ctypes.data_as(_I64P), C.byref(ms1)))
         ptr = np.zeros(n + 1, dtype=np.int64)
         np.cumsum(count, out=ptr[1:])
         rows = np.zeros(int(ptr[-1]), dtype=np.int32)
-        _lib.check(L.vrx_genematch_lists(h, int(ptr[-1]), rows.ctypes.data_as(_I32P), C.byref(ms2)))
-    finally:
-        L.vrx_genematch_destroy(h)
+        _lib.check(L.vrx_genematch_lists(h.ptr, int(ptr[-1]), rows.ctypes.data_as(_I32P), C.byref(ms2)))
     if timing is not None:
         timing["kernel_ms"] = ms1.value + ms2.value
     return flag, ptr, rows
@@ -240,20 +236,17 @@ def gene_counts(AD, DP, gene_list, flag_list=None, max_flag=None, gene_names=Non
     n_gene = int(names.size)
     _lib.require_gpu()
     L = _lib.lib()
-    h = C.c_void_p()
     n_out, ms = C.c_int64(0), C.c_double(0.0)
     colptr = np.ascontiguousarray(colptr, dtype=np.int64)
-    _lib.check(L.vrx_genecount_create(
-        default_device() if device is None else device, n_var, n_cell, n_gene, colptr.ctypes.data_as(_I64P),
-        rowidx.ctypes.data_as(_I32P), ad.ctypes.data_as(_I32P), dp.ctypes.data_as(_I32P), gptr.ctypes.data_as(_I64P),
-        gid.ctypes.data_as(_I32P), C.byref(h), C.byref(n_out), C.byref(ms)))
-    try:
+    with _lib.Handle("the gene counts", lambda out: L.vrx_genecount_create(
+            default_device() if device is None else device, n_var, n_cell, n_gene, colptr.ctypes.data_as(_I64P),
+            rowidx.ctypes.data_as(_I32P), ad.ctypes.data_as(_I32P), dp.ctypes.data_as(_I32P),
+            gptr.ctypes.data_as(_I64P), gid.ctypes.data_as(_I32P), out, C.byref(n_out), C.byref(ms)),
+            L.vrx_genecount_destroy) as h:
         key = np.zeros(n_out.value, dtype=np.int64)
         sa, sd = np.zeros(n_out.value, dtype=np.int64), np.zeros(n_out.value, dtype=np.int64)
-        _lib.check(L.vrx_genecount_read(h, key.ctypes.data_as(_I64P), sa.ctypes.data_as(_I64P),
+        _lib.check(L.vrx_genecount_read(h.ptr, key.ctypes.data_as(_I64P), sa.ctypes.data_as(_I64P),
                                         sd.ctypes.data_as(_I64P)))
-    finally:
-        L.vrx_genecount_destroy(h)
     if timing is not None:
         timing["kernel_ms"] = ms.value
     cell, gene = (key // n_gene, key % n_gene) if n_gene else (key, key)

@@ -191,7 +191,6 @@ def read_cellVCF(vcf_file, biallelic_only=True, keys=('AD', 'DP'), axes=(-1, -1)
     t_all = time.perf_counter()
     sec = dict(inflate=0.0, upload=0.0, kernels=0.0, download=0.0, host=0.0)
     text = _DonorText(vcf_file, sec)
-    handle = C.c_void_p()
     try:
         head = text.header()
         for raw in head:                                          # the '#' lines as load_VCF's text layer sees them
@@ -213,64 +212,66 @@ def read_cellVCF(vcf_file, biallelic_only=True, keys=('AD', 'DP'), axes=(-1, -1)
         S = len(samples)
         if S == 0:
             return host("no sample columns")
-        _lib.check(L.vrx_cellvcf_create(device, S, int(bool(biallelic_only)), C.byref(handle)))
-        info = np.zeros(4, dtype=np.int64)
-        t2 = np.zeros(2)
-        fmt = format_list = None
-        variants, repair = [], []
-        p_indptr, p_cell, p_v0, p_v1 = [], [], [], []
-        n_entries = 0
-        for slab in text.slabs(slab_bytes):
-            if len(slab) > _SLAB_LIMIT:
-                return host("a line of 2 GiB")
-            if fmt is None:
-                fmt, why = _first_kept_format(slab, biallelic_only)
-                if why is not None:
-                    return host(why)
-                if fmt is not None:
-                    format_list = fmt.decode("latin-1").split(":")
-                    if not 1 <= len(fmt) <= _CELL_FORMAT_MAX:
-                        return host("a FORMAT of %d bytes" % len(fmt))
-                    if keys[0] not in format_list or keys[1] not in format_list:
-                        return host("FORMAT does not name the keys")
-                    _lib.check(L.vrx_cellvcf_format(handle, fmt, len(fmt), format_list.index(keys[0]),
-                                                    format_list.index(keys[1])))
-            raw = (C.c_char * len(slab)).from_buffer(slab)
-            _lib.check(L.vrx_cellvcf_slab(handle, raw, len(slab), info.ctypes.data_as(_lib._I64), _lib.dptr(t2)))
-            del raw
-            sec['upload'] += t2[0]
-            sec['kernels'] += t2[1]
-            if info[3]:
-                return host(_cell_reason(int(info[3])))
-            R, E = int(info[0]), int(info[1])
-            if R == 0:
-                continue
-            indptr, flag = np.empty(R + 1, np.int64), np.empty(R, np.int32)
-            span, off = np.empty((R, 2), np.int64), np.empty((R, 10), np.int32)
-            cell, v0, v1 = np.empty(E, np.int32), np.empty(E, np.int32), np.empty(E, np.int32)
-            _lib.check(L.vrx_cellvcf_rows(handle, indptr.ctypes.data_as(_lib._I64), cell.ctypes.data_as(_lib._I32),
-                                          v0.ctypes.data_as(_lib._I32), v1.ctypes.data_as(_lib._I32),
-                                          flag.ctypes.data_as(_lib._I32), span.ctypes.data_as(_lib._I64),
-                                          off.ctypes.data_as(_lib._I32), _lib.dptr(t2)))
-            sec['download'] += t2[0]
-            assert indptr[0] == 0 and indptr[R] == E
-            for r in np.flatnonzero(flag):                        # the text of a flagged line outlives its slab
-                repair.append((len(variants) + int(r), bytes(slab[span[r, 0]:span[r, 1]])))
-            start, tab7 = span[:, 0].tolist(), off[:, 7].tolist()
-            for r in range(R):                                    # CHROM ... INFO: the text in front of the eighth tab
-                f = slab[start[r]:tab7[r]].decode("ascii").split("\t")
-                for k, v in zip(fkeys, f):
-                    fixed[k].append(v)
-                variants.append("_".join((f[0], f[1], f[3], f[4])))
-            p_indptr.append(indptr[:-1] + n_entries)
-            p_cell.append(cell)
-            p_v0.append(v0)
-            p_v1.append(v1)
-            n_entries += E
+        with _lib.Handle("the cell VCF reader",
+                         lambda out: L.vrx_cellvcf_create(device, S, int(bool(biallelic_only)), out),
+                         L.vrx_cellvcf_destroy) as reader:
+            info = np.zeros(4, dtype=np.int64)
+            t2 = np.zeros(2)
+            fmt = format_list = None
+            variants, repair = [], []
+            p_indptr, p_cell, p_v0, p_v1 = [], [], [], []
+            n_entries = 0
+            for slab in text.slabs(slab_bytes):
+                if len(slab) > _SLAB_LIMIT:
+                    return host("a line of 2 GiB")
+                if fmt is None:
+                    fmt, why = _first_kept_format(slab, biallelic_only)
+                    if why is not None:
+                        return host(why)
+                    if fmt is not None:
+                        format_list = fmt.decode("latin-1").split(":")
+                        if not 1 <= len(fmt) <= _CELL_FORMAT_MAX:
+                            return host("a FORMAT of %d bytes" % len(fmt))
+                        if keys[0] not in format_list or keys[1] not in format_list:
+                            return host("FORMAT does not name the keys")
+                        _lib.check(L.vrx_cellvcf_format(reader.ptr, fmt, len(fmt), format_list.index(keys[0]),
+                                                        format_list.index(keys[1])))
+                raw = (C.c_char * len(slab)).from_buffer(slab)
+                _lib.check(L.vrx_cellvcf_slab(reader.ptr, raw, len(slab), info.ctypes.data_as(_lib._I64),
+                                              _lib.dptr(t2)))
+                del raw
+                sec['upload'] += t2[0]
+                sec['kernels'] += t2[1]
+                if info[3]:
+                    return host(_cell_reason(int(info[3])))
+                R, E = int(info[0]), int(info[1])
+                if R == 0:
+                    continue
+                indptr, flag = np.empty(R + 1, np.int64), np.empty(R, np.int32)
+                span, off = np.empty((R, 2), np.int64), np.empty((R, 10), np.int32)
+                cell, v0, v1 = np.empty(E, np.int32), np.empty(E, np.int32), np.empty(E, np.int32)
+                _lib.check(L.vrx_cellvcf_rows(reader.ptr, indptr.ctypes.data_as(_lib._I64),
+                                              cell.ctypes.data_as(_lib._I32),
+                                              v0.ctypes.data_as(_lib._I32), v1.ctypes.data_as(_lib._I32),
+                                              flag.ctypes.data_as(_lib._I32), span.ctypes.data_as(_lib._I64),
+                                              off.ctypes.data_as(_lib._I32), _lib.dptr(t2)))
+                sec['download'] += t2[0]
+                assert indptr[0] == 0 and indptr[R] == E
+                for r in np.flatnonzero(flag):                        # the text of a flagged line outlives its slab
+                    repair.append((len(variants) + int(r), bytes(slab[span[r, 0]:span[r, 1]])))
+                start, tab7 = span[:, 0].tolist(), off[:, 7].tolist()
+                for r in range(R):                                # CHROM ... INFO: the text in front of the eighth tab
+                    f = slab[start[r]:tab7[r]].decode("ascii").split("\t")
+                    for k, v in zip(fkeys, f):
+                        fixed[k].append(v)
+                    variants.append("_".join((f[0], f[1], f[3], f[4])))
+                p_indptr.append(indptr[:-1] + n_entries)
+                p_cell.append(cell)
+                p_v0.append(v0)
+                p_v1.append(v1)
+                n_entries += E
     finally:
         text.close()
-        if handle:
-            L.vrx_cellvcf_destroy(handle)
 
     n_var = len(variants)
     if n_var == 0:

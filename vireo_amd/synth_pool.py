@@ -196,7 +196,7 @@ def _is_merged(s):
     return len(s) == 5 and isinstance(s[0], tuple)
 
 
-class DevicePool:
+class DevicePool(_lib.Handle):
     """The merged (ad, dp) columns of every sample on one GPU (C handle ``vrx_pool``): ``run`` pools them by a
     plan; several plans can run on one upload.  samples: a list of (AD, DP), each variants x cells in any format
     ``device_counts`` takes (or the tuple ``merge_counts`` returns), all with the same number of variants."""
@@ -227,26 +227,15 @@ class DevicePool:
         del merged
         _lib.require_gpu()
         self.device = default_device() if device is None else device
-        self._h = C.c_void_p()
-        _lib.check(_lib.lib().vrx_pool_create(self.device, self.n_var, self.n_src, colptr.ctypes.data_as(_I64P),
-                                              rowidx.ctypes.data_as(_I32P), ad.ctypes.data_as(_I32P),
-                                              dp.ctypes.data_as(_I32P), C.byref(self._h)))
+        L = _lib.lib()
+        super().__init__("DevicePool", lambda out: L.vrx_pool_create(
+            self.device, self.n_var, self.n_src, colptr.ctypes.data_as(_I64P), rowidx.ctypes.data_as(_I32P),
+            ad.ctypes.data_as(_I32P), dp.ctypes.data_as(_I32P), out), L.vrx_pool_destroy)
 
     def _check_sizes(self, sizes):
         if [int(n) for n in sizes] != self.sizes:
             raise ValueError("pool_counts: the plan has %s cells per sample, the samples have %s columns"
                              % (list(sizes), self.sizes))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().vrx_pool_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:                                           # interpreter shutdown
-            pass
 
     def run(self, plan, merged=False, timing=None, download=True):
         """-> (AD, DP) int64 SciPy CSC of shape (variants, pooled cells), AD's zeros dropped, or with merged

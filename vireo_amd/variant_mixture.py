@@ -22,7 +22,6 @@ cut-off and delta-BIC.  This is the reference's VB bound, not a re-implementatio
 not MQuad's, only the purpose and the names of the output files of ``python -m vireo_amd.variant_gain`` are.
 """
 import ctypes as C
-import weakref
 
 import numpy as np
 
@@ -66,7 +65,7 @@ def _check_fit_args(n_clone, max_iter, min_iter):
         raise ValueError("min_iter must not be negative")
 
 
-class VariantMixtures:
+class VariantMixtures(_lib.Handle):
     """The covered (AD, DP) entries of every variant resident on one GPU (C handle ``vrx_varmix``);
     ``fit`` may be called any number of times, so sweeping ``n_clone`` reuses one upload."""
 
@@ -76,13 +75,12 @@ class VariantMixtures:
         self.nnz = int(ad.size)
         _lib.require_gpu()
         self.device = default_device() if device is None else device
-        self._h = C.c_void_p()
         i32 = C.POINTER(C.c_int32)
-        _lib.check(_lib.lib().vrx_varmix_create(
+        L = _lib.lib()
+        super().__init__("VariantMixtures", lambda out: L.vrx_varmix_create(
             self.device, self.n_var, self.nnz, rowptr.ctypes.data_as(C.POINTER(C.c_int64)),
-            ad.ctypes.data_as(i32), dp.ctypes.data_as(i32), C.byref(self._h)))
+            ad.ctypes.data_as(i32), dp.ctypes.data_as(i32), out), L.vrx_varmix_destroy)
         self.kernel_ms = 0.0
-        self._fin = weakref.finalize(self, _lib.lib().vrx_varmix_destroy, self._h)
 
     def fit(self, n_clone=2, max_iter=200, min_iter=20, epsilon_conv=1e-2, return_trace=False):
         """-> dict(gain, elbo, elbo_one, beta_mu, beta_sum, size, n_iter, warn, n_covered [, trace]).
@@ -107,9 +105,6 @@ class VariantMixtures:
         if return_trace:
             out["trace"] = [trace[v, :n_iter[v] + 1].copy() for v in range(N)]
         return out
-
-    def close(self):
-        self._fin()
 
 
 def variant_mixture_gain(AD, DP, n_clone=2, max_iter=200, min_iter=20, epsilon_conv=1e-2, min_DP=1,

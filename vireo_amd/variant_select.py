@@ -97,28 +97,20 @@ def _check_input(GT, var_count):
     return G.astype(np.uint8), vc
 
 
-class BarcodeRounds(object):
+class BarcodeRounds(_lib.Handle):
     """The genotypes (and var_count) of one selection on the device, and the class ranks of the samples."""
 
     def __init__(self, GT, var_count=None, device=0):
-        self.handle = None
         G, vc = _check_input(GT, var_count)
         self.n_var, self.n_donor = G.shape
         _lib.require_gpu()
         rows = np.ascontiguousarray(G.T)                       # donor-major: a wave reads neighbouring variants
-        h = C.c_void_p()
-        _lib.check(_lib.lib().vrx_barcode_create(device, self.n_var, self.n_donor, int(G.max()) + 1,
-                                                 rows.ctypes.data_as(C.POINTER(C.c_uint8)), dptr(vc), C.byref(h)))
-        self.handle = h
+        L = _lib.lib()
+        super().__init__("BarcodeRounds", lambda out: L.vrx_barcode_create(
+            device, self.n_var, self.n_donor, int(G.max()) + 1, rows.ctypes.data_as(C.POINTER(C.c_uint8)), dptr(vc),
+            out), L.vrx_barcode_destroy)
         self.rank = np.zeros(self.n_donor, dtype=np.int64)
         self.ms = (0.0, 0.0)
-
-    def close(self):
-        if self.handle is not None:
-            _lib.lib().vrx_barcode_destroy(self.handle)
-            self.handle = None
-
-    __del__ = close
 
     def round(self, half_width=HALF_WIDTH):
         """all variants against the current classes: (max entropy, n_tied, n_kept)"""
@@ -131,7 +123,7 @@ class BarcodeRounds(object):
         ms = np.zeros(2)
         i32 = C.POINTER(C.c_int32)
         _lib.check(_lib.lib().vrx_barcode_round(
-            self.handle, order.ctypes.data_as(i32), bnd.ctypes.data_as(i32), n_class, dptr(table), half_width,
+            self._h, order.ctypes.data_as(i32), bnd.ctypes.data_as(i32), n_class, dptr(table), half_width,
             float(np.log(2)), C.byref(top), counts.ctypes.data_as(C.POINTER(C.c_int64)), dptr(ms)))
         self.ms = (float(ms[0]), float(ms[1]))
         return np.float64(top.value), int(counts[0]), int(counts[1])
@@ -139,7 +131,7 @@ class BarcodeRounds(object):
     def pick(self, r):
         """the r-th survivor of the last round in ascending variant index, and its entropy"""
         idx, ent = C.c_int64(-1), C.c_double(0.0)
-        _lib.check(_lib.lib().vrx_barcode_pick(self.handle, int(r), C.byref(idx), C.byref(ent)))
+        _lib.check(_lib.lib().vrx_barcode_pick(self._h, int(r), C.byref(idx), C.byref(ent)))
         return np.int64(idx.value), np.float64(ent.value)
 
     def choose(self, values):
@@ -150,7 +142,7 @@ class BarcodeRounds(object):
 
     def entropies(self):
         out = np.empty(self.n_var)
-        _lib.check(_lib.lib().vrx_barcode_entropies(self.handle, dptr(out)))
+        _lib.check(_lib.lib().vrx_barcode_entropies(self._h, dptr(out)))
         return out
 
 

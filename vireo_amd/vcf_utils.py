@@ -339,7 +339,6 @@ def load_donor_GPb(vcf_file, tag='GT', variants=None, biallelic_only=True, min_p
         return _donor_host(vcf_file, tag, variants, biallelic_only, min_prob, reason)
 
     text = _DonorText(vcf_file, sec)
-    handle = C.c_void_p()
     try:
         head = text.header()
         chrom = [x for x in head if x.startswith(b"#CHROM")]
@@ -357,55 +356,55 @@ def load_donor_GPb(vcf_file, tag='GT', variants=None, biallelic_only=True, min_p
             off = np.zeros(n_ids + 1, dtype=np.int64)
             np.cumsum([len(x) for x in enc], out=off[1:])
         table = 10 ** (-0.1 * np.arange(4096.) - 0.025) if tag == 'PL' else None
-        _lib.check(L.vrx_vcf_create(device, _TAG_CODE[tag], S, int(bool(biallelic_only)), n_ids, blob,
-                                    None if off is None else off.ctypes.data_as(_lib._I64), _lib.dptr(table),
-                                    C.byref(handle)))
-        info = np.zeros(4, dtype=np.int64)
-        t2 = np.zeros(2)
-        status = C.c_int32(0)
-        for mode in ((-1,) if variants is None else (0, 1, 2)):
-            if text is None:                                      # a "chr" retry of match_SNPs: the file once more
-                text = _DonorText(vcf_file, sec)
-                text.header()
-            _lib.check(L.vrx_vcf_begin(handle, mode, C.byref(status)))
-            if status.value:
-                return host(_status_reason(status.value))
-            n_lines = n_tagged = 0
-            parts, repair = [], []
-            for slab in text.slabs(slab_bytes):
-                if len(slab) > _SLAB_LIMIT:
-                    return host("a line of 2 GiB")
-                raw = (C.c_char * len(slab)).from_buffer(slab)
-                _lib.check(L.vrx_vcf_slab(handle, raw, len(slab), info.ctypes.data_as(_lib._I64), _lib.dptr(t2)))
-                sec['upload'] += t2[0]
-                sec['kernels'] += t2[1]
-                if info[3]:
-                    return host(_status_reason(int(info[3])))
-                n_lines += int(info[0])
-                n_tagged += int(info[1])
-                m = int(info[2])
-                if m == 0:
-                    continue
-                rows, slot, line = np.empty((m, S, 3)), np.empty(m, np.int64), np.empty(m, np.int64)
-                flag, span = np.empty(m, np.int32), np.empty((m, 2), np.int64)
-                _lib.check(L.vrx_vcf_rows(handle, _lib.dptr(rows), slot.ctypes.data_as(_lib._I64),
-                                          line.ctypes.data_as(_lib._I64), flag.ctypes.data_as(_lib._I32),
-                                          span.ctypes.data_as(_lib._I64), _lib.dptr(t2)))
-                sec['kernels'] += t2[0]
-                sec['download'] += t2[1]
-                parts.append((rows, slot, line, flag))
-                for r in np.flatnonzero(flag):                    # the text of a flagged row outlives its slab
-                    repair.append((int(slot[r]), bytes(slab[span[r, 0]:span[r, 1]])))
-                del raw
-            text.close()
-            text = None
-            if parts or variants is None:
-                break
+        with _lib.Handle("the donor VCF reader", lambda out: L.vrx_vcf_create(
+                device, _TAG_CODE[tag], S, int(bool(biallelic_only)), n_ids, blob,
+                None if off is None else off.ctypes.data_as(_lib._I64), _lib.dptr(table), out),
+                L.vrx_vcf_destroy) as reader:
+            info = np.zeros(4, dtype=np.int64)
+            t2 = np.zeros(2)
+            status = C.c_int32(0)
+            for mode in ((-1,) if variants is None else (0, 1, 2)):
+                if text is None:                                      # a "chr" retry of match_SNPs: the file once more
+                    text = _DonorText(vcf_file, sec)
+                    text.header()
+                _lib.check(L.vrx_vcf_begin(reader.ptr, mode, C.byref(status)))
+                if status.value:
+                    return host(_status_reason(status.value))
+                n_lines = n_tagged = 0
+                parts, repair = [], []
+                for slab in text.slabs(slab_bytes):
+                    if len(slab) > _SLAB_LIMIT:
+                        return host("a line of 2 GiB")
+                    raw = (C.c_char * len(slab)).from_buffer(slab)
+                    _lib.check(L.vrx_vcf_slab(reader.ptr, raw, len(slab), info.ctypes.data_as(_lib._I64),
+                                              _lib.dptr(t2)))
+                    sec['upload'] += t2[0]
+                    sec['kernels'] += t2[1]
+                    if info[3]:
+                        return host(_status_reason(int(info[3])))
+                    n_lines += int(info[0])
+                    n_tagged += int(info[1])
+                    m = int(info[2])
+                    if m == 0:
+                        continue
+                    rows, slot, line = np.empty((m, S, 3)), np.empty(m, np.int64), np.empty(m, np.int64)
+                    flag, span = np.empty(m, np.int32), np.empty((m, 2), np.int64)
+                    _lib.check(L.vrx_vcf_rows(reader.ptr, _lib.dptr(rows), slot.ctypes.data_as(_lib._I64),
+                                              line.ctypes.data_as(_lib._I64), flag.ctypes.data_as(_lib._I32),
+                                              span.ctypes.data_as(_lib._I64), _lib.dptr(t2)))
+                    sec['kernels'] += t2[0]
+                    sec['download'] += t2[1]
+                    parts.append((rows, slot, line, flag))
+                    for r in np.flatnonzero(flag):                    # the text of a flagged row outlives its slab
+                        repair.append((int(slot[r]), bytes(slab[span[r, 0]:span[r, 1]])))
+                    del raw
+                text.close()
+                text = None
+                if parts or variants is None:
+                    break
     finally:
         if text is not None:
             text.close()
-        if handle:
-            L.vrx_vcf_destroy(handle)
 
     if parts:
         rows, slot, line, flag = (np.concatenate([p[k] for p in parts]) for k in range(4))

@@ -13,7 +13,6 @@ resident next to one ``GT_prob`` (``BulkData.set_cohort``), every pass reads a t
 for a chunk of samples (``vrx_bulk_fit_cohort``) and the stop rule runs per sample on the device.
 """
 import ctypes as C
-import weakref
 
 import numpy as np
 
@@ -91,7 +90,7 @@ def _vector(x, n, name):
     return np.array(a, dtype=np.float64)        # (a copy: the library writes the fit into it)
 
 
-class BulkData:
+class BulkData(_lib.Handle):
     """(AD, DP, GT_prob) of a bulk sample on one GPU (C handle ``vrx_bulk``)."""
 
     def __init__(self, AD, DP, GT_prob, device=None):
@@ -104,10 +103,10 @@ class BulkData:
         self.n_var, self.n_donor, self.n_GT = (int(x) for x in GT.shape)
         self.n_sample = 0                           # (of the cohort: none yet)
         self.device = device
-        self._h = C.c_void_p()
-        _lib.check(_lib.lib().vrx_bulk_create(device, self.n_var, self.n_donor, self.n_GT, _lib.dptr(GT),
-                                              _lib.dptr(AD), _lib.dptr(DP), C.byref(self._h)))
-        self._fin = weakref.finalize(self, _lib.lib().vrx_bulk_destroy, self._h)
+        L = _lib.lib()
+        super().__init__("BulkData", lambda out: L.vrx_bulk_create(device, self.n_var, self.n_donor, self.n_GT,
+                                                                   _lib.dptr(GT), _lib.dptr(AD), _lib.dptr(DP), out),
+                         L.vrx_bulk_destroy)
 
     @property
     def handle(self):
@@ -210,9 +209,6 @@ class BulkData:
         _lib.check(_lib.lib().vrx_bulk_loglik_cohort(self._h, P.shape[1], _lib.dptr(P), _lib.dptr(theta),
                                                      _lib.dptr(out)))
         return out[:, 0] if one else out
-
-    def close(self):
-        self._fin()
 
 
 def device_bulk(AD, DP=None, GT_prob=None, device=None):
