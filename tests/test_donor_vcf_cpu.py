@@ -1,7 +1,9 @@
 """CPU-only: load_donor_GPb's host path (force_host=True) against the real reference's numbers in
 tests/golden/donor_vcf/ (made by tests/golden/make_donor_vcf_golden.py), and the two arithmetic rules the device
 parser rests on -- the GP digit rule and the PL table -- restated in NumPy against float() and the reference
-expression."""
+expression.  These fixtures are well-formed; what the host path does with malformed text -- ragged rows, control bytes,
+truncated lines, a missing #CHROM line -- is held to the reference's result or exception class, file by file, in
+tests/test_vcf_mutation_cpu.py."""
 import os
 
 import numpy as np

@@ -1,8 +1,10 @@
 """read_cellVCF on the GPU (vrx_cellvcf.h): cellSNP's cells.vcf.gz -> sparse AD / DP in one pass over the text.  The
-yardstick is the host composition load_VCF -> read_sparse_GeneINFO (force_host=True, held to the real reference's
-numbers in tests/test_cell_vcf_cpu.py) and the reference's own arrays in tests/golden/c1_cell_vcf.npz; every comparison
-is np.array_equal on indptr / indices / data with their dtypes and == on the lists -- there is no tolerance, every
-device value is an integer below 10^9."""
+yardstick is the host composition load_VCF -> read_sparse_GeneINFO (force_host=True) and the reference's own arrays in
+tests/golden/c1_cell_vcf.npz.  The host path is held to the real reference on the CPU: to its numbers on the well-formed
+files in tests/test_cell_vcf_cpu.py, and to its result or its exception's class on every file of a corpus of mutated
+text in tests/test_vcf_mutation_cpu.py (the device meets the same corpus in tests/test_gpu_vcf_mutation.py).  Every
+comparison is np.array_equal on indptr / indices / data with their dtypes and == on the lists -- there is no tolerance,
+every device value is an integer below 10^9."""
 import json
 import os
 import subprocess

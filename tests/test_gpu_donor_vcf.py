@@ -1,8 +1,10 @@
 """load_donor_GPb on the GPU (vrx_vcf.h): the donor VCF read, matched to the cell variants and converted in one pass
-over the text.  The yardstick is the host composition load_VCF -> match_SNPs -> parse_donor_GPb (force_host=True,
-held to the real reference's numbers in tests/test_donor_vcf_cpu.py); every comparison is np.array_equal on indices
-and tobytes() on GPb -- there is no tolerance, every device value is a constant, a table entry made by NumPy or a
-correctly rounded quotient."""
+over the text.  The yardstick is the host composition load_VCF -> match_SNPs -> parse_donor_GPb (force_host=True),
+which is held to the real reference on the CPU: to its numbers on the well-formed fixtures in
+tests/test_donor_vcf_cpu.py, and to its result or its exception's class on every file of a corpus of mutated text in
+tests/test_vcf_mutation_cpu.py (the device meets the same corpus in tests/test_gpu_vcf_mutation.py).  Every comparison
+is np.array_equal on indices and tobytes() on GPb -- there is no tolerance, every device value is a constant, a table
+entry made by NumPy or a correctly rounded quotient."""
 import functools
 import gzip
 import json
@@ -199,8 +201,6 @@ def test_flagged_rows_are_repaired_on_the_host(vcf, tmp_path):
         12: lambda f: sub(f, 2, other[tag]),                   # another code: above 4095 / not digits[.digits]
         20: lambda f: sub(f, 0, "1e1,0,3"),
         30: lambda f: sub(f, 4, "+7,0.5e0,3"),
-        40: lambda f: f[:9],                                    # fewer than 10 fields
-        50: lambda f: f[:-1],                                   # a sample-field count other than S
         60: lambda f: f[:-1] + [f[-1] + "\r"],                  # what rstrip() removes: \r\n, blanks, a tab
         70: lambda f: f[:-1] + [f[-1] + "  "],
         82: lambda f: f + [""],
@@ -209,21 +209,37 @@ def test_flagged_rows_are_repaired_on_the_host(vcf, tmp_path):
         path, ids = flagged_file(tmp_path, tag, kinds)
         dev, host = both(vcf, path, tag, cells_regular_first(ids))
         assert dev["path"] == "device" and dev["n_repaired"] == len(kinds)
-        assert np.isnan(host["GPb"]).any()                     # the short rows: zeros over a zero sum, on both paths
+        assert not np.isnan(host["GPb"]).any()
     # GT: the codes float() takes are the device's too; the structural kinds remain
-    path, ids = flagged_file(tmp_path, "GT", {k: kinds[k] for k in (40, 50, 60, 70, 82)})
+    path, ids = flagged_file(tmp_path, "GT", {k: kinds[k] for k in (60, 70, 82)})
     dev, _ = both(vcf, path, "GT", cells_regular_first(ids))
-    assert dev["path"] == "device" and dev["n_repaired"] == 5
+    assert dev["path"] == "device" and dev["n_repaired"] == 3
+    # a row with fewer sample fields than the first row in cell order: the reference sizes its result by the first row
+    # and indexes every row up to there (vcf_utils.py:328-331), so both paths raise IndexError as it does
+    short = {40: lambda f: f[:9],                               # fewer than 10 fields
+             50: lambda f: f[:-1]}                              # a sample-field count other than S
+    for tag in TAGS:
+        for k in short:
+            path, ids = flagged_file(tmp_path, "%s_short%d" % (tag, k), {k: short[k]})
+            for kw in (dict(), dict(force_host=True)):
+                with pytest.raises(IndexError):
+                    vcf.load_donor_GPb(path, tag, cells_regular_first(ids), **kw)
 
 
 def test_a_short_first_row_and_dos_line_ends(vcf, tmp_path):
     """parse_donor_GPb sizes its result by the first row in cell order: when that row lacks a sample field the whole
-    call is the host's; a file with \\r\\n line ends has every matched row repaired and the same values"""
+    call is the host's, and the result has the first row's four donors -- the reference's loop never looks at the
+    fifth code of the later rows (vcf_utils.py:328-331); a file with \\r\\n line ends has every matched row repaired
+    and the same values"""
     path, ids = flagged_file(tmp_path, "GT", {12: lambda f: f[:-1]})
     cells = [ids[12]] + [x for x in cell_list(ids, 9) if x != ids[12]]
-    for kw in (dict(), dict(force_host=True)):                 # the later, complete rows do not fit the result
-        with pytest.raises(IndexError):
-            vcf.load_donor_GPb(path, "GT", cells, **kw)
+    regular, _ = flagged_file(tmp_path, "GT_regular", {})
+    for tag in TAGS:
+        dev, host = both(vcf, path, tag, cells)
+        assert dev["path"] == "host" and "first row" in dev["reason"] and host["GPb"].shape[1] == 4
+        with np.errstate(invalid="ignore", divide="ignore"):
+            want = vcf.load_donor_GPb(regular, tag, cells, force_host=True)
+        assert host["GPb"].tobytes() == want["GPb"][:, :4].tobytes() and np.array_equal(host["keep"], want["keep"])
     lines, ids = make_lines(60, 5, seed=60)                    # one sample name more than the rows have fields
     named6 = write_vcf(str(tmp_path / "named6.vcf.gz"), ["s%d" % k for k in range(6)], lines)
     dev, host = both(vcf, named6, "PL", cell_list(ids, 9))
@@ -236,22 +252,61 @@ def test_a_short_first_row_and_dos_line_ends(vcf, tmp_path):
         assert dev["path"] == "device" and dev["n_repaired"] == len(dev["keep"]) > 20
 
 
-@pytest.mark.parametrize("what,error", (("code", ValueError), ("subfield", IndexError), ("sum", IndexError),
-                                        ("fields", IndexError)))
+@pytest.mark.parametrize("what,error", (("code", ValueError), ("subfield", IndexError), ("sum", IndexError)))
 def test_both_paths_raise_the_same(vcf, tmp_path, what, error):
     def bad(f):
         if what == "code":
             return f[:9] + ["0/1:x,1,2:0.1,0.2,zz"] + f[10:]
         if what == "subfield":
             return f[:9] + ["0/1"] + f[10:]
-        if what == "sum":
-            return f[:9] + ["2/1:x,1,2:0.1,0.2,zz"] + f[10:]
-        return f + f[-1:]                                       # one sample field too many
-    for tag in (("GT",) if what == "sum" else TAGS if what == "fields" else ("PL", "GP")):
+        return f[:9] + ["2/1:x,1,2:0.1,0.2,zz"] + f[10:]
+    for tag in (("GT",) if what == "sum" else ("PL", "GP")):
         path, ids = flagged_file(tmp_path, tag, {12: bad})
         for kw in (dict(), dict(force_host=True)):
             with pytest.raises(error):
                 vcf.load_donor_GPb(path, tag, cells_regular_first(ids), **kw)
+
+
+def test_sample_fields_beyond_the_first_rows_are_ignored(vcf, tmp_path):
+    """a row with more sample fields than the first row in cell order: the reference's loop ends at the first row's
+    count (vcf_utils.py:328-331), so it returns what the file without the extra fields gives, whatever their codes
+    are (load_VCF still splits them: they have their subfields); both paths do"""
+    for tag in TAGS:
+        regular, ids = flagged_file(tmp_path, tag + "_regular", {})
+        want, _ = both(vcf, regular, tag, cells_regular_first(ids))
+        for name, more in (("one", lambda f: f + f[-1:]), ("junk", lambda f: f + ["x:y:z", ""])):
+            path, ids = flagged_file(tmp_path, "%s_%s" % (tag, name), {12: more})
+            dev, host = both(vcf, path, tag, cells_regular_first(ids))
+            assert dev["path"] == "device" and dev["n_repaired"] == 1 and host["GPb"].shape[1] == 5
+            same(dev, want)
+
+
+def test_a_short_field_on_a_line_nobody_matches(vcf, tmp_path):
+    """load_VCF splits every sample field of every kept line and indexes the tag's subfield (vcf_utils.py:60-65)
+    before anything is matched: a field without it raises IndexError wherever the line stands, on both paths; a line
+    the biallelic filter drops is never split"""
+    lines, ids = make_lines(300, 5, seed=21, edges=False)
+    cells = cells_regular_first(ids)
+
+    def swap(i, field):
+        f = lines[i].split("\t")
+        assert len(f[8].split(":")) == 3 and ids[i] not in cells
+        return write_vcf(str(tmp_path / ("short_%d_%d.vcf.gz" % (i, len(field)))), ["s%d" % k for k in range(5)],
+                         lines[:i] + ["\t".join(f[:12] + [field] + f[13:])] + lines[i + 1:])
+    for field, raises in (("0/1", ("PL", "GP")), ("0/1:1,2,3", ("GP",)), ("", ("PL", "GP"))):
+        path = swap(13, field)                                  # kept, tagged, not in the cell list
+        for tag in TAGS:
+            if tag in raises:
+                for kw in (dict(), dict(slab_bytes=1), dict(force_host=True)):
+                    with pytest.raises(IndexError):
+                        vcf.load_donor_GPb(path, tag, cells, **kw)
+            else:
+                dev, _ = both(vcf, path, tag, cells)
+                assert dev["path"] == "device" and dev["n_repaired"] == 0
+    path = swap(3, "0/1")                                       # multi-allelic: dropped before it is split
+    for tag in TAGS:
+        dev, _ = both(vcf, path, tag, cells)
+        assert dev["path"] == "device" and dev["n_repaired"] == 0
 
 
 def test_duplicates_take_the_host_path(vcf, tmp_path):

@@ -5,7 +5,9 @@
 //                   layer would change the line structure (non-ASCII, a '\r' not followed by '\n') set a status bit
 //   (hipcub)        the flagged positions compacted into the line starts
 //   vrx_vcf_lines   a wavefront per line: rstrip(), the first nine tabs by ballot over VRX_VCF_CHUNK bytes per step,
-//                   the biallelic filter, the position of the tag in FORMAT, the 64-bit hash of CHROM_POS_REF_ALT,
+//                   the biallelic filter, the position of the tag in FORMAT, every sample field of the line counted
+//                   for the tag's subfield (the one thing load_VCF asks of a line nobody matches), the 64-bit hash of
+//                   CHROM_POS_REF_ALT,
 //                   a binary search of the sorted cell hashes, the hit verified on the bytes, the cell variant's slot
 //                   claimed with an integer compare-and-swap
 //   (hipcub)        kept lines scanned into file ordinals, matched lines compacted
@@ -35,6 +37,8 @@ enum {
     VRX_VCF_ST_COMMENT = 8,     // a '#' line after the first data line
     VRX_VCF_ST_SHORT = 16,      // a line with fewer than 9 fields (load_VCF indexes f[8])
     VRX_VCF_ST_BYTES = 32,      // a non-ASCII byte or a '\r' that is not followed by '\n'
+    // (64, 128 and 256 are the cell reader's, vrx_cellvcf.h)
+    VRX_VCF_ST_SUBFIELD = 512,  // a sample field of a kept line without the tag's subfield (IndexError in load_VCF)
 };
 enum { VRX_VCF_ROW_REPAIR = 1 };  // row flag: the host parses this line
 
@@ -243,6 +247,20 @@ __global__ __launch_bounds__(VRX_VCF_BLOCK) void vrx_vcf_lines(const VrxVcfLines
             }
             ++k;
             p = q + 1;
+        }
+        // load_VCF splits every sample field of a kept line and indexes the tag's subfield (vcf_utils.py:60-65),
+        // whether a cell variant matches the line or not: a field with fewer subfields raises there
+        if (tagidx > 0 && nt >= 9) {
+            bool lacks = false;
+            for (uint32_t base = tp[8]; base < e; base += VRX_VCF_CHUNK) {
+                const uint32_t pos = base + lane;
+                if (pos < e && b[pos] == '\t') {  // the lane that holds a tab counts the ':' of the field behind it
+                    int32_t need = tagidx;
+                    for (uint32_t p = pos + 1; p < e && b[p] != '\t' && need > 0; ++p) need -= b[p] == ':';
+                    lacks |= need > 0;
+                }
+            }
+            if (__ballot(lacks) != 0) st = VRX_VCF_ST_SUBFIELD;
         }
         if (g.mode < 0) {
             slot = 0;

@@ -13,6 +13,7 @@ import gzip
 import os
 import shutil
 import subprocess
+import sys
 import time
 
 import ctypes as C
@@ -27,10 +28,27 @@ from .vireo_base import donor_match, match
 _MISSING = (".", "./.", ".|.")
 
 
-def _open_text(path):
+def _text_lines(path):
+    """The lines of a VCF as the reference's loader meets them (vcf_utils.py:112-126): a .gz / .bgz file is read in
+    binary, cut at '\\n' only and decoded as UTF-8 one line at a time, so a lone '\\r' stays inside its line and a bad
+    byte raises when its line is reached; a plain file is read in text mode.  The '\\n' itself is left off: every
+    use of a line starts with rstrip()."""
     if path.endswith(".gz") or path.endswith(".bgz"):
-        return gzip.open(path, "rt")
-    return open(path, "r")
+        with gzip.open(path, "rb") as fh:
+            rest = b""
+            while True:
+                block = fh.read(_READ_BYTES)
+                if not block:
+                    break
+                parts = (rest + block).split(b"\n")
+                rest = parts.pop()
+                for raw in parts:
+                    yield raw.decode("utf-8")
+            if rest:
+                yield rest.decode("utf-8")
+    else:
+        with open(path, "r") as fh:
+            yield from fh
 
 
 def _sparse_geno(rows, formats, format_list):
@@ -40,12 +58,12 @@ def _sparse_geno(rows, formats, format_list):
     indices, indptr = [], [0]
     tagged = np.zeros(len(format_list), np.int64)
     want = set(format_list)
+    if any(set(fmt) != want for fmt in formats):       # every line's names first (:32-35), then the entries
+        print("Error: require the same format for all variants.")
+        raise SystemExit
+    blank = ":".join(["."] * len(format_list))
     for fmt, calls in zip(formats, rows):
-        if set(fmt) != want:
-            print("Error: require the same format for all variants.")
-            raise SystemExit
         pos = [fmt.index(k) for k in format_list]
-        blank = ":".join(["."] * len(format_list))
         for cell, call in enumerate(calls):
             if call == blank or call == ".":
                 continue
@@ -81,31 +99,42 @@ def load_VCF(vcf_file, biallelic_only=False, load_sample=True, sparse=True,
     """-> dict(variants, FixedINFO, contigs, comments[, samples, GenoINFO, n_SNP_tagged])
     like the reference loader (vcf_utils.py:80-159)."""
     fixed, contigs, comments = {}, [], []
-    keys, samples, variants, rows, formats = [], [], [], [], []
-    with _open_text(vcf_file) as fh:
-        for line in fh:
+    keys, samples, variants, heads, rows = None, [], [], [], []
+    n_keys = sys.maxsize                                # before the #CHROM line: more fields than a line has
+    for line in _text_lines(vcf_file):
+        if line.startswith("#"):
             line = line.rstrip()
-            if line.startswith("#"):
-                if line.startswith("##contig="):
-                    contigs.append(line)
-                if line.startswith("#CHROM"):
-                    cols = line[1:].split("\t")
-                    keys = cols[:8]
-                    fixed = {k: [] for k in keys}
-                    if load_sample:
-                        samples = cols[9:]
-                else:
-                    comments.append(line)
-                continue
-            f = line.split("\t")
-            if biallelic_only and (len(f[3]) > 1 or len(f[4]) > 1):
-                continue
-            for k, v in zip(keys, f):
-                fixed[k].append(v)
-            variants.append("_".join((f[0], f[1], f[3], f[4])))
-            if load_sample:
-                formats.append(f[8].split(":"))
-                rows.append(f[9:])
+            if line.startswith("##contig="):
+                contigs.append(line)
+            if line.startswith("#CHROM"):
+                cols = line[1:].split("\t")
+                keys = cols[:8]
+                n_keys = len(keys)
+                for k in keys:
+                    fixed[k] = []
+                if load_sample:
+                    samples = cols[9:]
+            else:
+                comments.append(line)
+            continue
+        f = line.rstrip().split("\t")
+        if biallelic_only and (len(f[3]) > 1 or len(f[4]) > 1):
+            continue
+        if load_sample:
+            # FORMAT, or none: looked at after the last line (:22); kept as text, a list per line more slows the
+            # garbage collector by a quarter of the whole call
+            heads.append(f[8] if len(f) > 8 else None)
+            rows.append(f[9:])
+        if len(f) < n_keys:                             # the reference indexes f[i] for every key (:145-146)
+            if keys is None:
+                raise UnboundLocalError("a data line before the #CHROM line: no key_ids yet")
+            raise IndexError("list index out of range")
+        for k, v in zip(keys, f):
+            fixed[k].append(v)
+        variants.append("_".join((f[0], f[1], f[3], f[4])))
+    if None in heads:                                   # a line of eight fields raises here, after the text
+        raise IndexError("list index out of range")
+    formats = [x.split(":") for x in heads]
     rv = dict(variants=variants, FixedINFO=fixed, contigs=contigs, comments=comments)
     if load_sample:
         rv["samples"] = samples
@@ -142,7 +171,7 @@ def _parse_codes_vectorised(GT_dat, tag):
     None when the input is not a regular table of well-formed codes."""
     n_var = len(GT_dat)
     n_don = len(GT_dat[0]) if n_var else 0
-    if any(len(row) != n_don for row in GT_dat):
+    if any(len(row) != n_don for row in GT_dat):        # the loop's bounds are the first row's
         return None
     flat = [code for row in GT_dat for code in row]
     missing = np.fromiter((code in _MISSING for code in flat), dtype=bool, count=len(flat))
@@ -188,9 +217,11 @@ def parse_donor_GPb(GT_dat, tag='GT', min_prob=0.0):
 
 
 def _parse_codes_one_by_one(GT_dat, tag, P):
-    """the reference's own loop (vcf_utils.py:311-331) into the zeroed P: raises what it raises"""
-    for i, row in enumerate(GT_dat):
-        for j, code in enumerate(row):
+    """the reference's own loop (vcf_utils.py:311-331) into the zeroed P, over P's rows and columns as there
+    (:328-331): a row with fewer codes raises IndexError, the codes a row has beyond them are not looked at"""
+    for i in range(P.shape[0]):
+        for j in range(P.shape[1]):
+            code = GT_dat[i][j]
             if code in _MISSING:
                 P[i, j] = 1 / 3
             elif tag == 'GT':
@@ -222,8 +253,11 @@ _SLAB_BYTES = 256 << 20
 _SLAB_LIMIT = (1 << 31) - 64
 
 
+_DONOR_STATUS = _VCF_STATUS + ((512, "a sample field without the tag's subfield"),)
+
+
 def _status_reason(status):
-    return "; ".join(text for bit, text in _VCF_STATUS if status & bit)
+    return "; ".join(text for bit, text in _DONOR_STATUS if status & bit)
 
 
 def _donor_host(vcf_file, tag, variants, biallelic_only, min_prob, reason):
