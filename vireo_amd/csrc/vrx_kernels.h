@@ -447,6 +447,55 @@ constexpr int VRX_CHUNK = 256;  // entries per refill (64 lanes x 16 B of one LD
 #else
 #define VRX_STREAM_POLICY ""
 #endif
+// Issue priority of a wave inside a slab visit.  The four waves of a SIMD carry equal work per visit, but
+// the arbiter serves the oldest first (priority, then age): it finishes its rounds early and the youngest
+// runs the end of the visit alone, its read -> wait -> FMA chain with nothing to hide behind.  A wave lowers
+// its priority as it advances through the rounds, so the laggards of its SIMD catch up and the four reach the
+// slab barrier together; it is back at the round-0 value before the next visit's hand-over.  One s_setprio
+// at the head of a round, none inside a trip: every wave executes the same instructions on the same data in
+// the same order.  Measured at c3: the first-to-last spread of a SIMD's waves 30 % -> 14 % of a visit's trips
+// phase, 0.592 -> 0.564 ms per iteration (profiles/r08_visit_timeline.txt, profiles/r08_ab_wave_prio.txt).
+// -DVRX_WAVE_PRIO=0 builds the walk without it (the A/B).
+#ifndef VRX_WAVE_PRIO
+#define VRX_WAVE_PRIO 1
+#endif
+// priority of round r of nr: min(3, nr - 1 - r) -- the late rounds are told apart, where the tail forms
+// (6 rounds: 3 3 3 2 1 0; the even map 3 - 4 r / nr measured slower: DESIGN_HISTORY.md section 4.2)
+constexpr int vrx_round_prio(int r, int nr) { return r >= nr ? 0 : nr - 1 - r < 3 ? nr - 1 - r : 3; }
+template <int P>
+__device__ __forceinline__ void vrx_setprio() {
+#if VRX_WAVE_PRIO
+    static_assert(P >= 0 && P <= 3, "s_setprio takes two bits");
+    asm volatile("s_setprio %0" ::"n"(P));
+#endif
+}
+// (the immediate must be a constant: r is the index of an unrolled loop, so the switch folds to one case)
+template <int NR>
+__device__ __forceinline__ void vrx_round_setprio(int r) {
+    static_assert(NR <= 6, "rounds per visit");
+    switch (r) {
+        case 0: vrx_setprio<vrx_round_prio(0, NR)>(); break;
+        case 1: vrx_setprio<vrx_round_prio(1, NR)>(); break;
+        case 2: vrx_setprio<vrx_round_prio(2, NR)>(); break;
+        case 3: vrx_setprio<vrx_round_prio(3, NR)>(); break;
+        case 4: vrx_setprio<vrx_round_prio(4, NR)>(); break;
+        default: vrx_setprio<vrx_round_prio(5, NR)>(); break;
+    }
+}
+#ifdef VRX_PROBE_VISITS
+// Timing probe (scratch builds only; profiles/r08_visit_timeline.txt): lane 0 of every wave of workgroup 0
+// records the cycle counter behind the second slab barrier and at the end of its last round of the visit.
+// Record n of a wave: {barrier, end, n_rows << 32 | RW << 16 | slab, item}; vrx_probe_visits reads them back.
+constexpr int VRX_PV_CAP = 1 << 13;
+__device__ unsigned long long vrx_pv_log[VRX_PV_CAP][16][4];
+__device__ unsigned vrx_pv_n[16];
+extern "C" int vrx_probe_visits(unsigned long long* log, unsigned* n, int* cap) {
+    *cap = VRX_PV_CAP;
+    if (hipDeviceSynchronize() != hipSuccess) return 1;
+    if (hipMemcpyFromSymbol(n, HIP_SYMBOL(vrx_pv_n), sizeof(vrx_pv_n)) != hipSuccess) return 2;
+    return hipMemcpyFromSymbol(log, HIP_SYMBOL(vrx_pv_log), sizeof(vrx_pv_log)) != hipSuccess ? 3 : 0;
+}
+#endif
 // LDS of a pass = one 2-KiB entry ring per wave + the slab; a slab is staged through PF 16-B
 // registers per thread: 16 waves: 32 KiB + 8 x 16 KiB = 160 KiB
 constexpr int VRX_LDS_PF = (160 * 1024 - VRX_LDS_WAVES * VRX_RING * 4) / (VRX_LDS_WAVES * 64 * 16);
@@ -838,6 +887,7 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
     slab_fetch(s_lo, rvec);
     if (GATHER) rvec = rows_load(s_lo + 1);
     for (int s = s_lo; s < s_hi; ++s) {
+        vrx_round_setprio<NR>(0);  // the hand-over runs with all waves equal
         __syncthreads();  // every wave is done reading the previous slab
         // The slab's bnd words go to scalar registers BEFORE the next slab's prefetch is issued: the
         // compiler guards the readlanes with a full `s_waitcnt vmcnt(0)` (it cannot count across the loop),
@@ -857,8 +907,13 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
             if (GATHER) rvec = rows_load(s + 2);
         }
         __syncthreads();
+#ifdef VRX_PROBE_VISITS
+        unsigned long long pv_t0 = 0;
+        if (blockIdx.x == 0) pv_t0 = __builtin_readcyclecounter();
+#endif
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
+            vrx_round_setprio<NR>(r);
             // the round's entries are stored trip-major; the zero words that pad the round's
             // last trip are not executed
             const int braw = bcur[r];
@@ -989,6 +1044,20 @@ __global__ __launch_bounds__(VRX_LDS_WAVES * 64)
                     if (u * SPLIT < tail) entry(w[u], acc[r], acc2[r]);
             }
         }
+#ifdef VRX_PROBE_VISITS
+        if (blockIdx.x == 0) {
+            const unsigned long long pv_t1 = __builtin_readcyclecounter();
+            if ((threadIdx.x & 63) == 0) {
+                const unsigned pv_n = vrx_pv_n[wave];
+                unsigned long long* rec = vrx_pv_log[pv_n % VRX_PV_CAP][wave];
+                rec[0] = pv_t0;
+                rec[1] = pv_t1;
+                rec[2] = (unsigned long long)n_rows << 32 | (unsigned)(RW << 16) | (unsigned)(s & 0xffff);
+                rec[3] = (unsigned long long)item;
+                vrx_pv_n[wave] = pv_n + 1;
+            }
+        }
+#endif
     }
     // (every issued chunk has been awaited by the walk; this only guards the invariant that no
     //  LDS-DMA write is in flight when the workgroup's LDS is released)
