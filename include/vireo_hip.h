@@ -561,6 +561,16 @@ int vrx_cellvcf_rows(vrx_cellvcf* h, int64_t* indptr, int32_t* cell, int32_t* v0
  * the depth of the data: AD/BD words unless a count needs so many of them (> 1.56 words per
  * entry, estimated at vrx_problem_create) that one pair word per entry is cheaper. */
 int vrx_model_info(vrx_model* m, int32_t* info16);
+/* Which instances of vrx_spmm_lds the last LDS-resident pass of an orientation launched (orient 0: the
+ * variant pass, 1: the cell pass), one record of VRX_LDS_LAUNCH_FIELDS values per column-block launch, in
+ * launch order: the instance's template arguments MODE (the kernel's: 1 also for a variant pass over AD/BD
+ * virtual rows), RW (rows per wave), PADK, SPLIT, FORM; then kb (columns of the block), ld (columns per
+ * operand row), perm (1: the balanced gather list was passed), slab_rows and n_slab of the stream.  The
+ * selection that returns the kernel returns these values with it.  *n_out = launches recorded (0: that
+ * pass has not run on the LDS-resident path); at most `cap` records are written to out. */
+#define VRX_LDS_LAUNCH_FIELDS 10
+int vrx_model_lds_launches(vrx_model* m, int32_t orient, int32_t* out /* cap x VRX_LDS_LAUNCH_FIELDS */,
+                           int32_t cap, int32_t* n_out);
 int vrx_model_profile(vrx_model* m, int32_t enable);
 int vrx_model_profile_read(vrx_model* m, double* ms_total /* VRX_KERN_COUNT */,
                            int64_t* launches /* VRX_KERN_COUNT */);

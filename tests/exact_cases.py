@@ -2,7 +2,9 @@
 tests/test_gpu_update_exact.py (the device): cases, the two flows, and the judge.
 
 A case names its data, model shape, flags, state, priors, the environment that selects a kernel
-path and what ``DeviceModel.info()`` / ``DeviceCounts.build_info()`` must then report.  Flow A runs
+path and what ``DeviceModel.info()`` / ``DeviceCounts.build_info()`` must then report, and may name
+the instances of ``vrx_spmm_lds`` its passes must launch (``DeviceModel.lds_launches()``; the dispatch
+is restated here, and the oracle has no launches: the CPU twin skips that part).  Flow A runs
 every update once from the case's state (theta, GT, ID with logLik_ID, ELBO from a given logLik_ID,
 ELBO recomputed); flow B runs whole iterations (theta, GT, ID, ELBO in the reference's order,
 vireo_model.py:257-264, bmm_model.py:183-188) and judges each of their updates from the float64
@@ -87,6 +89,46 @@ def _size(N, M):
     return make
 
 
+def _edged(ad, dp, depth=9):
+    """the last variant and the last cell hold one entry, the same one: it is the only entry of the
+    last contracted row of the last slab in both passes (and the last entry of the last output row),
+    so a slab edge that loses or repeats it has this entry's whole weight"""
+    dp[-1, :], dp[:, -1] = 0, 0
+    dp[-1, -1] = depth
+    ad = np.minimum(ad, dp)
+    ad[-1, -1] = depth // 3
+    return ad, dp
+
+
+def _pair_tall():
+    """deep counts on more than two cell-pass slabs (1100 variants > 2 x 512): the 64-row tile of the
+    pair-word cell pass; 1100 cells = two such tiles"""
+    rng = np.random.default_rng(21)
+    N = M = 1100
+    dp = np.minimum(1 + rng.poisson(20.0, (N, M)), 255) * (rng.random((N, M)) < 0.03)
+    ad = rng.binomial(dp, rng.choice([0.03, 0.5, 0.96], (N, 1)))
+    dp[-1, -1], ad[-1, -1] = 31, 12                  # (an entry in the last row of both orientations)
+    return ad, dp
+
+
+def _shallow_tall():
+    """depth about 1 on three cell-pass slabs: AD/BD words at the 96-row cell tile; 1600 cells = one
+    tile of 1536 rows and one of 64"""
+    ad, dp = _draw(1100, 1600, 0.03, 0.3, 22)
+    dp[-1, -1], ad[-1, -1] = 3, 1
+    return ad, dp
+
+
+def _slab_edge(N, M):
+    def make():
+        return _edged(*_draw(N, M, 0.1, 1.0, 7 * N + M))
+    return make
+
+
+# contracted lengths one beyond and one short of a slab: 512 variants in the cell pass, 1024 cells
+# in the variant pass (512 pairs of cells under AD/BD virtual rows); about 200 output rows
+SLAB_EDGES = {"v513": (513, 200), "v511": (511, 200), "c1025": (200, 1025), "c1023": (200, 1023)}
+
 DATA = {
     "small": _small,
     "mid": lambda: _draw(600, 900, 0.05, 1.0, 2),
@@ -102,7 +144,12 @@ DATA = {
     "one_beyond": _one_beyond,
     "deep": lambda: _draw(200, 150, 0.3, 50.0, 15),             # spreads beyond exp's range
     "count_free": lambda: _count_free(),
+    "pair_tall": _pair_tall,
+    "shallow_tall": _shallow_tall,
 }
+DATA["pair_short"] = DATA["depth255"]
+for _tag, (_n, _m) in SLAB_EDGES.items():
+    DATA["slab_edge_" + _tag] = _slab_edge(_n, _m)
 for _n, _m in ((255, 1), (1, 63), (256, 64), (257, 65), (1025, 257)):
     DATA["size_%dx%d" % (_n, _m)] = _size(_n, _m)
 
@@ -228,6 +275,79 @@ many = lambda v: v > 1                                                    # noqa
 some = lambda v: v > 0                                                    # noqa: E731
 
 
+# ---- which instance of vrx_spmm_lds a launch takes ------------------------------------------
+# The dispatch of vrx_engine.hip restated (lds_kernel, lds_kernel_rw, lds_kernel_form1, pick_rw_cell,
+# tile_layout): what ``DeviceModel.lds_launches()`` must report for a problem shape, its stream forms
+# and the total operand width Kt (restarts x K).  An instance is (MODE, RW, PADK, SPLIT, FORM).
+RW_VARIANT, RW_CELL, RW_CELL_PAIR, RW_CELL_SHORT = 32, 96, 64, 32
+SLAB_CELL, SLAB_VARIANT, LDS_WAVES = 512, 1024, 16
+LAUNCH_KEYS = ("inst_variant", "inst_cell", "perm", "slab_fill")    # ``want`` keys held by the launch record
+
+
+def _up(a, b):
+    return -(-a // b)
+
+
+def cell_rows_per_wave(n_var, n_cell, cell_form, n_cu):
+    """pick_rw_cell: the short tile when the problem has at most two cell-pass slabs and the busiest
+    CU's visits x rows per wave come out lower"""
+    tall = RW_CELL if cell_form == 1 else RW_CELL_PAIR
+    slabs = _up(n_var, SLAB_CELL)
+
+    def cost(rw):
+        return _up(_up(n_cell, LDS_WAVES * rw) * slabs, max(1, n_cu)) * rw
+    return RW_CELL_SHORT if slabs <= 2 and cost(RW_CELL_SHORT) < cost(tall) else tall
+
+
+def block_launches(mode, rw, form, Kt):
+    """one (MODE, RW, PADK, SPLIT, FORM, kb, ld) per block of 16 columns.  Pair words (FORM 0): 4 / 2
+    entries at once when kb <= 4 / 8, element-wise staging when kb % 4 or the rows are strided
+    (Kt > 16).  AD/BD words (FORM 1): PADK 0 flat rows of 16 columns, 2 whole 16-B units (kb and ld
+    even), 1 element-wise."""
+    out = []
+    for c0 in range(0, Kt, 16):
+        kb, strided = min(16, Kt - c0), Kt > 16
+        if form == 1:
+            out.append((mode, rw, 0 if kb == 16 and not strided else 2 if (kb | Kt) % 2 == 0 else 1, 1, 1, kb, Kt))
+        else:
+            out.append((mode, rw, int(kb % 4 != 0 or strided), 4 if kb <= 4 else 2 if kb <= 8 else 1, 0, kb, Kt))
+    return out
+
+
+def expected_launches(n_var, n_cell, Kt, cell_form, var_form, n_cu):
+    """(variant pass, cell pass).  The variant pass over AD/BD virtual rows (var_form 3) runs the cell
+    pass's kernel (MODE 1, FORM 1) at its tall tile."""
+    var = block_launches(1, RW_CELL, 1, Kt) if var_form == 3 else block_launches(0, RW_VARIANT, 0, Kt)
+    return var, block_launches(1, cell_rows_per_wave(n_var, n_cell, cell_form, n_cu), cell_form, Kt)
+
+
+def slab_geometry(n_rows, n_contract, rw, nominal, n_cu, fill):
+    """(slab_rows, n_slab) of tile_layout for n_rows row pieces.  VIREO_LDS_FILL_CUS:
+    with fewer (tile, slab) visits than CUs the slabs are shortened until every CU has one -- to a
+    multiple of 16 rows, 64 at least; one or two slabs are first spread over whole rounds of CUs
+    where that leaves four rows per wave."""
+    slab, n_slab, n_tile = nominal, _up(n_contract, nominal), _up(n_rows, LDS_WAVES * rw)
+    if fill and n_cu > 0:
+        def spread(n_tile):
+            nt = _up(n_tile * n_slab, n_cu) * n_cu // n_slab
+            return nt if nt > n_tile and nt * LDS_WAVES * 16 <= max(n_rows, 1) * 4 else n_tile
+        if n_slab <= 2:
+            n_tile = spread(n_tile)
+        if n_tile * n_slab < n_cu:
+            slab = min(nominal, max(64, _up(_up(n_contract, _up(n_cu, n_tile)), 16) * 16))
+            n_slab = _up(n_contract, slab)
+    return slab, n_slab
+
+
+def expected_slabs(n_var, n_cell, cell_form, var_form, n_cu, fill, extra=(0, 0)):
+    """(variant pass, cell pass): (slab_rows, n_slab); extra: the row pieces beyond one per row
+    (``info()``'s extra_pieces_*: the tiles are counted in pieces)"""
+    var = (slab_geometry(2 * n_var + extra[0], (n_cell + 1) // 2, RW_CELL, SLAB_CELL, n_cu, fill) if var_form == 3
+           else slab_geometry(n_var + extra[0], n_cell, RW_VARIANT, SLAB_VARIANT, n_cu, fill))
+    rw = cell_rows_per_wave(n_var, n_cell, cell_form, n_cu)
+    return var, slab_geometry(n_cell + extra[1], n_var, rw, SLAB_CELL, n_cu, fill)
+
+
 def _a(*a, **k):
     _case(CASES_A, *a, **k)
 
@@ -238,7 +358,8 @@ def _b(*a, **k):
 
 # paths: gather kernels / LDS-resident passes, work-list sizes, one and many contracted ranges
 _a("gather", "mid", K=6, env=LDS0, want=OFF)
-_a("lds", "mid", K=6, env=LDS1, want=dict(ON, cell_form=1, var_form=3))
+_a("lds", "mid", K=6, env=LDS1, want=dict(ON, cell_form=1, var_form=3, inst_variant={(1, 96, 2, 1, 1)},
+                                           inst_cell={(1, 32, 2, 1, 1)}))     # (AD/BD words, the short cell tile)
 for blocks in (1, 16, 1024):
     _a("blocks%d_one" % blocks, "tiny", K=8, env=dict(LDS1, VIREO_LDS_BLOCKS=str(blocks)),
        want=dict(ON, ranges_variant=1, ranges_cell=1))
@@ -267,7 +388,8 @@ _a("build_device", "mid", K=6, env=dict(LDS1, VIREO_BUILD="device"), want=dict(O
 for K in (1, 2, 3, 4, 5, 8, 9, 16, 17, 33, 64, 70):
     _a("K%d_gather" % K, "small", K=K, env=LDS0, want=OFF)
     if K >= 2:                                   # (one column stays on the gather kernels)
-        _a("K%d_lds" % K, "small", K=K, env=LDS1, want=ON)
+        _a("K%d_lds" % K, "small", K=K, env=LDS1,  # (AD/BD words at the short cell tile: flat rows, element-wise)
+           want=dict(ON, **({16: dict(inst_cell={(1, 32, 0, 1, 1)}), 5: dict(inst_cell={(1, 32, 1, 1, 1)})}.get(K, {}))))
 for T in (2, 3, 4, 8):
     _a("T%d_gather" % T, "small", K=4, T=T, env=LDS0, want=OFF)
     _a("T%d_lds" % T, "small", K=5, T=T, env=LDS1, want=ON)
@@ -314,6 +436,69 @@ _a("underflow_id", "deep", K=4, state=[st_sharp_gt], env=LDS0, want=OFF)
 _a("underflow_gt", "deep", K=4, state=[st_one_hot_id], env=LDS0, want=OFF)
 _a("underflow_lds", "deep", K=4, state=[st_sharp_gt, st_one_hot_id], env=LDS1, want=ON)
 
+# ---- every instance of vrx_spmm_lds, named ---------------------------------------------------
+# Each case names the instances its passes must launch (inst_*: sets of (MODE, RW, PADK, SPLIT, FORM));
+# the launch record of the model (DeviceModel.lds_launches) is held to them, and to the restated
+# dispatch above block by block.  PADK, SPLIT per block of the pair-word passes / PADK of the AD/BD ones:
+PAIR_BLOCKS = {2: {(1, 4)}, 3: {(1, 4)}, 4: {(0, 4)}, 6: {(1, 2)}, 7: {(1, 2)}, 8: {(0, 2)}, 11: {(1, 1)}, 15: {(1, 1)},
+               16: {(0, 1)}, 17: {(1, 1), (1, 4)}, 18: {(1, 1), (1, 4)}, 33: {(1, 1), (1, 4)}}
+F1_BLOCKS = {16: {0}, 7: {1}, 12: {2}, 6: {2}, 17: {1}, 18: {2}}
+PAIRS = dict(LDS1, VIREO_CELL_FORM="0", VIREO_VAR_FORM="0")
+
+
+def _pair_inst(K, rw_cell):
+    return dict(inst_variant={(0, RW_VARIANT, pk, sp, 0) for pk, sp in PAIR_BLOCKS[K]},
+                inst_cell={(1, rw_cell, pk, sp, 0) for pk, sp in PAIR_BLOCKS[K]})
+
+
+def _f1_inst(K, rw_cell):      # (the variant pass over virtual rows: the cell pass's kernel at its tall tile)
+    return dict(inst_variant={(1, RW_CELL, pk, 1, 1) for pk in F1_BLOCKS[K]},
+                inst_cell={(1, rw_cell, pk, 1, 1) for pk in F1_BLOCKS[K]})
+
+
+# pair words: the six PADK x SPLIT instances of the variant pass and of each cell tile height; K > 16:
+# strided blocks of 16 with an odd (17, 33) and an even (18) row stride, and the blocks of 1 and 2 behind them
+for K in (2, 4, 6, 8, 11, 16, 17, 18, 33):
+    for tag, dat, rw in (("short", "pair_short", RW_CELL_SHORT), ("tall", "pair_tall", RW_CELL_PAIR)):
+        _a("pair_%s_K%d" % (tag, K), dat, K=K, env=PAIRS,
+           want=dict(ON, cell_form=0, var_form=0, perm=False, **_pair_inst(K, rw)))
+# clone mode on the pair words its deep counts choose by themselves (nothing forced)
+for K in (3, 8, 16):
+    _a("clone_pairs_K%d" % K, "clone", K=K, kind="bmm", state=[st_random_theta], env=LDS1,
+       want=dict(ON, cell_form=0, var_form=0, perm=False, **_pair_inst(K, RW_CELL_SHORT)))
+# AD/BD words at the 96-row cell tile: flat rows, element-wise, whole units, strided blocks
+for K in (16, 7, 12, 17):
+    _a("shallow_tall_K%d" % K, "shallow_tall", K=K, env=LDS1,
+       want=dict(ON, cell_form=1, var_form=3, perm=False, **_f1_inst(K, RW_CELL)))
+# balanced slabs: the permuted gather of each staging path (flat, element-wise, whole units is
+# ``balanced`` above), inside column blocks, and over rows cut into pieces
+BALANCED = dict(LDS1, VIREO_BUILD="device", VIREO_LDS_SPLIT_X10="60")
+for K in (16, 7, 17):
+    _a("balanced_K%d" % K, "many", K=K, balance=True, env=BALANCED,
+       want=dict(ON, balanced_variant=True, balanced_cell=True, device_built=True, cell_form=1, var_form=3,
+                 perm=True, **_f1_inst(K, RW_CELL)))
+_a("balanced_split_K16", "many", K=16, balance=True, env=dict(BALANCED, VIREO_LDS_SPLIT_X10="5"),
+   want=dict(ON, balanced_variant=True, balanced_cell=True, device_built=True, cell_form=1, var_form=3,
+             extra_pieces_cell=some, extra_pieces_variant=some, perm=True, **_f1_inst(16, RW_CELL)))
+# (balanced slabs are AD/BD streams: asked for on pair words the build leaves the stream unbalanced and
+# the pass gets no gather list -- the pair-word instances have no permuted staging)
+_a("balanced_pairs", "pair_tall", K=6, balance=True, env=dict(PAIRS, VIREO_BUILD="device"),
+   want=dict(ON, balanced_variant=False, balanced_cell=False, device_built=True, cell_form=0, var_form=0,
+             perm=False, **_pair_inst(6, RW_CELL_PAIR)))
+# slab edges: a last slab of one row and of one row short, in the flat copy (K = 16: lanes past the
+# slab re-read its last unit) and the element-wise staging (K = 7), with the slabs as laid out for
+# the CUs (VIREO_LDS_FILL_CUS=1: shortened) and at their nominal height
+for tag in SLAB_EDGES:
+    for fill in (1, 0):
+        for K in (16, 7):
+            env = dict(VIREO_LDS_FILL_CUS=str(fill))
+            _a("slab_edge_%s_fill%d_K%d" % (tag, fill, K), "slab_edge_" + tag, K=K, env=dict(LDS1, **env),
+               want=dict(ON, cell_form=1, var_form=3, perm=False,
+                         slab_fill=bool(fill), **_f1_inst(K, RW_CELL_SHORT)))
+            _a("slab_edge_%s_fill%d_pairs_K%d" % (tag, fill, K), "slab_edge_" + tag, K=K, env=dict(PAIRS, **env),
+               want=dict(ON, cell_form=0, var_form=0, perm=False,
+                         slab_fill=bool(fill), **_pair_inst(K, RW_CELL_SHORT)))
+
 # the fit loop's own kernels and fusions
 FUSE1, FUSE0 = {"VIREO_FUSE_SOFTMAX": "1"}, {"VIREO_FUSE_SOFTMAX": "0"}
 # (fused_softmax: whether the cell softmax runs in the cell pass's epilogue -- small gather problems,
@@ -338,6 +523,12 @@ _b("clone_lds", "clone", K=5, kind="bmm", state=[st_random_theta], prior=[pr_bmm
    env=dict(LDS1, VIREO_ELBO_RIDE="0"), want=ON, fused_softmax=False)
 _b("batch3", "mid", K=4, restarts=3, env=LDS1, want=dict(ON, n_batch=3))
 _b("batch3_gather", "small", K=4, restarts=3, iters=2, env=LDS0, want=dict(OFF, n_batch=3))
+# restart batches as one operand: 5 x 3 = 15 columns on pair words (one block, element-wise), 3 x 6 = 18
+# columns on AD/BD words (blocks of 16 and 2 with an even row stride: whole 16-B units)
+_b("batch5_pairs", "pair_short", K=3, restarts=5, env=PAIRS,
+   want=dict(ON, n_batch=5, cell_form=0, var_form=0, perm=False, **_pair_inst(15, RW_CELL_SHORT)))
+_b("batch3_blocks", "mid", K=6, restarts=3, env=LDS1,
+   want=dict(ON, n_batch=3, cell_form=1, var_form=3, perm=False, **_f1_inst(18, RW_CELL_SHORT)))
 
 
 # ------------------------------------------------------------------------------------

@@ -6,13 +6,18 @@
   for honest float64 arithmetic) or a restatement that computed something else would show here.
 * The checker has teeth: results corrupted the way a kernel would be wrong fail the rule the GPU
   test asserts (``exact_np.held``).
+* The cases that name instances of the LDS pass cover all 24 and agree with the restated dispatch; on
+  their data, four defects of a slab edge, a column block or a row piece, planted through the oracle,
+  fail the rule.
 * On the c1_onestep fixture (values of the real reference) the restatement agrees with the golden
   values within the same rule.
 """
+import copy
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
+from scipy.sparse import csc_matrix
 from scipy.special import betaln, digamma
 
 from oracle import vireo_oracle as O
@@ -190,6 +195,146 @@ def test_d_partial_added_twice_fails(gather):
     s1 = s1 + 1e-9 * np.sum(A[:, :, None] * s.GT[:256], axis=(0, 1))
     assert _fails(p, out, u_orc, "beta_mu", s1 / (s1 + s2))
     assert _fails(p, out, u_orc, "beta_sum", s1 + s2)
+
+
+# ---------------------------------------------------------------- the instance cases
+def _named(table):
+    return {n: c for n, c in table.items() if "inst_cell" in c.want or "inst_variant" in c.want}
+
+
+def test_every_instance_of_the_lds_pass_is_named_by_a_case():
+    """the 24 instances of vrx_spmm_lds -- pair words: PADK {0, 1} x SPLIT {1, 2, 4} of the variant pass
+    (32 rows per wave) and of the cell pass at 64 and at 32 rows; AD/BD words: PADK {0, 1, 2} at 96 and
+    32 rows -- each in the ``inst_*`` of some case, and what a case names is what the restated dispatch
+    gives for its shape (at the 256 CUs the tile heights were worked out for)"""
+    every = {(m, rw, pk, sp, 0) for m, rw in ((0, 32), (1, 64), (1, 32)) for pk in (0, 1) for sp in (1, 2, 4)}
+    every |= {(1, rw, pk, 1, 1) for rw in (96, 32) for pk in (0, 1, 2)}
+    assert len(every) == 24
+    named = set()
+    for table in (EC.CASES_A, EC.CASES_B):
+        for name, c in _named(table).items():
+            N, M = EC.data(c.data)[0].shape
+            rule = EC.expected_launches(N, M, c.K * c.restarts, c.want.get("cell_form", 1),
+                                        c.want.get("var_form", 3), 256)
+            for o, launches in zip(("variant", "cell"), rule):
+                if "inst_" + o in c.want:
+                    assert {l[:5] for l in launches} == c.want["inst_" + o], (name, o, launches)
+                    named |= c.want["inst_" + o]
+    assert named == every, named ^ every
+
+
+def test_slab_edge_data_sits_on_the_edges():
+    """the instance cases' data has an entry in the last row of both orientations; the slab-edge sets hold
+    exactly one there, one row beyond / short of a nominal slab, and their slabs -- nominal and as
+    shortened for the CUs -- end where the cases say: a last slab of 1 and of 63 / 511 / 1023 rows"""
+    for name in ("pair_short", "pair_tall", "shallow_tall", "clone", "many"):
+        dp = EC.data(name)[1]
+        assert dp[-1, :].nnz > 0 and dp[:, -1].nnz > 0, name
+    for tag, (N, M) in EC.SLAB_EDGES.items():
+        dp = EC.data("slab_edge_" + tag)[1]
+        assert dp.shape == (N, M) and dp[-1, :].nnz == 1 and dp[:, -1].nnz == 1 and dp[-1, -1] > 0
+    geo = EC.expected_slabs
+    assert geo(513, 200, 1, 3, 256, False) == ((512, 1), (512, 2)) and geo(513, 200, 1, 3, 256, True)[1] == (64, 9)
+    assert geo(511, 200, 0, 0, 256, False) == ((1024, 1), (512, 1)) and geo(511, 200, 0, 0, 256, True)[1] == (64, 8)
+    assert geo(200, 1025, 1, 3, 256, False)[0] == (512, 2) and geo(200, 1025, 1, 3, 256, True)[0] == (64, 9)
+    assert geo(200, 1025, 0, 0, 256, False)[0] == (1024, 2) and geo(200, 1025, 0, 0, 256, True)[0] == (64, 17)
+    assert geo(200, 1023, 1, 3, 256, False)[0] == (512, 1) and geo(200, 1023, 0, 0, 256, True)[0] == (64, 16)
+    # (a problem of the flagship's size keeps its nominal slabs)
+    assert geo(40000, 20000, 1, 3, 256, True) == ((512, 20), (512, 79))
+
+
+# ---------------------------------------------------------------- planted defects on the instance cases
+def _with_data(p, ad, dp):
+    """the case with other counts in the backend's hands; the exact side (p.C) keeps the true ones"""
+    q = copy.copy(p)
+    q.AD, q.DP = csc_matrix(ad), csc_matrix(dp)
+    return q
+
+
+def _planted(name, change, keys):
+    """the oracle run on counts a defective pass would in effect have summed, judged against the exact
+    update of the true counts: every output in ``keys`` must miss the rule"""
+    p = EC.problem_a(name)
+    u_orc = EC.distances_a(p, EC.run_a(p, EC.OracleBackend(p)))
+    ad, dp = p.AD.toarray(), p.DP.toarray()
+    change(ad, dp)
+    q = _with_data(p, ad, dp)
+    u = EC.distances_a(p, EC.run_a(q, EC.OracleBackend(q)))
+    for k in keys:
+        print("%-28s %-10s %.3g units against the oracle's %.2f" % (name, k, u[k], u_orc[k]))
+        assert not X.held(u[k], u_orc[k]), (name, k, u[k], u_orc[k])
+
+
+# (the outputs that read the counts; flow A's ELBO parts take a given logLik_ID)
+SUMS = ("beta_mu", "beta_sum", "GT_prob", "logLik_ID", "ID_prob", "re_logLik_ID")
+
+
+@pytest.mark.parametrize("tag", list(EC.SLAB_EDGES))
+def test_dropped_entry_of_the_last_slab_fails(tag):
+    """the single entry of the last contracted row of the last slab (both passes contract it) dropped"""
+    def drop(ad, dp):
+        ad[-1, -1] = dp[-1, -1] = 0
+    _planted("slab_edge_%s_fill0_K16" % tag, drop, SUMS)
+    _planted("slab_edge_%s_fill1_pairs_K7" % tag, drop, SUMS)
+
+
+@pytest.mark.parametrize("name", ["pair_tall_K17", "shallow_tall_K7", "slab_edge_v513_fill1_K7"])
+def test_last_entry_of_the_last_output_row_counted_twice_fails(name):
+    def twice(ad, dp):
+        for a in (ad, dp):                       # last cell: its last variant; last variant: its last cell
+            a[np.flatnonzero(dp[:, -1])[-1], -1] *= 2
+        n = np.flatnonzero(dp[-1, :])[-1]
+        if n != dp.shape[1] - 1 or np.flatnonzero(dp[:, -1])[-1] != dp.shape[0] - 1:
+            ad[-1, n], dp[-1, n] = 2 * ad[-1, n], 2 * dp[-1, n]
+    _planted(name, twice, SUMS)
+
+
+@pytest.mark.parametrize("name", ["pair_short_K17", "pair_tall_K17", "shallow_tall_K17", "balanced_K17"])
+def test_last_column_taken_from_the_first_fails(name):
+    """column 16 of a K = 17 operand (the block of one column) read from column 0: the cell pass's
+    logLik_ID column and the variant pass's sums over that donor"""
+    p = EC.problem_a(name)
+    out = EC.run_a(p, EC.OracleBackend(p))
+    u_orc = EC.distances_a(p, out)
+    L = out["logLik_ID"].copy()
+    L[:, 16] = L[:, 0]
+    assert _fails(p, out, u_orc, "logLik_ID", L)
+    q = copy.copy(p)                              # the variant pass: ID_prob's column 16 from column 0
+    q.states = [copy.copy(p.s0)]
+    q.s0 = q.states[0]
+    q.s0.ID = p.s0.ID.copy()
+    q.s0.ID[:, 16] = q.s0.ID[:, 0]
+    bad = EC.OracleBackend(q)
+    mu, sm = bad.theta()
+    assert _fails(p, out, u_orc, "beta_mu", mu) and _fails(p, out, u_orc, "beta_sum", sm)
+    assert _fails(p, out, u_orc, "GT_prob", bad.gt())
+
+
+def test_a_row_piece_left_out_fails():
+    """balanced_split_K16: rows longer than half the mean are cut into P interleaved pieces (entry j of
+    a row -> piece j % P, cap = max(64, mean / 2)); one piece of the longest cell and of the longest
+    variant left out"""
+    name = "balanced_split_K16"
+    p = EC.problem_a(name)
+    dp0 = p.DP.toarray()
+
+    def pieces(lengths):
+        cap = max(64, int(lengths.mean() * 0.5 + 0.5))
+        return int(np.argmax(lengths)), -(-int(lengths.max()) // cap)
+
+    def cell_piece(ad, dp):
+        m, P = pieces((dp0 > 0).sum(0))
+        assert P > 1
+        rows = np.flatnonzero(dp0[:, m])[::P]
+        ad[rows, m] = dp[rows, m] = 0
+    _planted(name, cell_piece, ("logLik_ID", "ID_prob", "re_logLik_ID"))
+
+    def variant_piece(ad, dp):
+        n, P = pieces((dp0 > 0).sum(1))
+        assert P > 1
+        cols = np.flatnonzero(dp0[n, :])[::P]
+        ad[n, cols] = dp[n, cols] = 0
+    _planted(name, variant_piece, ("beta_mu", "beta_sum", "GT_prob"))
 
 
 # ---------------------------------------------------------------- the restatement against the fixture

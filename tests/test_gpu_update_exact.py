@@ -17,6 +17,8 @@ there every update of every iteration is judged from the float64 state the devic
 in front of it (a run of each length from the same state), so what one update rounds is the next
 one's input and never its excuse.  Every case asserts through ``info()`` / ``build_info()`` that
 the path it names ran, and the cases that switch a fusion of the fit loop count its launches.
+Every case is also held, after its updates have run, to the instances of ``vrx_spmm_lds`` its passes
+launched (``DeviceModel.lds_launches()``): template arguments, column blocks, gather list, slabs.
 The cases are in tests/exact_cases.py; the same sweep runs on the CPU with the oracle in the
 device's place (tests/test_exact_cpu.py).
 
@@ -85,8 +87,45 @@ def _assert_path(p, dm, counts):
     """the kernels, formats and builder the case names are the ones this model runs"""
     seen = dict(dm.info(), **counts.build_info())
     for k, v in p.spec.want.items():
-        assert v(seen[k]) if callable(v) else seen[k] == v, (p.spec.name, k, seen[k])
+        if k not in EC.LAUNCH_KEYS:
+            assert v(seen[k]) if callable(v) else seen[k] == v, (p.spec.name, k, seen[k])
     return seen
+
+
+def _assert_instances(p, dm, seen):
+    """the instances of ``vrx_spmm_lds`` the passes of this case launched, from the model's launch
+    record: block by block what the dispatch rule (restated in tests/exact_cases.py) gives for the
+    shape, the stream forms and the operand's width; the set a case names (``inst_*``); the gather
+    list passed exactly to the balanced streams; and the slab geometry of the cases that set it
+    (``slab_fill``).  A pass on the gather kernels has recorded nothing."""
+    sp, want, name = p.spec, p.spec.want, p.spec.name
+    n_cu = _lib_info()["n_cu"]
+    got = dict(zip(("variant", "cell"), dm.lds_launches()))
+    rule = dict(zip(("variant", "cell"), EC.expected_launches(p.N, p.M, p.K * sp.restarts, seen["cell_form"],
+                                                              seen["var_form"], n_cu)))
+    if "slab_fill" in want:
+        extra = (seen["extra_pieces_variant"], seen["extra_pieces_cell"])
+        slabs = dict(zip(("variant", "cell"), EC.expected_slabs(p.N, p.M, seen["cell_form"], seen["var_form"],
+                                                                n_cu, want["slab_fill"], extra)))
+    for o in ("variant", "cell"):
+        print("%-28s %-7s launches %s" % (name, o, [tuple(int(v) for v in l) for l in got[o]]))
+        if not seen["lds_" + o]:
+            assert got[o] == [], (name, o, got[o])
+            continue
+        assert [tuple(l[:7]) for l in got[o]] == rule[o], (name, o, got[o], rule[o])
+        if "inst_" + o in want:
+            assert {tuple(l[:5]) for l in got[o]} == want["inst_" + o], (name, o, got[o])
+        perm = want.get("perm", seen["balanced_" + o])
+        assert perm == seen["balanced_" + o] and all(l.perm == perm for l in got[o]), (name, o, perm, got[o])
+        if "slab_fill" in want:
+            for l in got[o]:
+                assert (l.slab_rows, l.n_slab) == slabs[o], (name, o, l, slabs[o])
+                assert l.slab_rows % 16 == 0 and l.slab_rows >= 64, (name, o, l)
+
+
+def _lib_info():
+    from vireo_amd import _lib
+    return _lib.device_info(0)
 
 
 class DeviceBackend:
@@ -228,8 +267,10 @@ def test_each_update_against_exact(va, monkeypatch, name):
     p = EC.problem_a(name)
     counts = _counts(p, monkeypatch)
     be = DeviceBackend(p, counts)
-    _assert_path(p, be.dm, counts)
-    u_dev = EC.distances_a(p, EC.run_a(p, be))
+    seen = _assert_path(p, be.dm, counts)
+    out = EC.run_a(p, be)
+    _assert_instances(p, be.dm, seen)
+    u_dev = EC.distances_a(p, out)
     u_orc = EC.distances_a(p, EC.run_a(p, EC.OracleBackend(p)))
     _judge("A", name, u_dev, u_orc)
 
@@ -239,11 +280,12 @@ def test_fit_loop_iterations_against_exact(va, monkeypatch, name):
     p = EC.problem_b(name)
     counts = _counts(p, monkeypatch)
     be = DeviceBackend(p, counts)
-    _assert_path(p, be.batch or be.dm, counts)
+    seen = _assert_path(p, be.batch or be.dm, counts)
     orc = EC.OracleBackend(p)
     for r in range(p.spec.restarts):
         u_dev = EC.distances_b(p, EC.run_b(p, be, r), r)
         if r == 0:
             _assert_launches(p, be)
+            _assert_instances(p, be.batch or be.dm, seen)
         u_orc = EC.distances_b(p, EC.run_b(p, orc, r), r)
         _judge("B", name if p.spec.restarts == 1 else "%s[%d]" % (name, r), u_dev, u_orc)

@@ -1855,6 +1855,13 @@ struct StatePart {
     size_t block() const { return (size_t)(rows * cols); }
 };
 
+// One column-block launch of an LDS-resident pass: the template arguments of the instance that ran
+// (MODE: the kernel's, 1 for the variant pass over virtual rows), the block's columns and the operand's
+// row stride, whether the balanced gather list was passed, and the slab geometry of the stream
+struct LdsLaunch {
+    int32_t mode, rw, padk, split, form, kb, ld, perm, slab_rows, n_slab;
+};
+
 struct vrx_model {
     vrx_problem* p = nullptr;
     vrx_model_cfg cfg{};
@@ -1916,6 +1923,8 @@ struct vrx_model {
     double prof_ms[VRX_KERN_COUNT] = {0, 0, 0};
     int64_t prof_n[VRX_KERN_COUNT] = {0, 0, 0};
     hipEvent_t t0 = nullptr, t1 = nullptr;
+    // the launches of the last LDS-resident pass of each orientation (0 variant, 1 cell): vrx_model_lds_launches
+    std::vector<LdsLaunch> lds_log[2];
 
     ~vrx_model() {
         if (h_pin) (void)hipHostFree(h_pin);
@@ -2488,30 +2497,45 @@ static bool lds_eligible(const vrx_problem& p, int K) {
     return o.tiled.ready && K >= 2;
 }
 
+// One instance of vrx_spmm_lds: the kernel together with the template arguments it was compiled with.
+// The selection below returns both from one place, so what a launch records (LdsLaunch,
+// vrx_model_lds_launches) cannot drift from what it ran.
+using LdsKernel = void (*)(const uint32_t*, const int64_t*, const int32_t*, const int32_t*, const int32_t*,
+                           const int32_t*, int, int, int64_t, int64_t, const double*, int, int, double*,
+                           const int32_t*, int, const int32_t*);
+struct LdsInstance {
+    LdsKernel fn;
+    int mode, rw, padk, split, form;
+};
+template <int LPE, int MODE, int RW, int PADK, int SPLIT, int FORM = 0>
+static LdsInstance lds_instance() {
+    return LdsInstance{vrx_spmm_lds<LPE, MODE, RW, PADK, SPLIT, FORM>, MODE, RW, PADK, SPLIT, FORM};
+}
+
 // kernel instance for K: zero-padded rows when K % 4, 2 / 4 entries at once when K <= 8 / 4
 template <int LPE, int MODE, int RW>
-static auto lds_kernel_rw(int K, bool strided) {
+static LdsInstance lds_kernel_rw(int K, bool strided) {
     const int split = K <= 4 ? 4 : K <= 8 ? 2 : 1;
     // (the element-wise slab copy handles row strides and rows that do not fill whole lanes)
     const bool pad = K % (16 / LPE) != 0 || strided;
-    if (split == 4) return pad ? vrx_spmm_lds<LPE, MODE, RW, 1, 4> : vrx_spmm_lds<LPE, MODE, RW, 0, 4>;
-    if (split == 2) return pad ? vrx_spmm_lds<LPE, MODE, RW, 1, 2> : vrx_spmm_lds<LPE, MODE, RW, 0, 2>;
-    return pad ? vrx_spmm_lds<LPE, MODE, RW, 1, 1> : vrx_spmm_lds<LPE, MODE, RW, 0, 1>;
+    if (split == 4) return pad ? lds_instance<LPE, MODE, RW, 1, 4>() : lds_instance<LPE, MODE, RW, 0, 4>();
+    if (split == 2) return pad ? lds_instance<LPE, MODE, RW, 1, 2>() : lds_instance<LPE, MODE, RW, 0, 2>();
+    return pad ? lds_instance<LPE, MODE, RW, 1, 1>() : lds_instance<LPE, MODE, RW, 0, 1>();
 }
 
 // the AD/BD form of the cell pass (FORM 1): one instance for K = 16, one that stages
 // element-wise and masks its stores for every other K / column block
 // (pad: 0 flat rows of 16 columns, 1 element-wise, 2 whole 16-B units -- see the kernel)
 template <int RW>
-static auto lds_kernel_form1(int pad) {
-    return pad == 0   ? vrx_spmm_lds<VRX_LDS_LPE, 1, RW, 0, 1, 1>
-           : pad == 1 ? vrx_spmm_lds<VRX_LDS_LPE, 1, RW, 1, 1, 1>
-                      : vrx_spmm_lds<VRX_LDS_LPE, 1, RW, 2, 1, 1>;
+static LdsInstance lds_kernel_form1(int pad) {
+    if (pad == 1) return lds_instance<VRX_LDS_LPE, 1, RW, 1, 1, 1>();
+    if (pad == 2) return lds_instance<VRX_LDS_LPE, 1, RW, 2, 1, 1>();
+    return lds_instance<VRX_LDS_LPE, 1, RW, 0, 1, 1>();
 }
 
 // rows per wave: the pass default, or (cell pass) the shorter tile of short_tile_pays()
 template <int LPE, int MODE>
-static auto lds_kernel(int K, int ld, bool strided, int rw, int form) {
+static LdsInstance lds_kernel(int K, int ld, bool strided, int rw, int form) {
     // AD/BD forms: flat rows, or whole 16-B units (even K and row stride), or element-wise
     const int pad = K == 16 && !strided ? 0 : ((K | ld) & 1) == 0 ? 2 : 1;
     // (the caller has checked rw against the heights compiled for this mode and form: lds_rw_ok)
@@ -2535,8 +2559,9 @@ static bool lds_rw_ok(int rw, int form) {
 
 template <int LPE, int MODE>
 static int launch_lds_one(const Orient& o, hipStream_t s, const double* X, int K, double* dst,
-                          const int32_t* ctl, int R) {
+                          const int32_t* ctl, int R, std::vector<LdsLaunch>& log) {
     const TiledStream& t = o.tiled;
+    log.clear();  // (the record of this orientation's last pass)
     VRX_REQUIRE(lds_rw_ok<MODE>(t.rw, t.form),
                 "LDS pass: no kernel instance for %d rows per wave (mode %d, form %d)", t.rw, MODE, t.form);
     constexpr int XD = MODE == 1 ? 2 : 1, NV = MODE == 0 ? 2 : 1;
@@ -2549,9 +2574,12 @@ static int launch_lds_one(const Orient& o, hipStream_t s, const double* X, int K
         constexpr int CPL = 16 / LPE;  // columns per lane: LDS rows hold whole lanes
         const size_t lds = (size_t)t.slab_rows * (f1 ? 256 : (kb + CPL - 1) / CPL * CPL * (MODE == 1 ? 16 : 8)) +
                            VRX_LDS_WAVES * VRX_RING * 4;
-        auto kern = lds_kernel<LPE, MODE>(kb, K, K > 16, t.rw, t.form);
+        const LdsInstance inst = lds_kernel<LPE, MODE>(kb, K, K > 16, t.rw, t.form);
+        const LdsKernel kern = inst.fn;
         VRX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        log.push_back(LdsLaunch{inst.mode, inst.rw, inst.padk, inst.split, inst.form, kb, K, t.perm.p != nullptr,
+                                t.slab_rows, t.n_slab});
         kern<<<grid, VRX_LDS_WAVES * 64, lds, s>>>(t.ent.p, t.wave_start.p, t.bnd.p, t.rowmap.p, t.items.p,
                                      t.wg_first.p, t.n_slab,
                                      t.slab_rows, t.n_contract, t.n_vrows,
@@ -2572,11 +2600,11 @@ static int launch_spmm_lds(vrx_model* m, const Orient& o, const double* X, int K
         // virtual rows: the cell pass's kernel over (variant, AD) / (variant, BD) rows and the
         // operand as double rows; planar partial sums [slot][virtual piece][K], turned into
         // S = (S1, S1 + S2) by take_S or by its consumer (vrx_theta_partial)
-        return launch_lds_one<VRX_LDS_LPE, 1>(o, s, X, K, range_partial, m->ctl.p, m->R);
+        return launch_lds_one<VRX_LDS_LPE, 1>(o, s, X, K, range_partial, m->ctl.p, m->R, m->lds_log[MODE]);
     }
     double* dst = t.n_range == 1 && !t.split ? out : range_partial;
     int rc;
-    rc = launch_lds_one<VRX_LDS_LPE, MODE>(o, s, X, K, dst, m->ctl.p, m->R);  // K < 16 leaves lanes idle
+    rc = launch_lds_one<VRX_LDS_LPE, MODE>(o, s, X, K, dst, m->ctl.p, m->R, m->lds_log[MODE]);  // K < 16 leaves lanes idle
     if (rc) return rc;
     if (t.split && !(MODE == 1 && defer_sum)) {  // rows cut into pieces: sum pieces and ranges in one fixed order
         // (the cell pass's consumer, vrx_cell_softmax, sums the pieces itself when asked to: defer_sum)
@@ -3224,6 +3252,18 @@ extern "C" int vrx_model_info(vrx_model* m, int32_t* info) {
     const int32_t iv = v.tiled.ready ? (int32_t)std::min(65535.0, v.tiled.imbalance * 1000.0 + 0.5) : 0;
     const int32_t ic = c.tiled.ready ? (int32_t)std::min(32767.0, c.tiled.imbalance * 1000.0 + 0.5) : 0;
     info[15] = iv | (ic << 16);
+    return VRX_OK;
+}
+
+extern "C" int vrx_model_lds_launches(vrx_model* m, int32_t orient, int32_t* out, int32_t cap, int32_t* n_out) {
+    VRX_REQUIRE(m && n_out && (out || cap == 0), "vrx_model_lds_launches: null argument");
+    VRX_REQUIRE((orient == 0 || orient == 1) && cap >= 0, "vrx_model_lds_launches: orientation %d, room for %d",
+                orient, cap);
+    const std::vector<LdsLaunch>& log = m->lds_log[orient];
+    static_assert(sizeof(LdsLaunch) == VRX_LDS_LAUNCH_FIELDS * sizeof(int32_t), "a record is its fields");
+    const size_t n = std::min(log.size(), (size_t)cap);
+    if (n) memcpy(out, log.data(), n * sizeof(LdsLaunch));
+    *n_out = (int32_t)log.size();
     return VRX_OK;
 }
 

@@ -3,12 +3,16 @@
 Everything numeric happens in libvireo_hip.so; this class only moves the reference's
 NumPy attributes across the C ABI.
 """
+import collections
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 from ._lib import dptr, f64
+
+# one column-block launch of an LDS-resident pass (include/vireo_hip.h, vrx_model_lds_launches)
+LdsLaunch = collections.namedtuple("LdsLaunch", "mode rw padk split form kb ld perm slab_rows n_slab")
 
 
 def _prior_rows(P, full_rows):
@@ -173,6 +177,21 @@ class DeviceModel(_lib.Handle):
                     cell_form=int(a[12]), var_form=int(a[13]), n_batch=int(a[14]),
                     imbalance_variant=(int(a[15]) & 0xffff) / 1000.0,
                     imbalance_cell=(int(a[15]) >> 16) / 1000.0)
+
+    def lds_launches(self):
+        """(variant pass, cell pass): the ``vrx_spmm_lds`` instances the last LDS-resident pass of each
+        orientation launched, one ``LdsLaunch`` per column block (vrx_model_lds_launches); empty for
+        a pass that has not run there"""
+        L, i32 = _lib.lib(), C.POINTER(C.c_int32)
+        out = []
+        for orient in (0, 1):
+            n = C.c_int32(0)
+            _lib.check(L.vrx_model_lds_launches(self._h, orient, None, 0, C.byref(n)))
+            a = np.zeros((n.value, len(LdsLaunch._fields)), dtype=np.int32)
+            _lib.check(L.vrx_model_lds_launches(self._h, orient, a.ctypes.data_as(i32), n.value, C.byref(n)))
+            out.append([LdsLaunch(*(int(v) for v in row[:7]), bool(row[7]), int(row[8]), int(row[9]))
+                        for row in a])
+        return tuple(out)
 
     # ---- timing -----------------------------------------------------------------------
     def profile(self, enable=True):
