@@ -541,6 +541,39 @@ int vrx_cellvcf_slab(vrx_cellvcf* h, const char* text, int64_t n_bytes, int64_t*
 int vrx_cellvcf_rows(vrx_cellvcf* h, int64_t* indptr, int32_t* cell, int32_t* v0, int32_t* v1, int32_t* flag,
                      int64_t* span /* [rows][2] */, int32_t* off /* [rows][10] */, double* seconds /* 1 */);
 
+/* ---- BGZF inflation (vrx_bgzf.h) ---------------------------------------------------------------------
+ * A BGZF file (bgzip, cellSNP) is a chain of gzip members of at most 64 KiB of text each; a member's
+ * header holds its compressed size, its footer the CRC32 and the length of its text.  The members are
+ * independent: one wavefront inflates one member into LDS, holds it to the footer and writes it out.
+ * vrx_bgzf_scan (host only): the members of the file image file[0, n_bytes).  Every member must begin
+ * with the 18 bytes bgzip / htslib write (1f 8b 08 04, XLEN 6, subfield BC of length 2), and the chain of
+ * their sizes must end exactly at n_bytes.  Returns VRX_OK and *status = 0, or *status = 1 a member with
+ * another header (plain gzip, other flags, further subfields, trailing bytes), 2 a member cut short, 3 a
+ * size the format does not allow.  *n_members = the whole members (in front of the fault); the first
+ * `room` of them are stored (room = 0: counting only, the arrays may be NULL): payload_off / payload_len
+ * = the deflate stream of each, isize = its footer's text length, out_off (room + 1 places) = the sum of
+ * isize in front of it, the total at [*n_members].  A file without the empty end-of-file member is fine.
+ * vrx_bgzf_create: max_text = the text bytes of one vrx_bgzf_inflate call (64 KiB ... 1 GiB; 0 = 256 MiB).
+ * vrx_bgzf_inflate: a batch of n_members >= 1 members out of the n_comp < 2^31 compressed bytes at comp:
+ * payload_off / payload_len as vrx_bgzf_scan gives them, relative to comp (each footer, the 8 bytes behind
+ * the payload, lies inside comp); out_off (n_members + 1, non-decreasing from 0, steps of at most 64 KiB,
+ * the last at most max_text) = where each member's text goes in text.  Both directions go through a
+ * pinned buffer the handle owns.  status[i] = 0, or the bits of what the device could not vouch for in
+ * member i (VRX_BGZF_ST_* in vrx_bgzf.h: 1 stream longer than the payload, 2 block type 3, 4 stored
+ * LEN / NLEN, 8 code-length header, 16 over-subscribed, 32 incomplete, 64 no end-of-block code, 128 an
+ * invalid symbol, 256 a distance before the first byte, 512 a write beyond ISIZE, 1024 fewer bytes than
+ * ISIZE, 2048 payload bytes left over, 4096 CRC32, 8192 iteration cap, 16384 ISIZE is not the step of
+ * out_off); the text of such a member is undefined, the other members are not affected.  seconds (may be
+ * NULL): upload, kernels, download. */
+typedef struct vrx_bgzf vrx_bgzf;
+int vrx_bgzf_scan(const uint8_t* file, int64_t n_bytes, int64_t room, int64_t* n_members, int64_t* payload_off,
+                  int32_t* payload_len, int32_t* isize, int64_t* out_off, int32_t* status);
+int vrx_bgzf_create(int device, int64_t max_text, vrx_bgzf** out);
+void vrx_bgzf_destroy(vrx_bgzf* h);
+int vrx_bgzf_inflate(vrx_bgzf* h, const uint8_t* comp, int64_t n_comp, int64_t n_members, const int64_t* payload_off,
+                     const int32_t* payload_len, const int64_t* out_off, uint8_t* text, int32_t* status,
+                     double* seconds /* 3 */);
+
 /* ---- timing (bench.py roofline leg) ---------------------------------------------------
  * When enabled, every launch of a pass kernel is bracketed by hipEvents on the model's
  * stream; totals are read back after a sync.  Kernel ids: */

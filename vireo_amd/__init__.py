@@ -8,6 +8,7 @@ fallback and no PyTorch in the compute path.
 """
 __version__ = "0.2.0"
 
+from . import bgzf
 from . import vcf_utils as vcf
 from . import vireo_base as base
 from . import vireo_model as model
@@ -50,4 +51,4 @@ __all__ = ["__version__", "Vireo", "BinomMixtureVB", "vireo_wrap", "predict_doub
            "read_cellVCF", "read_vartrix", "normalize", "tensor_normalize", "loglik_amplify", "get_binom_coeff",
            "binom_coeff_sum", "beta_entropy", "match", "optimal_match", "donor_select",
            "genotype_distance", "donor_match", "match_VCF_samples", "snp_gene_match", "gene_counts",
-           "get_confusion", "vcf", "base", "model"] + list(_POOL)
+           "get_confusion", "vcf", "base", "model", "bgzf"] + list(_POOL)

@@ -35,6 +35,7 @@ _P = C.c_void_p
 _D = C.POINTER(C.c_double)
 _I32 = C.POINTER(C.c_int32)
 _I64 = C.POINTER(C.c_int64)
+_U8 = C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes); exactly the declarations of include/vireo_hip.h
 SIGNATURES = {
@@ -132,6 +133,10 @@ SIGNATURES = {
     "vrx_cellvcf_format": (C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32]),
     "vrx_cellvcf_slab": (C.c_int, [_P, C.c_char_p, C.c_int64, _I64, _D]),
     "vrx_cellvcf_rows": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I64, _I32, _D]),
+    "vrx_bgzf_scan": (C.c_int, [_U8, C.c_int64, C.c_int64, _I64, _I64, _I32, _I32, _I64, _I32]),
+    "vrx_bgzf_create": (C.c_int, [C.c_int, C.c_int64, C.POINTER(_P)]),
+    "vrx_bgzf_destroy": (None, [_P]),
+    "vrx_bgzf_inflate": (C.c_int, [_P, _U8, C.c_int64, C.c_int64, _I64, _I32, _I64, _U8, _I32, _D]),
     "vrx_model_info": (C.c_int, [_P, _I32]),
     "vrx_model_lds_launches": (C.c_int, [_P, C.c_int32, _I32, C.c_int32, _I32]),
     "vrx_model_profile": (C.c_int, [_P, C.c_int32]),

@@ -1,5 +1,6 @@
 // VCF text on the device: the vrx_vcf_* entries of include/vireo_hip.h on the kernels of vrx_vcf.h (donor VCFs) and
-// the vrx_cellvcf_* entries on those of vrx_cellvcf.h (cell VCFs).
+// the vrx_cellvcf_* entries on those of vrx_cellvcf.h (cell VCFs); in front of both, the vrx_bgzf_* entries inflate the
+// file's BGZF members with the decoder of vrx_bgzf.h.
 // A handle owns its stream and buffers; nothing here touches a vrx_problem or a vrx_model.
 #include <algorithm>
 #include <chrono>
@@ -7,6 +8,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "vrx_handle.h"
+#include "vrx_bgzf.h"
 #include "vrx_cellvcf.h"
 #include "vrx_vcf.h"
 
@@ -507,5 +509,153 @@ extern "C" int vrx_cellvcf_rows(vrx_cellvcf* h, int64_t* indptr, int32_t* cell, 
     }
     VRX_HIP(hipStreamSynchronize(s));
     if (seconds) seconds[0] = seconds_since(t0);
+    return VRX_OK;
+}
+
+// ---- BGZF inflation: the vrx_bgzf_* entries on the decoder of vrx_bgzf.h -----------------------------------------
+namespace {
+constexpr int64_t kBgzfTextDefault = (int64_t)256 << 20, kBgzfTextMax = (int64_t)1 << 30;
+
+// One wavefront, one workgroup, one member; the working memory of vrx_bgzf.h is the launch's dynamic LDS.
+__global__ __launch_bounds__(VRX_BGZF_LANES) void vrx_bgzf_members(const uint8_t* __restrict__ comp,
+                                                                   const uint32_t* __restrict__ payload_off,
+                                                                   const uint32_t* __restrict__ payload_len,
+                                                                   const uint32_t* __restrict__ out_off, uint32_t n_members,
+                                                                   const VrxBgzfCrc* __restrict__ crc,
+                                                                   uint8_t* __restrict__ text, int32_t* __restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t vrx_bgzf_lds[];
+    VrxBgzfWork& w = *reinterpret_cast<VrxBgzfWork*>(vrx_bgzf_lds);
+    const uint32_t m = blockIdx.x, lane = threadIdx.x;
+    if (m >= n_members) return;
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(crc);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&w.crc);
+        for (uint32_t i = lane; i < sizeof(VrxBgzfCrc) / sizeof(uint32_t); i += VRX_BGZF_LANES) dst[i] = src[i];
+    }
+    __syncthreads();
+    const uint8_t* payload = comp + payload_off[m];
+    const uint32_t n = payload_len[m], room = out_off[m + 1] - out_off[m];
+    const uint32_t want_crc = vrx_bgzf_le32(payload + n), isize = vrx_bgzf_le32(payload + n + 4);
+    uint32_t st = VRX_BGZF_ST_ISIZE;
+    if (isize == room) st = vrx_bgzf_member(w, payload, n, isize, want_crc, w.window);
+    if (st == 0) {
+        uint8_t* dst = text + out_off[m];
+        for (uint32_t i = lane; i < isize; i += VRX_BGZF_LANES) dst[i] = w.window[i];
+    }
+    if (lane == 0) status[m] = (int32_t)st;
+}
+
+struct PinnedBytes {
+    uint8_t* p = nullptr;
+    size_t n = 0;
+    PinnedBytes() = default;
+    PinnedBytes(const PinnedBytes&) = delete;
+    PinnedBytes& operator=(const PinnedBytes&) = delete;
+    ~PinnedBytes() {
+        if (p) (void)hipHostFree(p);
+    }
+    hipError_t reserve(size_t count) {
+        if (n >= count) return hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), count + count / 8, hipHostMallocDefault);
+        if (e == hipSuccess) n = count + count / 8;
+        return e;
+    }
+};
+}  // namespace
+
+struct vrx_bgzf : VrxQueue {
+    int64_t max_text = 0;
+    PinnedBytes pin;  // the compressed bytes on their way up, then the text on its way down
+    DevBuf<uint8_t> comp, text;
+    DevBuf<uint32_t> meta;  // payload_off, payload_len (n each), out_off (n + 1)
+    DevBuf<int32_t> status;
+    DevBuf<VrxBgzfCrc> crc;
+};
+
+extern "C" int vrx_bgzf_scan(const uint8_t* file, int64_t n_bytes, int64_t room, int64_t* n_members, int64_t* payload_off,
+                             int32_t* payload_len, int32_t* isize, int64_t* out_off, int32_t* status) {
+    VRX_REQUIRE(n_members && status, "vrx_bgzf_scan: null argument");
+    VRX_REQUIRE(n_bytes >= 0 && (n_bytes == 0 || file), "vrx_bgzf_scan: null file");
+    VRX_REQUIRE(room >= 0 && (room == 0 || (payload_off && payload_len && isize && out_off)), "vrx_bgzf_scan: null output");
+    *status = vrx_bgzf_scan_image(file, n_bytes, room, n_members, payload_off, payload_len, isize, out_off);
+    return VRX_OK;
+}
+
+extern "C" void vrx_bgzf_destroy(vrx_bgzf* h) { vrx_destroy(h); }
+
+extern "C" int vrx_bgzf_create(int device, int64_t max_text, vrx_bgzf** out) {
+    VRX_REQUIRE(out, "vrx_bgzf_create: null argument");
+    if (max_text == 0) max_text = kBgzfTextDefault;
+    VRX_REQUIRE(max_text >= VRX_BGZF_TEXT_MAX && max_text <= kBgzfTextMax, "vrx_bgzf_create: max_text is 64 KiB ... 1 GiB");
+    VrxOwned<vrx_bgzf> h(new vrx_bgzf());
+    VRX_TRY(h->open("vrx_bgzf_create", device, 0));
+    h->max_text = max_text;
+    VrxBgzfCrc tables;
+    vrx_bgzf_crc_init(tables);
+    VRX_HIP(h->crc.upload(&tables, 1, h->stream));
+    VRX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(vrx_bgzf_members), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)sizeof(VrxBgzfWork)));
+    VRX_HIP(hipStreamSynchronize(h->stream));  // (the tables die at return)
+    *out = h.release();
+    return VRX_OK;
+}
+
+extern "C" int vrx_bgzf_inflate(vrx_bgzf* h, const uint8_t* comp, int64_t n_comp, int64_t n_members,
+                                const int64_t* payload_off, const int32_t* payload_len, const int64_t* out_off, uint8_t* text,
+                                int32_t* status, double* seconds) {
+    VRX_REQUIRE(h && comp && payload_off && payload_len && out_off && status, "vrx_bgzf_inflate: null argument");
+    VRX_REQUIRE(n_members >= 1 && n_members < ((int64_t)1 << 31) - 1, "vrx_bgzf_inflate: 1 <= n_members < 2^31 - 1");
+    VRX_REQUIRE(n_comp >= 1 && n_comp < ((int64_t)1 << 31), "vrx_bgzf_inflate: 1 <= n_comp < 2^31");
+    VRX_REQUIRE(out_off[0] == 0, "vrx_bgzf_inflate: out_off starts at 0");
+    for (int64_t i = 0; i < n_members; ++i) {
+        VRX_REQUIRE(payload_len[i] >= 0 && payload_off[i] >= 0 &&
+                        payload_off[i] <= n_comp - VRX_BGZF_FOOTER - (int64_t)payload_len[i],
+                    "vrx_bgzf_inflate: member %lld lies outside the compressed bytes", (long long)i);
+        VRX_REQUIRE(out_off[i + 1] >= out_off[i] && out_off[i + 1] - out_off[i] <= VRX_BGZF_TEXT_MAX,
+                    "vrx_bgzf_inflate: member %lld has 0 ... 65536 bytes of text", (long long)i);
+    }
+    const int64_t n_text = out_off[n_members];
+    VRX_REQUIRE(n_text <= h->max_text, "vrx_bgzf_inflate: %lld bytes of text in a batch of at most %lld", (long long)n_text,
+                (long long)h->max_text);
+    VRX_REQUIRE(n_text == 0 || text, "vrx_bgzf_inflate: null text");
+    if (seconds) seconds[0] = seconds[1] = seconds[2] = 0.0;
+    VRX_TRY(h->use());
+    hipStream_t s = h->stream;
+    const size_t M = (size_t)n_members, meta_bytes = (3 * M + 1) * sizeof(uint32_t);
+    // upload: the members and where they lie, through the pinned buffer
+    auto t0 = std::chrono::steady_clock::now();
+    VRX_HIP(h->pin.reserve(std::max((size_t)n_comp + meta_bytes, (size_t)n_text)));
+    VRX_HIP(vrx_reserve(h->comp, (size_t)n_comp));
+    VRX_HIP(vrx_reserve(h->meta, 3 * M + 1));
+    VRX_HIP(vrx_reserve(h->status, M));
+    VRX_HIP(vrx_reserve(h->text, std::max<size_t>((size_t)n_text, 1)));
+    uint32_t* meta = reinterpret_cast<uint32_t*>(h->pin.p);
+    for (size_t i = 0; i < M; ++i) {
+        meta[i] = (uint32_t)payload_off[i];
+        meta[M + i] = (uint32_t)payload_len[i];
+        meta[2 * M + i] = (uint32_t)out_off[i];
+    }
+    meta[3 * M] = (uint32_t)n_text;
+    std::copy(comp, comp + n_comp, h->pin.p + meta_bytes);
+    VRX_HIP(hipMemcpyAsync(h->meta.p, meta, meta_bytes, hipMemcpyHostToDevice, s));
+    VRX_HIP(hipMemcpyAsync(h->comp.p, h->pin.p + meta_bytes, (size_t)n_comp, hipMemcpyHostToDevice, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    if (seconds) seconds[0] = seconds_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    vrx_bgzf_members<<<(unsigned)M, VRX_BGZF_LANES, sizeof(VrxBgzfWork), s>>>(h->comp.p, h->meta.p, h->meta.p + M,
+                                                                              h->meta.p + 2 * M, (uint32_t)M, h->crc.p,
+                                                                              h->text.p, h->status.p);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(hipStreamSynchronize(s));
+    if (seconds) seconds[1] = seconds_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    VRX_HIP(hipMemcpyAsync(status, h->status.p, M * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (n_text > 0) VRX_HIP(hipMemcpyAsync(h->pin.p, h->text.p, (size_t)n_text, hipMemcpyDeviceToHost, s));
+    VRX_HIP(hipStreamSynchronize(s));
+    if (n_text > 0) std::copy(h->pin.p, h->pin.p + n_text, text);
+    if (seconds) seconds[2] = seconds_since(t0);
     return VRX_OK;
 }

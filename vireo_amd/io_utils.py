@@ -18,6 +18,7 @@ import numpy as np
 from scipy.sparse import coo_matrix, csc_matrix, csr_matrix
 
 from . import _lib
+from .bgzf import BgzfStatus
 from .vcf_utils import (_DonorText, _SLAB_BYTES, _SLAB_LIMIT, _VCF_STATUS, _labels_blob, _sparse_geno, load_VCF,
                         match_SNPs, read_sparse_GeneINFO)
 
@@ -163,10 +164,10 @@ def read_cellVCF(vcf_file, biallelic_only=True, keys=('AD', 'DP'), axes=(-1, -1)
     (vcf_utils.py:80-159, parse_sample_info :12-57) and ``read_sparse_GeneINFO`` (:192-205): one float64 CSR matrix
     (variants x cells) per name in ``keys``, samples, variants, FixedINFO, contigs, comments and n_SNP_tagged, with the
     same index dtypes, explicit zeros and entry order, from one pass over the text on the GPU (``vrx_cellvcf_*``,
-    csrc/vrx_cellvcf.h).  The host inflates the file and feeds it in slabs of whole lines (``slab_bytes``, default
-    256 MiB); the device finds the lines, the filter, the entries among the sample fields, their cells and the two
-    values; lines with a value outside its grammar ('.' or 1-9 digits after the last comma) come back flagged and
-    their values are parsed here by the host functions; variants and FixedINFO are sliced from the text at the
+    csrc/vrx_cellvcf.h).  The file is inflated on the device when it is BGZF (``vireo_amd.bgzf``; by Python's gzip
+    otherwise, or with VIREO_INFLATE=host) and fed in slabs of whole lines (``slab_bytes``, default 256 MiB); the
+    device finds the lines, the filter, the entries among the sample fields, their cells and the two values; lines
+    with a value outside its grammar ('.' or 1-9 digits after the last comma) come back flagged and their values are parsed here by the host functions; variants and FixedINFO are sliced from the text at the
     offsets the device returns.  Also returned: path 'device' | 'host', reason, n_lines (kept lines), n_repaired,
     seconds dict(inflate, upload, kernels, download, host).  The host path, the composition above, is taken with
     ``force_host`` or VIREO_CELL_VCF=host, for keys / axes other than two keys with axis -1, and for files whose
@@ -190,8 +191,9 @@ def read_cellVCF(vcf_file, biallelic_only=True, keys=('AD', 'DP'), axes=(-1, -1)
         raise ValueError("slab_bytes must lie in 1 ... %d" % _SLAB_LIMIT)
     t_all = time.perf_counter()
     sec = dict(inflate=0.0, upload=0.0, kernels=0.0, download=0.0, host=0.0)
-    text = _DonorText(vcf_file, sec)
+    text = None
     try:
+        text = _DonorText(vcf_file, sec, device)
         head = text.header()
         for raw in head:                                          # the '#' lines as load_VCF's text layer sees them
             core = raw[:-2] if raw.endswith(b"\r\n") else raw.rstrip(b"\n")
@@ -270,8 +272,11 @@ def read_cellVCF(vcf_file, biallelic_only=True, keys=('AD', 'DP'), axes=(-1, -1)
                 p_v0.append(v0)
                 p_v1.append(v1)
                 n_entries += E
+    except BgzfStatus as e:                                           # the whole file on the host: gzip raises its own
+        return host("BGZF " + e.reason)
     finally:
-        text.close()
+        if text is not None:
+            text.close()
 
     n_var = len(variants)
     if n_var == 0:

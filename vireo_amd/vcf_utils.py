@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 from scipy.sparse import csr_matrix
 
-from . import _lib
+from . import _lib, bgzf
 from .gene_match import snp_gene_match                         # noqa: F401  (vcf_utils.py:423-491)
 from .vireo_base import donor_match, match
 
@@ -281,10 +281,23 @@ def _donor_host(vcf_file, tag, variants, biallelic_only, min_prob, reason):
 
 
 class _DonorText:
-    """The decompressed bytes of a VCF: the '#' lines at its head, then slabs of whole lines."""
+    """The decompressed bytes of a VCF: the '#' lines at its head, then slabs of whole lines.  A BGZF file is
+    inflated on ``device`` unless VIREO_INFLATE=host (bgzf.BgzfReader, which raises bgzf.BgzfStatus for a file
+    the device does not vouch for), every other compressed file by gzip; bgzf.last() records which."""
 
-    def __init__(self, path, seconds):
-        self.fh = gzip.open(path, "rb") if path.endswith((".gz", ".bgz")) else open(path, "rb")
+    def __init__(self, path, seconds, device=None):
+        t0 = time.perf_counter()
+        if not path.endswith((".gz", ".bgz")):
+            self.fh = open(path, "rb")
+        elif bgzf.wanted() == "host":
+            bgzf.note_host(path, "VIREO_INFLATE=host")
+            self.fh = gzip.open(path, "rb")
+        elif not bgzf.is_bgzf(path):
+            bgzf.note_host(path, "not a BGZF file")
+            self.fh = gzip.open(path, "rb")
+        else:
+            self.fh = bgzf.BgzfReader(path, device)
+        seconds['inflate'] += time.perf_counter() - t0
         self.seconds = seconds
         self.buf, self.pos, self.eof = bytearray(), 0, False
 
@@ -347,8 +360,9 @@ def load_donor_GPb(vcf_file, tag='GT', variants=None, biallelic_only=True, min_p
     "CHROM_POS_REF_ALT" ids), in the order of ``variants``: what ``load_VCF(sparse=False, format_list=[tag])``
     (vcf_utils.py:80-159), ``match_donor_VCF`` (io_utils.py:10-39; ``match_SNPs`` with its "chr" retries, :339-350)
     and ``parse_donor_GPb`` (:299-336) give together, bit for bit, from one pass over the text on the GPU
-    (``vrx_vcf_*``).  ``variants=None``: every kept line in file order.  The host inflates the file and feeds it in
-    slabs of whole lines (``slab_bytes``, default 256 MiB); the device finds the lines, ids, filter, tag counts,
+    (``vrx_vcf_*``).  ``variants=None``: every kept line in file order.  The file is inflated on the device when it is
+    BGZF (``vireo_amd.bgzf``; by Python's gzip otherwise, or with VIREO_INFLATE=host) and fed in slabs of whole lines
+    (``slab_bytes``, default 256 MiB); the device finds the lines, ids, filter, tag counts,
     matches and the unnormalised values of the codes; rows outside its grammar come back flagged and are parsed
     here by the host functions; ``P += min_prob; P /= P.sum(2)`` is NumPy's.  Returns dict(GPb (n_rows, n_sample,
     3), samples, keep (indices into variants), line (ordinal among the kept lines), n_lines, n_tagged, n_repaired,
@@ -372,8 +386,9 @@ def load_donor_GPb(vcf_file, tag='GT', variants=None, biallelic_only=True, min_p
     def host(reason):
         return _donor_host(vcf_file, tag, variants, biallelic_only, min_prob, reason)
 
-    text = _DonorText(vcf_file, sec)
+    text = None
     try:
+        text = _DonorText(vcf_file, sec, device)
         head = text.header()
         chrom = [x for x in head if x.startswith(b"#CHROM")]
         if any(max(x) >= 0x80 for x in chrom) or any(b"\r" in x.rstrip(b"\r\n") for x in head):
@@ -399,7 +414,7 @@ def load_donor_GPb(vcf_file, tag='GT', variants=None, biallelic_only=True, min_p
             status = C.c_int32(0)
             for mode in ((-1,) if variants is None else (0, 1, 2)):
                 if text is None:                                      # a "chr" retry of match_SNPs: the file once more
-                    text = _DonorText(vcf_file, sec)
+                    text = _DonorText(vcf_file, sec, device)
                     text.header()
                 _lib.check(L.vrx_vcf_begin(reader.ptr, mode, C.byref(status)))
                 if status.value:
@@ -436,6 +451,8 @@ def load_donor_GPb(vcf_file, tag='GT', variants=None, biallelic_only=True, min_p
                 text = None
                 if parts or variants is None:
                     break
+    except bgzf.BgzfStatus as e:                                      # the whole file on the host: gzip raises its own
+        return host("BGZF " + e.reason)
     finally:
         if text is not None:
             text.close()
