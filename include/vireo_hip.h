@@ -705,6 +705,17 @@ int vrx_write_vcf_records(const char* path, const char* head, const char* prefix
                           const int64_t* ad, const int64_t* dp, const int64_t* pl /* [..][3] */,
                           int64_t n_var, int64_t n_sample, int32_t gz);
 
+/* ---- the stop rule of the fit loops (csrc/vrx_stop.h), test infrastructure ---------------------
+ * Every fit loop of the library judges its iterations with vrx_stop_judge, in the form of its
+ * reference loop (vireo_model.py:266-274, bmm_model.py:190-199, vireo_bulk.py:97-105 =
+ * vireo_doublet.py:173-181).  vrx_stop_verdicts runs the device compile of that judge on n rows,
+ * one lane per row: rows_i [n][4] = (form, it, min_iter, max_iter), rows_d [n][3] = (eps,
+ * X[it - 1] as the trace holds it, X[it]); verdict [n] = 0 continue, 1 warn "decreased",
+ * 2 warn "did not converge", 3 stop; prev [n] = the value X[it - 1] was taken to have (it = 0:
+ * 0, or X[it] when max_iter = 1, like Python's X[-1] of np.zeros(max_iter)). */
+int vrx_stop_verdicts(int device, int64_t n, const int32_t* rows_i, const double* rows_d,
+                      int32_t* verdict, double* prev);
+
 #ifdef __cplusplus
 }
 #endif

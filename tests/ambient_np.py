@@ -23,10 +23,11 @@ def theta_of(GT_prob, beta_mu):
     return np.tensordot(GT_prob, beta_mu[0, :], axes=(2, 0))
 
 
-def fit_cell(a, b, th, psi0, min_iter=20, max_iter=200, eps=1e-3, dtype=float):
+def fit_cell(a, b, th, psi0, min_iter=20, max_iter=200, eps=1e-3, dtype=float, trace=None):
     """one cell: a, b (n_e,) counts of its selected entries, th (n_e, K) their theta rows.
     -> psi, var, llr, it (the loop index at exit, as in the reference).  ``dtype=np.longdouble``
-    runs the same statements in extended precision (is a cell's exit decided by rounding?)"""
+    runs the same statements in extended precision (is a cell's exit decided by rounding?).  ``trace``: a list
+    that receives logLik[0 .. it], which the reference does not return."""
     a = np.asarray(a, dtype)
     b = np.asarray(b, dtype)
     th = np.asarray(th, dtype)
@@ -50,6 +51,8 @@ def fit_cell(a, b, th, psi0, min_iter=20, max_iter=200, eps=1e-3, dtype=float):
                 pass
             elif ll[it] - ll[it - 1] < eps:
                 break
+    if trace is not None:
+        trace.extend(ll[:it + 1])
     tv = th @ psi
     var = 1.0 / ((th / tv[:, None]) ** 2 * a[:, None] + (th / (1 - tv[:, None])) ** 2 * b[:, None]).sum(0)
     tm = th[:, int(np.argmax(psi))]

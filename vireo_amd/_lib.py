@@ -137,6 +137,7 @@ SIGNATURES = {
     "vrx_bgzf_create": (C.c_int, [C.c_int, C.c_int64, C.POINTER(_P)]),
     "vrx_bgzf_destroy": (None, [_P]),
     "vrx_bgzf_inflate": (C.c_int, [_P, _U8, C.c_int64, C.c_int64, _I64, _I32, _I64, _U8, _I32, _D]),
+    "vrx_stop_verdicts": (C.c_int, [C.c_int, C.c_int64, _I32, _D, _I32, _D]),
     "vrx_model_info": (C.c_int, [_P, _I32]),
     "vrx_model_lds_launches": (C.c_int, [_P, C.c_int32, _I32, C.c_int32, _I32]),
     "vrx_model_profile": (C.c_int, [_P, C.c_int32]),

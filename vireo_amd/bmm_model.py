@@ -7,7 +7,7 @@ import numpy as np
 from . import _lib
 from .counts import device_counts
 from .dist import LocalComm, first_record, gather_restart_elbos, my_restarts
-from .engine import DeviceBatch, DeviceModel
+from .engine import DeviceBatch, DeviceModel, trace_prev
 from .restarts import LegacyStream, restart_batch
 from .vireo_base import normalize
 
@@ -158,9 +158,12 @@ class BinomMixtureVB():
     @staticmethod
     def _warn(trace, it, min_iter, max_iter):
         """the reference's prints (bmm_model.py:192-197)"""
-        for i in range(min_iter + 1, it + 1):
-            if trace[i] - trace[i - 1] < -1e-6:
-                print("Warning: ELBO decreases %.8f to %.8f!\n" % (trace[i - 1], trace[i]))
+        for i in range(max(min_iter + 1, 0), it + 1):          # (it > min_iter, from it = 0 on)
+            prev = trace_prev(trace, i, max_iter)
+            with np.errstate(invalid="ignore"):                # (inf - inf: not a decrease)
+                down = trace[i] - prev < -1e-6
+            if down:
+                print("Warning: ELBO decreases %.8f to %.8f!\n" % (prev, trace[i]))
             elif i == max_iter - 1:
                 print("Warning: VB did not converge!\n")
 

@@ -30,6 +30,7 @@
 
 #include "vrx_common.h"
 #include "vrx_kernels.h"
+#include "vrx_stop.h"
 
 constexpr int VRX_AMB_CELLS = 4;  // cells (waves) per block of the compaction kernels
 
@@ -199,7 +200,10 @@ __device__ __forceinline__ void vrx_amb_cell(int K, int n, const int32_t* __rest
         if (p >= 1) {  // ll = logLik[it] of the reference, it = p - 1 (vireo_doublet.py:170-178)
             const int it = p - 1;
             bool stop = it == max_iter - 1;
-            if (it > min_iter && !(ll < ll_prev) && it != max_iter - 1 && ll - ll_prev < eps) stop = true;
+            // (it == 0: ll_prev is not the reference's logLik[-1] -- vrx_stop_prev is; min_iter >= 0 never judges it)
+            if (vrx_stop_judge(VRX_STOP_EM, it, min_iter, max_iter, eps, vrx_stop_prev(it, max_iter, ll_prev, ll), ll) ==
+                VRX_STOP_STOP)
+                stop = true;
             if (stop) {  // psi_p is final; the reference returns logLik[it - 1] (logLik_RV = logLik[:it])
                 *ll_ret = ll_prev;
                 *it_ret = it;

@@ -31,6 +31,7 @@
 #pragma once
 
 #include "vrx_common.h"
+#include "vrx_stop.h"
 
 constexpr int VRX_BULK_BLOCK = 256;
 constexpr int VRX_BULK_Q = 8;           // psi vectors per log-likelihood pass
@@ -223,15 +224,9 @@ __device__ __forceinline__ void vrx_bulk_finish_one(int n_wg, int K, int G, size
             const int it = p - 1;
             const double ll = sums[W - 1];
             // (it == 0 reads logLik[-1] in the reference: the unwritten last entry, 0, or itself)
-            const double prev = it >= 1 ? trace[it - 1] : (max_iter == 1 ? ll : 0.0);
+            const double prev = vrx_stop_prev(it, max_iter, it >= 1 ? trace[it - 1] : 0.0, ll);
             trace[it] = ll;
-            if (it > min_iter) {
-                if (ll < prev) {
-                } else if (it == max_iter - 1) {
-                } else if (ll - prev < eps) {
-                    stop = true;
-                }
-            }
+            stop = vrx_stop_judge(VRX_STOP_EM, it, min_iter, max_iter, eps, prev, ll) == VRX_STOP_STOP;
             if (it == max_iter - 1) stop = true;  // the loop ends: the update summed here is not applied
             if (stop) {
                 ctl[VRX_BULK_IT] = it;

@@ -2913,6 +2913,7 @@ static VrxStopRule no_rule(int slot) {
     r.it = slot;
     r.min_iter = r.max_iter = r.active = 0;
     r.eps = 0.0;
+    r.form = VRX_STOP_VIREO;  // (never judged)
     return r;
 }
 
@@ -3104,6 +3105,7 @@ extern "C" int vrx_model_fit(vrx_model* m, int32_t max_iter, int32_t min_iter, d
     rule.max_iter = max_iter;
     rule.active = 1;
     rule.eps = eps;
+    rule.form = vrx_stop_form_of_kind(m->cfg.kind);
     const Schedule sc{rule, delay_fit_theta, elbo_can_ride(m, rule)};
     const int R = m->R;  // elbo_trace [R][max_iter], it_out [R], warn_flags [R]
     // two pinned read-back buffers of R * VRX_CTL_WORDS <= 64 words inside h_pin (64 doubles)
@@ -3553,5 +3555,38 @@ extern "C" int vrx_problem_ambient(vrx_problem* p, int64_t n_donor, const double
     VRX_HIP(hipStreamSynchronize(s));
     if (ms3)
         for (int i = 0; i < 3; ++i) VRX_TRY(timer.ms(i, i + 1, &ms3[i]));
+    return VRX_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// the stop rule (vrx_stop.h) as the device compiles it: one lane per row, for the tests
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void vrx_stop_rows(int64_t n, const int32_t* __restrict__ rows_i,
+                                                     const double* __restrict__ rows_d,
+                                                     int32_t* __restrict__ verdict, double* __restrict__ prev_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int form = rows_i[4 * i], it = rows_i[4 * i + 1], min_iter = rows_i[4 * i + 2], max_iter = rows_i[4 * i + 3];
+    const double eps = rows_d[3 * i], trace_prev = rows_d[3 * i + 1], cur = rows_d[3 * i + 2];
+    const double prev = vrx_stop_prev(it, max_iter, trace_prev, cur);
+    prev_out[i] = prev;
+    verdict[i] = vrx_stop_judge(form, it, min_iter, max_iter, eps, prev, cur);
+}
+
+extern "C" int vrx_stop_verdicts(int device, int64_t n, const int32_t* rows_i, const double* rows_d,
+                                 int32_t* verdict, double* prev) {
+    VRX_REQUIRE(n >= 1 && n <= ((int64_t)1 << 24) && rows_i && rows_d && verdict && prev,
+                "vrx_stop_verdicts: null argument, or n outside 1..2^24");
+    if (int e = vrx_use_device("vrx_stop_verdicts", device)) return e;
+    DevBuf<int32_t> d_i, d_v;
+    DevBuf<double> d_d, d_p;
+    VRX_HIP(d_i.upload(rows_i, (size_t)n * 4, 0));
+    VRX_HIP(d_d.upload(rows_d, (size_t)n * 3, 0));
+    VRX_HIP(d_v.alloc((size_t)n));
+    VRX_HIP(d_p.alloc((size_t)n));
+    vrx_stop_rows<<<(unsigned)((n + 255) / 256), 256, 0, 0>>>(n, d_i.p, d_d.p, d_v.p, d_p.p);
+    VRX_HIP(hipGetLastError());
+    VRX_HIP(hipMemcpy(verdict, d_v.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    VRX_HIP(hipMemcpy(prev, d_p.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return VRX_OK;
 }

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "vrx_special.h"
+#include "vrx_stop.h"
 
 constexpr int VRX_BLOCK = 256;  // 4 wavefronts
 constexpr int VRX_WAVES = VRX_BLOCK / 64;
@@ -75,6 +76,7 @@ __device__ __forceinline__ int64_t vrx_col(const VrxBatch& b, int64_t i, int r) 
 struct VrxStopRule {  // by value to the ELBO kernel
     int it, min_iter, max_iter, active;
     double eps;
+    int form;  // VRX_STOP_VIREO / VRX_STOP_BMM (vrx_stop.h), from the model's kind
 };
 
 // ------------------------------------------------------------------------------------
@@ -1330,7 +1332,7 @@ __device__ __forceinline__ void vrx_elbo_final_block(const double* cell_part, in
     const int stop = ctl[VRX_CTL_STOP];
     const bool judge = rule.active && rule.it > rule.min_iter;
     double prev = 0.0;
-    if (threadIdx.x == 0 && judge) prev = elbo_out[rule.it - 1];
+    if (threadIdx.x == 0 && judge && rule.it >= 1) prev = elbo_out[rule.it - 1];  // (it == 0: vrx_stop_prev)
     // the loads of 8 strides are issued together (one memory round trip instead of 8), the
     // additions keep the order of the plain strided loop
     constexpr int UN = 8;
@@ -1387,13 +1389,15 @@ __device__ __forceinline__ void vrx_elbo_final_block(const double* cell_part, in
         elbo_out[rule.it] = cur;
 #pragma unroll
         for (int i = 0; i < 4; ++i) parts_out[i] = tot[i];
-        // the stop rule of _fit_VB / _fit_BV (vireo_model.py:266-274, bmm_model.py:190-199)
+        // the stop rule of _fit_VB / _fit_BV (vireo_model.py:266-274, bmm_model.py:190-199), each in its own form
         if (judge) {
-            if (cur < prev - 1e-6) {
+            const int verdict = vrx_stop_judge(rule.form, rule.it, rule.min_iter, rule.max_iter, rule.eps,
+                                               vrx_stop_prev(rule.it, rule.max_iter, prev, cur), cur);
+            if (verdict == VRX_STOP_WARN_DECREASED) {
                 ctl[VRX_CTL_WARN] |= 1;
-            } else if (rule.it == rule.max_iter - 1) {
+            } else if (verdict == VRX_STOP_WARN_NOT_CONVERGED) {
                 ctl[VRX_CTL_WARN] |= 2;
-            } else if (cur - prev < rule.eps) {
+            } else if (verdict == VRX_STOP_STOP) {
                 ctl[VRX_CTL_IT] = rule.it;
                 __threadfence();
                 ctl[VRX_CTL_STOP] = 1;

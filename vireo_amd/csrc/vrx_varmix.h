@@ -33,6 +33,7 @@
 
 #include "vrx_common.h"
 #include "vrx_special.h"
+#include "vrx_stop.h"
 
 constexpr int VRX_VM_BLOCK = 256;  // threads of a workgroup: four rows by wave, or one long row
 constexpr int VRX_VM_WAVES = VRX_VM_BLOCK / 64;
@@ -286,15 +287,15 @@ __global__ __launch_bounds__(VRX_VM_BLOCK) void vrx_varmix_fit_k(const VrxVmArgs
         const double elbo = acc[3 * K] - acc[3 * K + 1] - kl_theta;
         if (g->trace && t == 0) g->trace[v * g->max_iter + it] = elbo;
         bool stop = it == g->max_iter - 1;
-        if (it > g->min_iter) {  // bmm_model.py:190-199, in its order of comparisons
-            const double diff = elbo - prev;
-            if (diff < -1e-6)
-                warn |= 1;
-            else if (it == g->max_iter - 1)
-                warn |= 2;
-            else if (diff < g->eps)
-                stop = true;
-        }
+        // bmm_model.py:190-199, in its order of comparisons
+        const int verdict = vrx_stop_judge(VRX_STOP_BMM, it, g->min_iter, g->max_iter, g->eps,
+                                           vrx_stop_prev(it, g->max_iter, prev, elbo), elbo);
+        if (verdict == VRX_STOP_WARN_DECREASED)
+            warn |= 1;
+        else if (verdict == VRX_STOP_WARN_NOT_CONVERGED)
+            warn |= 2;
+        else if (verdict == VRX_STOP_STOP)
+            stop = true;
         if (stop) break;  // (uniform over the unit)
         prev = elbo;
     }

@@ -30,6 +30,15 @@ def _prior_rows(P, full_rows):
     return f64(P), full_rows
 
 
+def trace_prev(trace, i, max_iter):
+    """What the reference's ``ELBO[i - 1]`` holds while ``ELBO[i]`` is its newest entry, ``ELBO`` being
+    ``np.zeros(max_iter)`` (vireo_model.py:255, bmm_model.py:182): at i = 0 Python reads the LAST entry, which
+    is still 0 -- or ``ELBO[0]`` itself when max_iter is 1 (csrc/vrx_stop.h, vrx_stop_prev)."""
+    if i >= 1:
+        return trace[i - 1]
+    return trace[0] if max_iter == 1 else 0.0
+
+
 class DeviceModel(_lib.Handle):
     def __init__(self, counts, kind, n_donor, n_gt=3, learn_gt=True, learn_theta=True,
                  ase_mode=False, fix_beta_sum=False, n_batch=1):

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from .counts import device_counts
-from .engine import DeviceModel
+from .engine import DeviceModel, trace_prev
 from .vireo_base import normalize
 
 
@@ -221,8 +221,8 @@ class Vireo():
         self._pull(dm, want_GT=True)
         dm.close()
         if verbose:          # replay the reference's prints (vireo_model.py:266-272)
-            for i in range(min_iter + 1, it + 1):
-                if trace[i] < trace[i - 1] - 1e-6:
+            for i in range(max(min_iter + 1, 0), it + 1):      # (it > min_iter, from it = 0 on)
+                if trace[i] < trace_prev(trace, i, max_iter) - 1e-6:
                     print("Warning: Lower bound decreases!\n")
                 elif i == max_iter - 1:
                     print("Warning: VB did not converge!\n")
