@@ -17,6 +17,23 @@
  *       beta_mu/beta_sum (theta_rows, n_gt) for Vireo [theta_rows = n_var in ASE mode
  *       else 1], (n_var, n_donor) for BinomMixtureVB.
  *   - one host thread per handle; distinct handles may be driven concurrently.
+ *   - a model's VISIBLE STATE is: its state arrays (ID_prob, GT_prob, beta_mu, beta_sum; per
+ *     restart in a batch), the priors as last set, logLik_ID on the device, the content of the
+ *     snapshot slot (if anything was saved) and of the two staging buffers.  The results of a
+ *     call -- what it returns and the visible state it leaves -- depend on the visible state
+ *     alone, bit for bit, never on which calls came before: whatever the library defers or
+ *     caches between calls is invisible here.  A fresh model of the same problem and
+ *     configuration that is given the visible state (set_prior, set_state, set_loglik,
+ *     snapshot, stage_raw) continues exactly as the old one would.
+ *   - logLik_ID on the device is defined by VRX_STEP_ID, VRX_STEP_LOGLIK, vrx_model_fit and
+ *     vrx_model_run_iters (their last iteration's, on every kernel path) and by
+ *     vrx_model_set_loglik; it is all zeros in a new model.  The other calls leave it alone.
+ *   - vrx_model_get_elbo_parts is defined only straight after a call that computed an ELBO
+ *     (VRX_STEP_ELBO, vrx_model_fit, vrx_model_run_iters): the parts of the last ELBO that call
+ *     computed.  No other successful call may come between.
+ *   - a refused call (any error return of an argument check: a restore with nothing saved, a
+ *     staged upload before vrx_model_stage_reserve, an unknown step code, ...) changes nothing:
+ *     not the visible state, and not the ELBO parts of the call before it.
  */
 #ifndef VIREO_HIP_H
 #define VIREO_HIP_H
@@ -197,10 +214,13 @@ int vrx_model_fit(vrx_model* m, int32_t max_iter, int32_t min_iter, double epsil
 #define VRX_STEP_SOFTMAX 6 /* ID_prob <- softmax(logLik_ID on device + log ID_prior): the tail of
                               update_ID_prob alone (bmm_model.py:153-154 with logLik_ID given) */
 int vrx_model_step(vrx_model* m, int32_t which, double* elbo_out /* VRX_STEP_ELBO only */);
+/* logLik_ID as the call that defined it last left it (see Conventions): a step, the last
+ * iteration of a fit or of vrx_model_run_iters, or vrx_model_set_loglik.  Single models. */
 int vrx_model_get_loglik(vrx_model* m, double* logLik_ID /* n_cell x n_donor */);
 int vrx_model_set_loglik(vrx_model* m, const double* logLik_ID);
 /* the four ELBO terms of the last VRX_STEP_ELBO / fit iteration:
- * LB_p, KL_ID, KL_GT, KL_theta (vireo_model.py:236-245) */
+ * LB_p, KL_ID, KL_GT, KL_theta (vireo_model.py:236-245); [R][4] for a batch.  Defined only
+ * straight after the call that computed that ELBO (see Conventions). */
 int vrx_model_get_elbo_parts(vrx_model* m, double* parts4);
 
 /* Doublet scoring with a fitted model, the device form of predict_doublet

@@ -2367,9 +2367,11 @@ int vrx_model_state_buffers(vrx_model* m, bool will_write, VrxModelBuffers* out)
     return VRX_OK;
 }
 
-// logLik_ID as the last step (VRX_STEP_ID / VRX_STEP_LOGLIK) left it.  Not after a fit: on tiled cell
-// streams with several ranges or split rows, a fit's cell passes leave logLik_ID as partials in RC
-// (summed inside the softmax kernel, take_LID) and never write LID.
+// logLik_ID as the call that defined it last left it: VRX_STEP_ID / VRX_STEP_LOGLIK, vrx_model_set_loglik,
+// or the last iteration of a fit / vrx_model_run_iters.  On tiled cell streams with several ranges or split
+// rows a fit's cell passes leave logLik_ID as partials in RC (take_LID); vrx_cell_softmax sums them and
+// STORES the summed row into LID, so LID is final behind every iteration on every path
+// (tests/test_gpu_model_sequences.py holds it against the oracle and against set_loglik, bit for bit).
 extern "C" int vrx_model_get_loglik(vrx_model* m, double* out) {
     VRX_REQUIRE(m && out, "vrx_model_get_loglik: null argument");
     VRX_HIP(hipSetDevice(m->p->device));
