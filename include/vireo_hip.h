@@ -624,6 +624,46 @@ int vrx_model_info(vrx_model* m, int32_t* info16);
 #define VRX_LDS_LAUNCH_FIELDS 10
 int vrx_model_lds_launches(vrx_model* m, int32_t orient, int32_t* out /* cap x VRX_LDS_LAUNCH_FIELDS */,
                            int32_t cap, int32_t* n_out);
+/* What the dense kernels' last launches of each kind did (host bookkeeping, written where the launch is
+ * enqueued; 0 / -1 until that kind has been launched).  out[VRX_DENSE_FIELDS], by index:
+ *   N_CU          compute units the grid caps were formed for
+ *   NB_THETA      blocks of the last theta kernel without the ELBO ride block (vrx_theta_partial; the
+ *                 whole grid of vrx_theta_ase / vrx_bmm_theta)
+ *   THETA_FINAL   how the last shared-theta update was finalised: VRX_DENSE_THETA_NONE (none yet, or a
+ *                 kind that finalises inside its theta kernel), _FUSED (inside vrx_gt_update, VrxThetaFuse)
+ *                 or _KERNEL (vrx_theta_final); THETA_PARTS = the stage-1 partials it summed
+ *   NB_GT         blocks (= KL_GT partials) of the last vrx_gt_update
+ *   NB_CELL, KP   blocks and lanes per cell of the last vrx_cell_softmax<KP>
+ *   CELL_SOURCE   where the cell partials the next ELBO sums came from: VRX_DENSE_CELL_SOFTMAX or
+ *                 VRX_DENSE_CELL_FUSED (the epilogue of the fused cell pass), -1 before either
+ *   ELBO_CELL / _GT / _TH   the partial counts (per restart) the last vrx_elbo_final summed
+ *   RIDE_CELL / _GT / _TH   the same of the last ELBO that rode as the extra block of the next theta launch
+ *   ELBO_CARRIER  which of the two ran last: VRX_DENSE_ELBO_NONE, _KERNEL (vrx_elbo_final) or _RIDE        */
+#define VRX_DENSE_N_CU 0
+#define VRX_DENSE_NB_THETA 1
+#define VRX_DENSE_THETA_FINAL 2
+#define VRX_DENSE_THETA_PARTS 3
+#define VRX_DENSE_NB_GT 4
+#define VRX_DENSE_NB_CELL 5
+#define VRX_DENSE_KP 6
+#define VRX_DENSE_CELL_SOURCE 7
+#define VRX_DENSE_ELBO_CELL 8
+#define VRX_DENSE_ELBO_GT 9
+#define VRX_DENSE_ELBO_TH 10
+#define VRX_DENSE_RIDE_CELL 11
+#define VRX_DENSE_RIDE_GT 12
+#define VRX_DENSE_RIDE_TH 13
+#define VRX_DENSE_ELBO_CARRIER 14
+#define VRX_DENSE_FIELDS 15
+#define VRX_DENSE_THETA_NONE 0
+#define VRX_DENSE_THETA_FUSED 1
+#define VRX_DENSE_THETA_KERNEL 2
+#define VRX_DENSE_CELL_SOFTMAX 0
+#define VRX_DENSE_CELL_FUSED 1
+#define VRX_DENSE_ELBO_NONE 0
+#define VRX_DENSE_ELBO_KERNEL 1
+#define VRX_DENSE_ELBO_RIDE 2
+int vrx_model_dense_launches(vrx_model* m, int32_t* out /* VRX_DENSE_FIELDS */);
 int vrx_model_profile(vrx_model* m, int32_t enable);
 int vrx_model_profile_read(vrx_model* m, double* ms_total /* VRX_KERN_COUNT */,
                            int64_t* launches /* VRX_KERN_COUNT */);

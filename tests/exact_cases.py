@@ -260,12 +260,17 @@ CASES_A, CASES_B = {}, {}
 
 
 def _case(table, name, data, K=4, T=3, kind="vireo", ase=False, fix=False, learn_gt=True, state=(),
-          prior=(), env=None, balance=None, want=None, seed=0, restarts=1, iters=1, fused_softmax=None):
+          prior=(), env=None, balance=None, want=None, seed=0, restarts=1, iters=1, fused_softmax=None,
+          route=None):
+    """data: a name of DATA, or a function of the grid terms (``grid_terms``) that gives (N, M, maker) --
+    the dense-grid cases, whose sizes follow the device's CU count; route: what ``dense_grid`` and the
+    model's launch record must give for them"""
     assert name not in table
     table[name] = SimpleNamespace(name=name, data=data, K=K, T=T, kind=kind, ase=ase, fix=fix,
                                   learn_gt=learn_gt, state=tuple(state), prior=tuple(prior),
                                   env=dict(env or {}), balance=balance, want=dict(want or {}), seed=seed,
-                                  restarts=restarts, iters=iters, fused_softmax=fused_softmax)
+                                  restarts=restarts, iters=iters, fused_softmax=fused_softmax,
+                                  route=dict(route or {}))
 
 
 LDS0, LDS1 = {"VIREO_LDS": "0"}, {"VIREO_LDS": "1"}
@@ -346,6 +351,131 @@ def expected_slabs(n_var, n_cell, cell_form, var_form, n_cu, fill, extra=(0, 0))
            else slab_geometry(n_var + extra[0], n_cell, RW_VARIANT, SLAB_VARIANT, n_cu, fill))
     rw = cell_rows_per_wave(n_var, n_cell, cell_form, n_cu)
     return var, slab_geometry(n_cell + extra[1], n_var, rw, SLAB_CELL, n_cu, fill)
+
+
+# ---- the grids of the dense kernels -------------------------------------------------------------
+# vrx_model_create, theta_step, gt_step, softmax_step and cell_pass_softmax of vrx_engine.hip restated:
+# what ``DeviceModel.dense_launches()`` must report for a shape, and how many sweeps of a capped grid
+# / trips of a second-stage loop that makes.  Each constant with the line it restates:
+VRX_BLOCK = 256                   # vrx_kernels.h: constexpr int VRX_BLOCK = 256
+VRX_WAVES = VRX_BLOCK // 64       # vrx_kernels.h: constexpr int VRX_WAVES = VRX_BLOCK / 64
+XCDS = 8                          # vrx_engine.hip: static constexpr int kXcd = 8
+THETA_BLOCKS_PER_CU = 4           # m->nb_theta = std::min(m->nb_nk, p->n_cu * 4)
+GT_BLOCKS_PER_CU = 8              # m->nb_gt = std::min(m->nb_nk, p->n_cu * 8)
+SOFTMAX_BLOCKS_PER_CU = 4         # env_int("VIREO_SOFTMAX_BLOCKS_PER_CU", 4); 0: no cap
+FUSE_THETA_MAX_PARTS = 256        # env_int("VIREO_FUSE_THETA_MAX_PARTS", 256): nb_theta <= fuse_max fuses
+THETA_FINAL_IN_FLIGHT = 4         # vrx_theta_final_block: b0 += 4 * VRX_BLOCK
+ELBO_IN_FLIGHT = 8                # vrx_elbo_final_block: constexpr int UN = 8
+BMM_LANES = 16                    # theta_step: (m->NK * 16 + VRX_BLOCK - 1) / VRX_BLOCK with the range sum fused
+N_CU = 256                        # the CU count the sizes of the dense cases are evaluated for (``set_n_cu``)
+
+
+def pick_kp(K):
+    """pick_kp: lanes per cell of vrx_cell_softmax<KP>, the power of two >= K, 64 at most"""
+    kp = 1
+    while kp < K and kp < 64:
+        kp <<= 1
+    return kp
+
+
+def dense_grid(N, M, K, R=1, kind="vireo", ase=False, n_cu=256, softmax_cap=SOFTMAX_BLOCKS_PER_CU,
+               fused_cell_pass=False, n_seg=0, fused_range_sum=False):
+    """The grids and partial counts of the dense kernels for a model of N variants, M cells, K donors
+    (R restarts change none of them: the batch is the grid's y), and the loop trips they imply.
+    fused_cell_pass: the cell partials come from the epilogue of the gather cell pass over n_seg
+    segments; fused_range_sum (clone mode): vrx_bmm_theta sums the LDS pass's ranges, 16 lanes an element."""
+    g = SimpleNamespace(n_cu=n_cu, KP=pick_kp(K))
+    nb_nk = _up(N * K, VRX_BLOCK)
+    g.nb_gt = min(nb_nk, n_cu * GT_BLOCKS_PER_CU)
+    if kind != "vireo":
+        g.nb_theta = _up(N * K * BMM_LANES, VRX_BLOCK) if fused_range_sum else nb_nk
+    elif ase:
+        g.nb_theta = _up(N, VRX_BLOCK)               # vrx_theta_ase: a thread per variant, no stride
+    else:
+        g.nb_theta = min(nb_nk, n_cu * THETA_BLOCKS_PER_CU)
+    shared = kind == "vireo" and not ase
+    g.fuse = shared and g.nb_theta <= FUSE_THETA_MAX_PARTS     # (in the fit loop; ``step`` never fuses)
+    g.nb_cell = _up(M * g.KP, VRX_BLOCK)
+    if softmax_cap > 0:
+        g.nb_cell = min(g.nb_cell, n_cu * softmax_cap)
+    g.n_cell_part = n_seg // VRX_WAVES if fused_cell_pass else g.nb_cell
+    g.n_gt_part = g.nb_gt if kind == "vireo" else 0
+    g.n_th_part = 1 if shared else g.nb_theta
+    # sweeps of the grid-stride loops, strides of the shared theta's second stage, trips of the ELBO's
+    g.theta_sweeps = _up(nb_nk, g.nb_theta) if shared else 1
+    g.gt_sweeps = _up(nb_nk, g.nb_gt) if kind == "vireo" else 0
+    g.cell_sweeps = _up(M, g.nb_cell * VRX_BLOCK // g.KP)
+    g.final_strides = _up(g.nb_theta, VRX_BLOCK) if shared else 0          # (partials per thread)
+    g.final_trips = _up(g.nb_theta, THETA_FINAL_IN_FLIGHT * VRX_BLOCK) if shared else 0   # (2 past 256 CUs only)
+    g.elbo_trips = _up(max(g.n_cell_part, g.n_gt_part, g.n_th_part), ELBO_IN_FLIGHT * VRX_BLOCK)
+    return g
+
+
+def fused_cell_segments(M):
+    """n_seg of build_orient for M cells of one short segment each on one tile: groups of VRX_WAVES
+    segments go round the XCDs, every XCD is padded to the longest, whole blocks"""
+    return _up(_up(M, VRX_WAVES), XCDS) * XCDS * VRX_WAVES
+
+
+def grid_terms(n_cu, softmax_cap=SOFTMAX_BLOCKS_PER_CU):
+    """what the dense cases write their sizes in: S1 / S2 elements fill the capped grid of
+    vrx_theta_partial / vrx_gt_update once, C lanes that of vrx_cell_softmax, B one block; rows(n, K) is
+    the fewest rows of K columns that hold n elements"""
+    return SimpleNamespace(n_cu=n_cu, B=VRX_BLOCK, S1=THETA_BLOCKS_PER_CU * n_cu * VRX_BLOCK,
+                           S2=GT_BLOCKS_PER_CU * n_cu * VRX_BLOCK, C=softmax_cap * n_cu * VRX_BLOCK,
+                           rows=_up)
+
+
+def set_n_cu(n_cu):
+    """the device's CU count, for the sizes of the dense cases (the CPU twin keeps 256)"""
+    global N_CU
+    N_CU = int(n_cu)
+
+
+def softmax_cap_of(spec):
+    return int(spec.env.get("VIREO_SOFTMAX_BLOCKS_PER_CU", SOFTMAX_BLOCKS_PER_CU))
+
+
+def dense_shape(spec, n_cu):
+    """(N, M, maker) of a dense case for a CU count"""
+    return spec.data(grid_terms(n_cu, softmax_cap_of(spec)))
+
+
+def dense_route(spec, N, M, n_cu):
+    """``dense_grid`` of a case: flow B's cell partials come from the fused cell pass where the case
+    says so (fused_softmax), clone mode on the LDS path fuses its range sum in the fit loop"""
+    fused = bool(spec.fused_softmax)
+    return dense_grid(N, M, spec.K, spec.restarts, spec.kind, spec.ase, n_cu, softmax_cap_of(spec),
+                      fused_cell_pass=fused, n_seg=fused_cell_segments(M) if fused else 0,
+                      fused_range_sum=bool(spec.route.get("fused_range_sum")))
+
+
+ROUTE_KEYS = ("theta_sweeps", "gt_sweeps", "cell_sweeps", "final_strides", "elbo_trips", "fuse", "n_cell_part",
+              "n_th_part")
+
+
+def route_misses(spec, n_cu):
+    """[(key, declared, restated)] where ``dense_grid`` does not put the case on the route it declares"""
+    N, M, _ = dense_shape(spec, n_cu)
+    g = dense_route(spec, N, M, n_cu)
+    return [(k, v, getattr(g, k)) for k, v in spec.route.items() if k in ROUTE_KEYS and getattr(g, k) != v]
+
+
+def _thin(cells_full=False, density=0.15, depth=3.0, full_rows=(), full_cols=()):
+    """the dense cases' counts: the other dimension is tiny, so the sparse passes stay trivial;
+    full_rows / full_cols: variants / cells with an entry everywhere (long rows are cut into pieces)"""
+    def make(N, M):
+        ad, dp = _draw(N, M, density, depth, 3 * N + M)
+        dp[-1, -1] = max(dp[-1, -1], 2)              # (an entry in the last row of both orientations)
+        for n in full_rows:
+            dp[n, :] = np.maximum(dp[n, :], 1)
+        for m in full_cols:
+            dp[:, m] = np.maximum(dp[:, m], 1)
+        if cells_full:                                # every cell has an entry: the fused cell softmax needs it
+            for m in np.flatnonzero(dp.sum(0) == 0):
+                dp[m % N, m] = 2
+        return np.minimum(ad, dp), dp
+    return make
 
 
 def _a(*a, **k):
@@ -531,13 +661,180 @@ _b("batch3_blocks", "mid", K=6, restarts=3, env=LDS1,
    want=dict(ON, n_batch=3, cell_form=1, var_form=3, perm=False, **_f1_inst(18, RW_CELL_SHORT)))
 
 
+# ---- the dense kernels past their grid caps -----------------------------------------------------
+# Sizes are expressions in the grid terms (``grid_terms``: S1, S2, C, B, rows), evaluated for the
+# device's CU count; ``route`` declares the sweeps / strides / trips the case must take (held to
+# ``dense_grid`` on the CPU for three CU counts, and to ``DeviceModel.dense_launches()`` on the device
+# before any number is compared).  The other dimension stays tiny.  An element's (n, k) matters only
+# to the batched index (R > 1), the fused range sums (npiece[n], vptr), the per-donor and per-variant
+# priors, W in planar form and psi in ASE mode: a K that divides the stride (16) never takes the wrap
+# branch of the stepping, an odd K does in every sweep.
+DENSE_A, DENSE_B = [], []
+
+
+def _variants(elements, K, M=32, **thin):
+    """N = the fewest variants with N K >= elements(g), on M cells"""
+    return lambda g: (g.rows(elements(g), K), M, _thin(**thin))
+
+
+def _cells(cells, N=32, **thin):
+    return lambda g: (N, cells(g), _thin(**thin))
+
+
+def _da(name, *a, **k):
+    DENSE_A.append(name)
+    _a(name, *a, **k)
+
+
+def _db(name, *a, **k):
+    DENSE_B.append(name)
+    _b(name, *a, **k)
+
+
+# the shared theta's second stage (``step`` runs it as vrx_theta_final): 256 partials = one per thread,
+# 257 and 513 = two and three strides, 4 n_cu = the whole capped grid, still one sweep of the first stage
+_da("dense_parts256", lambda g: (g.B * g.B // 5, 32, _thin()), K=5, env=LDS0, want=OFF,
+    route=dict(theta_sweeps=1, final_strides=1, fuse=True))
+_da("dense_parts257", lambda g: (g.B * g.B // 5 + 1, 32, _thin()), K=5, env=LDS0, want=OFF,
+    route=dict(theta_sweeps=1, final_strides=2, fuse=False))
+_da("dense_parts513", _variants(lambda g: 2 * g.B * g.B + 1, 7), K=7, env=LDS0, want=OFF,
+    route=dict(theta_sweeps=1, final_strides=3, fuse=False))
+_da("dense_theta_full_grid", lambda g: (g.S1 // 16, 32, _thin()), K=16, env=LDS0, want=OFF,
+    route=dict(theta_sweeps=1, gt_sweeps=1, fuse=False))
+# vrx_theta_partial past its cap: second and third sweep, step_k = 0 (K = 16) and the wrap (K = 17, 7, 5)
+_da("dense_theta2_K16", _variants(lambda g: g.S1 + 1, 16), K=16, env=LDS0, want=OFF,
+    route=dict(theta_sweeps=2, gt_sweeps=1))
+_da("dense_theta2_K17", _variants(lambda g: g.S1 + 1, 17), K=17, env=LDS0, want=OFF,
+    route=dict(theta_sweeps=2, gt_sweeps=1))
+_da("dense_theta2_K5_T4", _variants(lambda g: g.S1 + 1, 5), K=5, T=4, env=LDS0, want=OFF,
+    route=dict(theta_sweeps=2, gt_sweeps=1))
+_da("dense_theta3_K7", _variants(lambda g: 2 * g.S1 + 3, 7), K=7, env=LDS0, want=OFF,
+    route=dict(theta_sweeps=3, gt_sweeps=2))
+# vrx_gt_update past its cap (learn = 1 in the GT step, learn = 0 in the ID and ELBO steps of every case)
+_da("dense_gt2_K16", _variants(lambda g: g.S2 + 1, 16, M=24), K=16, env=LDS0, want=OFF,
+    route=dict(theta_sweeps=3, gt_sweeps=2))
+_da("dense_gt2_K17", _variants(lambda g: g.S2 + 1, 17, M=24), K=17, env=LDS0, want=OFF,
+    route=dict(theta_sweeps=3, gt_sweeps=2))
+_da("dense_gt2_K7_T4", _variants(lambda g: g.S2 + 1, 7, M=24), K=7, T=4, env=LDS0, want=OFF,
+    route=dict(theta_sweeps=3, gt_sweeps=2))
+_da("dense_gt3_K5", _variants(lambda g: 2 * g.S2 + 3, 5, M=24), K=5, env=LDS0, want=OFF,
+    route=dict(theta_sweeps=5, gt_sweeps=3))
+# what reads an element's (n, k), each on a strided shape with an odd K
+_da("dense_gt2_prior_row", _variants(lambda g: g.S2 + 1, 17, M=24), K=17, prior=[pr_gt_row], env=LDS0, want=OFF,
+    route=dict(gt_sweeps=2))
+_da("dense_gt2_prior_full", _variants(lambda g: g.S2 + 1, 17, M=24), K=17, prior=[pr_gt_full], env=LDS0, want=OFF,
+    route=dict(gt_sweeps=2))
+_da("dense_gt2_fixed_gt", _variants(lambda g: g.S2 + 1, 17, M=24), K=17, learn_gt=False, env=LDS0, want=OFF,
+    route=dict(gt_sweeps=2))
+# (wform 0: every gather case above; wform 1: planar W for the AD/BD cell stream, row index n, column k)
+_da("dense_gt2_planar_w", _variants(lambda g: g.S2 + 1, 17, M=24), K=17,
+    env=dict(LDS1, VIREO_CELL_FORM="1", VIREO_VAR_FORM="3"), want=dict(ON, cell_form=1, var_form=3),
+    route=dict(gt_sweeps=2))
+_da("dense_gt2_pairs_w", _variants(lambda g: g.S2 + 1, 17, M=24), K=17, env=PAIRS,
+    want=dict(ON, cell_form=0, var_form=0), route=dict(gt_sweeps=2))
+# (ASE: psi row n.  One mpmath argument per variant and class in the reference, so K is large and N small)
+_da("dense_gt2_ase_K63", _variants(lambda g: g.S2 + 1, 63, M=24), K=63, ase=True, state=[st_random_theta],
+    env=LDS0, want=OFF, route=dict(gt_sweeps=2))
+
+# the cell softmax past its cap: every KP at two sweeps, 16 / 32 / 64 at three; K inside its KP (5 in 8,
+# 17 in 32, 33 in 64); the first sweep's preload must not reach the second
+for _K in (16, 17, 33):
+    _kp = pick_kp(_K)
+    _da("dense_cell2_K%d" % _K, _cells(lambda g, kp=_kp: g.C // kp + 1), K=_K, env=LDS0, want=OFF,
+        route=dict(cell_sweeps=2))
+    _da("dense_cell3_K%d" % _K, _cells(lambda g, kp=_kp: 2 * (g.C // kp) + 3), K=_K, env=LDS0, want=OFF,
+        route=dict(cell_sweeps=3))
+_da("dense_cell2_K5", _cells(lambda g: g.C // 8 + 1, N=24), K=5, env=LDS0, want=OFF, route=dict(cell_sweeps=2))
+CAP1 = {"VIREO_SOFTMAX_BLOCKS_PER_CU": "1"}
+for _K in (2, 3, 8):
+    _kp = pick_kp(_K)
+    _da("dense_cell2_cap1_K%d" % _K, _cells(lambda g, kp=_kp: g.C // kp + 1, N=24), K=_K, env=dict(LDS0, **CAP1),
+        want=OFF, route=dict(cell_sweeps=2))
+# id_mode 0 is every case above; 1 and 2; logLik_ID summed from the LDS cell pass's output
+_da("dense_cell2_id_vector", _cells(lambda g: g.C // 32 + 1), K=17, prior=[pr_id_vector], env=LDS0, want=OFF,
+    route=dict(cell_sweeps=2))
+_da("dense_cell2_id_cells", _cells(lambda g: g.C // 32 + 1), K=17, prior=[pr_id_cells], env=LDS0, want=OFF,
+    route=dict(cell_sweeps=2))
+_da("dense_cell2_lds", _cells(lambda g: g.C // 32 + 1), K=17, env=LDS1, want=ON, route=dict(cell_sweeps=2))
+
+# the ELBO's second stage through vrx_elbo_final (VRX_STEP_ELBO): 2 048 cell partials = one trip, 2 049 = two,
+# 4 097 = three, with the softmax's grid uncapped (KP = 64: four cells a block)
+CAP0 = {"VIREO_SOFTMAX_BLOCKS_PER_CU": "0"}
+for _blocks, _trips in ((2048, 1), (2049, 2), (4097, 3)):
+    _da("dense_elbo_parts%d" % _blocks, _cells(lambda g, b=_blocks: 4 * b - 1, N=24), K=33,
+        env=dict(LDS0, **CAP0), want=OFF, route=dict(elbo_trips=_trips, cell_sweeps=1, n_cell_part=_blocks))
+
+# the fit loop at these sizes, two iterations (run_iters: no stop rule): the first ELBO rides in the second
+# theta launch, the second has its own kernel; past 256 partials the theta finalisation is vrx_theta_final
+RIDE1 = {"VIREO_ELBO_RIDE": "1"}
+_db("dense_fit_parts256", lambda g: (g.B * g.B // 5, 32, _thin()), K=5, iters=2, env=dict(LDS0, **RIDE1, **FUSE0),
+    want=OFF, fused_softmax=False, route=dict(theta_sweeps=1, fuse=True))
+_db("dense_fit_parts257", lambda g: (g.B * g.B // 5 + 1, 32, _thin()), K=5, iters=2,
+    env=dict(LDS0, **RIDE1, **FUSE0), want=OFF, fused_softmax=False, route=dict(theta_sweeps=1, fuse=False))
+_db("dense_fit_theta2_K17", _variants(lambda g: g.S1 + 1, 17), K=17, iters=2, env=dict(LDS0, **RIDE1, **FUSE0),
+    want=OFF, fused_softmax=False, route=dict(theta_sweeps=2, fuse=False))
+_db("dense_fit_gt2_K7_R3", _variants(lambda g: g.S2 + 1, 7, M=24), K=7, iters=2, restarts=3,
+    env=dict(LDS0, **RIDE1), want=dict(OFF, n_batch=3), route=dict(theta_sweeps=3, gt_sweeps=2, fuse=False))
+# the range sums fused into the strided kernels: AD/BD virtual rows (var_form 3) and pair words
+_db("dense_fit_theta2_virtual", _variants(lambda g: g.S1 + 1, 17), K=17, iters=2,
+    env=dict(LDS1, VIREO_CELL_FORM="1", VIREO_VAR_FORM="3", **RIDE1), want=dict(ON, cell_form=1, var_form=3),
+    route=dict(theta_sweeps=2, fuse=False))
+# (pair words sum their ranges in the kernel only when a tile has several: 130 cells = 3 slabs of 64)
+_db("dense_fit_theta2_pairs_R2", _variants(lambda g: g.S1 + 1, 17, M=130), K=17, iters=2, restarts=2,
+    env=dict(PAIRS, **RIDE1), want=dict(ON, cell_form=0, var_form=0, n_batch=2, ranges_variant=many),
+    route=dict(theta_sweeps=2, fuse=False))
+# (rows cut into pieces -- vptr: two variants that cover every one of 200 cells)
+_db("dense_fit_theta2_pieces", _variants(lambda g: g.S1 + 1, 17, M=200, full_rows=(5, -1)), K=17, iters=2,
+    env=dict(LDS1, VIREO_CELL_FORM="1", VIREO_VAR_FORM="3", **RIDE1),
+    want=dict(ON, cell_form=1, var_form=3, extra_pieces_variant=some), route=dict(theta_sweeps=2, fuse=False))
+# logLik_ID from the LDS cell pass's ranges (200 variants = 4 slabs of 64), and from a cell cut into pieces
+_db("dense_fit_cell2_lds", _cells(lambda g: g.C // 32 + 1, N=200, density=0.1), K=17, iters=2,
+    env=dict(LDS1, **RIDE1), want=dict(ON, ranges_cell=many), fused_softmax=False, route=dict(cell_sweeps=2))
+_db("dense_fit_cell2_pieces", _cells(lambda g: g.C // 32 + 1, N=200, density=0.1, full_cols=(3, -1)), K=17, iters=2,
+    env=dict(LDS1, **RIDE1), want=dict(ON, extra_pieces_cell=some), fused_softmax=False, route=dict(cell_sweeps=2))
+_db("dense_fit_cell2_R3", _cells(lambda g: g.C // 8 + 1, N=24), K=5, iters=2, restarts=3, env=dict(LDS1, **RIDE1),
+    want=dict(ON, n_batch=3), route=dict(cell_sweeps=2))
+# the ELBO's second stage in the ride block: the softmax's grid uncapped, and the fused cell pass (one
+# partial per block of VRX_WAVES segments, padded: ``fused_cell_segments``)
+_db("dense_fit_elbo_parts2049", _cells(lambda g: 4 * 2049 - 1, N=24), K=33, iters=2,
+    env=dict(LDS0, **RIDE1, **CAP0, **FUSE0), want=OFF, fused_softmax=False,
+    route=dict(elbo_trips=2, n_cell_part=2049))
+_db("dense_fit_fused_cells2056", _cells(lambda g: 8193, N=24, cells_full=True), K=4, iters=2,
+    env=dict(LDS0, **RIDE1, **FUSE1), want=OFF, fused_softmax=True, route=dict(elbo_trips=2, n_cell_part=2056))
+_db("dense_fit_fused_cells4104", _cells(lambda g: 16385, N=24, cells_full=True), K=16, iters=2,
+    env=dict(LDS0, **RIDE1, **FUSE1), want=OFF, fused_softmax=True, route=dict(elbo_trips=3, n_cell_part=4104))
+# clone mode with the range sum fused into vrx_bmm_theta: 16 lanes an element, N K / 16 KL_theta partials
+# (fused only when a tile has several ranges: 130 cells = 3 slabs of 64.  One iteration: the reference
+# costs six mpmath arguments per element and iteration, so this ELBO has vrx_elbo_final for its carrier;
+# the ride block's trips are held by the cell partials above -- the same vrx_elbo_final_block)
+_db("dense_fit_clone_parts2049", lambda g: (4097, 130, _thin(density=0.5, depth=30.0)), K=8, kind="bmm",
+    state=[st_random_theta], iters=1, env=dict(PAIRS, **RIDE1), want=dict(ON, var_form=0, ranges_variant=many),
+    route=dict(elbo_trips=2, n_th_part=2049, fused_range_sum=True))
+
+# What the sweep leaves out, with the reason (the run's table repeats it):
+NOT_COVERED = (
+    ("n_gt_part > 2048", "nb_gt = min(.., 8 n_cu): 2 048 at 256 CUs, never more"),
+    ("clone mode without the fused range sum, n_th_part > 2048",
+     "needs N K > 524 288 with one mpmath argument per element of the reference; repeated variant rows would "
+     "hide an (n, k) mix-up"),
+)
+
+
 # ------------------------------------------------------------------------------------
 # a case's problem: data, states, priors, exact counts
 # ------------------------------------------------------------------------------------
+def _counts_of(spec, n_cu):
+    if callable(spec.data):
+        N, M, make = dense_shape(spec, n_cu)
+        ad, dp = make(N, M)
+        return csc_matrix(ad), csc_matrix(dp)
+    return data(spec.data)
+
+
 @functools.lru_cache(maxsize=2)
-def _problem(flow, name):
+def _problem(flow, name, n_cu):
     spec = (CASES_A if flow == "A" else CASES_B)[name]
-    AD, DP = data(spec.data)
+    AD, DP = _counts_of(spec, n_cu)
     p = SimpleNamespace(spec=spec, AD=AD, DP=DP, N=AD.shape[0], M=AD.shape[1], K=spec.K, T=spec.T,
                         kind=spec.kind)
     p.C = X.Counts(AD, DP)
@@ -568,11 +865,11 @@ def _problem(flow, name):
 
 
 def problem_a(name):
-    return _problem("A", name)
+    return _problem("A", name, N_CU)
 
 
 def problem_b(name):
-    return _problem("B", name)
+    return _problem("B", name, N_CU)
 
 
 # ------------------------------------------------------------------------------------

@@ -52,11 +52,24 @@ def _mp(x):
     return mpmath.mpf(hi) + mpmath.mpf(float(x - LD(hi)))
 
 
+_MEMO = {}              # fn -> {(hi, lo): value}: one update's functions share their arguments
+
+
 def _special(fn, v):
     v = ld(v)
     u, inv = np.unique(v.ravel(), return_inverse=True)
+    memo = _MEMO.setdefault(fn, {})
+    if len(memo) > 1 << 20:
+        memo.clear()
+    hi = u.astype(np.float64)
+    lo = (u - hi.astype(LD)).astype(np.float64)      # (the two halves of ``_mp``)
+    out = np.empty(u.shape, dtype=LD)
     with mpmath.workdps(40):
-        out = np.array([LD(mpmath.nstr(fn(_mp(x)), 30)) for x in u], dtype=LD)
+        for i, key in enumerate(zip(hi.tolist(), lo.tolist())):
+            val = memo.get(key)
+            if val is None:
+                val = memo[key] = LD(mpmath.nstr(fn(mpmath.mpf(key[0]) + mpmath.mpf(key[1])), 30))
+            out[i] = val
     return out[inv.ravel()].reshape(v.shape)
 
 

@@ -337,6 +337,243 @@ def test_a_row_piece_left_out_fails():
     _planted(name, variant_piece, ("beta_mu", "beta_sum", "GT_prob"))
 
 
+# ---------------------------------------------------------------- the dense kernels past their grid caps
+CU_COUNTS = (256, 208, 304)      # (the fixed 256 / 257 / 513 partials need a cap 4 n_cu >= 513)
+
+
+def _dense(table, names):
+    return [(n, table[n]) for n in names]
+
+
+def test_dense_grid_puts_every_case_on_its_route():
+    """the sizes are expressions in the grid terms: for three CU counts ``dense_grid`` gives every dense
+    case the sweeps / strides / trips it declares, and together they take every threshold of the dense
+    kernels from both sides -- each grid-stride loop twice and three times, the second stage of the
+    shared theta at one, two and three strides (fused and as a kernel), every KP of the cell softmax
+    past its cap, the ELBO's second stage at one, two and three trips by kernel and at two and three
+    in the ride block"""
+    every = _dense(EC.CASES_A, EC.DENSE_A) + _dense(EC.CASES_B, EC.DENSE_B)
+    assert len(every) == len(EC.DENSE_A) + len(EC.DENSE_B) >= 40
+    for n_cu in CU_COUNTS:
+        for name, c in every:
+            assert c.route and EC.route_misses(c, n_cu) == [], (n_cu, name, EC.route_misses(c, n_cu))
+            N, M, _ = EC.dense_shape(c, n_cu)
+            assert min(N, M) <= 200, (name, N, M)            # (the other dimension stays tiny)
+    seen = {}
+    for name, c in every:
+        N, M, _ = EC.dense_shape(c, 256)
+        g = EC.dense_route(c, N, M, 256)
+        flow = "A" if name in EC.DENSE_A else "B"
+        rides = flow == "B" and c.iters >= 2
+        odd = c.K % 16 != 0
+        for k in ("theta_sweeps", "gt_sweeps", "final_strides"):
+            if k in c.route:
+                seen.setdefault(k, set()).add((c.route[k], odd))
+        if "cell_sweeps" in c.route:
+            seen.setdefault("cell_sweeps", set()).add((EC.softmax_cap_of(c), g.KP, c.route["cell_sweeps"]))
+        if "fuse" in c.route:
+            seen.setdefault("fuse", set()).add((flow, c.route["fuse"], g.nb_theta))
+        if "elbo_trips" in c.route:
+            seen.setdefault("elbo_trips", set()).add(("ride" if rides else "kernel", c.route["elbo_trips"]))
+    assert {(2, False), (2, True), (3, True)} <= seen["theta_sweeps"]
+    assert {(2, False), (2, True), (3, True)} <= seen["gt_sweeps"]
+    assert {(1, True), (2, True), (3, True)} <= seen["final_strides"]
+    assert {("B", True, 256), ("B", False, 257)} <= seen["fuse"]
+    assert {(4, kp, s) for kp in (16, 32, 64) for s in (2, 3)} | {(4, 8, 2)} | {(1, kp, 2) for kp in (2, 4, 8)} \
+        <= seen["cell_sweeps"]
+    assert {("kernel", 1), ("kernel", 2), ("kernel", 3), ("ride", 2), ("ride", 3)} <= seen["elbo_trips"]
+
+
+def _sweep_of(p, nb):
+    """(sweep, block) of every (variant, donor) element of a grid-stride kernel of nb blocks"""
+    i = np.arange(p.N * p.K).reshape(p.N, p.K)
+    return i // (nb * EC.VRX_BLOCK), (i // EC.VRX_BLOCK) % nb
+
+
+def _theta_np(p, A, B, GT):
+    """update_theta_size (vireo_model.py:176-185) in float64 from S and GT_prob, element by element"""
+    s1 = p.pri.th1 + np.sum(A[:, :, None] * GT, axis=(0, 1))
+    s2 = p.pri.th2 + np.sum(B[:, :, None] * GT, axis=(0, 1))
+    return s1 / (s1 + s2), s1 + s2
+
+
+def _theta_judge(p, s, A, B, GT):
+    """(units of a planted theta, units of the honest float64 one) for beta_mu and beta_sum"""
+    ex = X.vireo_theta(p.C, s.ID, s.GT, p.pri.th1, p.pri.th2, s.sm)
+    A0 = (p.AD @ s.ID)
+    B0 = (p.DP @ s.ID) - A0
+    out = []
+    for got, honest in zip(_theta_np(p, A, B, GT), _theta_np(p, A0, B0, s.GT)):
+        key = "beta_mu" if len(out) == 0 else "beta_sum"
+        out.append((X.distance(got, *ex[key]), X.distance(honest, *ex[key])))
+    return out
+
+
+def _theta_defect_fails(name, p, s, change):
+    A = p.AD @ s.ID
+    B = (p.DP @ s.ID) - A
+    GT = s.GT.copy()
+    A, B, GT = change(A.copy(), B.copy(), GT)
+    for (u, u_orc), key in zip(_theta_judge(p, s, A, B, GT), ("beta_mu", "beta_sum")):
+        print("%-28s %-9s planted %.3g units against the oracle's %.2f" % (name, key, u, u_orc))
+        assert not X.held(u, u_orc), (name, key, u, u_orc)
+
+
+def _strided_theta(table, names):
+    return [n for n in names if table[n].route.get("theta_sweeps", 1) >= 2 and table[n].kind == "vireo"
+            and not table[n].ase]
+
+
+@pytest.mark.parametrize("name", _strided_theta(EC.CASES_A, EC.DENSE_A))
+def test_b_elements_past_the_first_sweep_dropped_fails(name):
+    """(b) vrx_theta_partial stops after one sweep of its capped grid"""
+    p = EC.problem_a(name)
+    g = EC.dense_route(p.spec, p.N, p.M, EC.N_CU)
+    sweep, _ = _sweep_of(p, g.nb_theta)
+    assert sweep.max() + 1 == p.spec.route["theta_sweeps"]
+
+    def drop(A, B, GT):
+        GT[sweep >= 1] = 0.0
+        return A, B, GT
+    _theta_defect_fails(name, p, p.s0, drop)
+
+
+@pytest.mark.parametrize("name", ["dense_parts257", "dense_parts513", "dense_theta_full_grid", "dense_theta2_K17"])
+def test_c_theta_partials_past_255_dropped_fails(name):
+    """(c) the second stage of the shared theta takes one partial per thread only"""
+    p = EC.problem_a(name)
+    g = EC.dense_route(p.spec, p.N, p.M, EC.N_CU)
+    _, block = _sweep_of(p, g.nb_theta)
+    assert block.max() + 1 == g.nb_theta > 256
+
+    def drop(A, B, GT):
+        GT[block >= 256] = 0.0
+        return A, B, GT
+    _theta_defect_fails(name, p, p.s0, drop)
+
+
+def test_c_partials_inside_the_first_stride_all_count():
+    """the control of (c): at 256 partials the same defect changes nothing"""
+    p = EC.problem_a("dense_parts256")
+    _, block = _sweep_of(p, EC.dense_route(p.spec, p.N, p.M, EC.N_CU).nb_theta)
+    assert block.max() == 255
+
+
+@pytest.mark.parametrize("name", ["dense_elbo_parts2049", "dense_elbo_parts4097"])
+def test_c_elbo_partials_past_2047_dropped_fails(name):
+    """(c) the ELBO's second stage stops after its first trip: the cells of the softmax blocks from 2 048 on
+    are missing from LB_p and KL_ID"""
+    p = EC.problem_a(name)
+    g = EC.dense_route(p.spec, p.N, p.M, EC.N_CU)
+    out = EC.run_a(p, EC.OracleBackend(p))
+    u_orc = EC.distances_a(p, out)
+    block = np.arange(p.M) * g.KP // EC.VRX_BLOCK
+    assert g.cell_sweeps == 1 and block.max() + 1 == g.n_cell_part > 2048
+    keep = block < 2048
+    s = p.s0
+    assert _fails(p, out, u_orc, "LB_p", np.sum((p.L_given * s.ID)[keep]))
+    assert _fails(p, out, u_orc, "KL_ID", np.sum(s.ID[keep] * (np.log(s.ID[keep]) + np.log(p.K))))
+
+
+def _cell_sweep(p, g):
+    """(sweep, the first sweep's cell of the same lanes) of every cell in vrx_cell_softmax"""
+    per = g.nb_cell * EC.VRX_BLOCK // g.KP
+    cell = np.arange(p.M)
+    return cell // per, cell % per
+
+
+@pytest.mark.parametrize("name", [n for n in EC.DENSE_A if "cell_sweeps" in EC.CASES_A[n].route
+                                  and EC.CASES_A[n].route["cell_sweeps"] >= 2])
+def test_d_preload_of_the_first_sweep_reused_fails(name):
+    """(d) a cell of a later sweep takes the logLik_ID its lanes preloaded for the first sweep's cell"""
+    p = EC.problem_a(name)
+    g = EC.dense_route(p.spec, p.N, p.M, EC.N_CU)
+    sweep, first = _cell_sweep(p, g)
+    assert sweep.max() + 1 == p.spec.route["cell_sweeps"]
+    out = EC.run_a(p, EC.OracleBackend(p))
+    u_orc = EC.distances_a(p, out)
+    L = out["logLik_ID"].copy()
+    late = sweep >= 1
+    L[late, :min(p.K, g.KP)] = L[first[late], :min(p.K, g.KP)]
+    prior = p.pri.ID_prior if p.pri.ID_prior is not None else np.ones((1, p.K))
+    assert _fails(p, out, u_orc, "ID_prob", O.softmax_log(L + np.log(prior)))
+
+
+def _stale_k(p, nb):
+    """(a): the element a thread reads in sweep s when its k stays the first sweep's -- index i - s step_k"""
+    sweep, _ = _sweep_of(p, nb)
+    step_k = nb * EC.VRX_BLOCK % p.K
+    i = np.arange(p.N * p.K).reshape(p.N, p.K)
+    return sweep, i - sweep * step_k
+
+
+def test_a_stale_k_in_later_sweeps_fails():
+    """(a) elements of the later sweeps keep the k of the first (no step_k, no wrap), seen where k is read:
+    the per-donor genotype prior of vrx_gt_update, and the batched index of vrx_theta_partial (R > 1:
+    S and GT_prob of element i - s step_k).  A K that divides the stride cannot show it."""
+    p = EC.problem_a("dense_gt2_prior_row")
+    g = EC.dense_route(p.spec, p.N, p.M, EC.N_CU)
+    sweep, j = _stale_k(p, g.nb_gt)
+    assert sweep.max() == 1 and (j % p.K != np.arange(p.K)).any()
+    be = EC.OracleBackend(p)
+    good = be.gt()
+    ex = X.vireo_gt(p.C, p.s0.ID, p.s0.mu, p.s0.sm, p.pri.GT_prior, p.T)["GT_prob"]
+    q = copy.copy(p)
+    q.pri = copy.copy(p.pri)
+    step_k = g.nb_gt * EC.VRX_BLOCK % p.K
+    assert step_k and np.array_equal(j[sweep == 1] % p.K, ((np.arange(p.N * p.K) - step_k) % p.K)[sweep.ravel() == 1])
+    q.pri.GT_prior = np.roll(p.pri.GT_prior, step_k, axis=1)       # (one (1, K, T) slab: donor k reads k - step_k)
+    stale = EC.OracleBackend(q).gt()
+    bad = np.where((sweep >= 1)[:, :, None], stale, good)
+    u, u_orc = X.distance(bad, *ex), X.distance(good, *ex)
+    print("GT_prob with the stale donor's prior: %.3g units against %.2f" % (u, u_orc))
+    assert not X.held(u, u_orc)
+    assert EC.grid_terms(EC.N_CU).S2 % 16 == 0           # (K = 16: step_k = 0, nothing to see)
+    for name in ("dense_fit_theta2_pairs_R2", "dense_fit_gt2_K7_R3"):
+        p = EC.problem_b(name)
+        g = EC.dense_route(p.spec, p.N, p.M, EC.N_CU)
+        sweep, j = _stale_k(p, g.nb_theta)
+
+        def stale_elements(A, B, GT):
+            late = sweep >= 1
+            A[late], B[late] = A.ravel()[j[late]], B.ravel()[j[late]]
+            GT[late] = GT.reshape(-1, p.T)[j[late]]
+            return A, B, GT
+        _theta_defect_fails(name, p, p.states[1], stale_elements)
+
+
+@pytest.mark.parametrize("name", ["dense_fit_theta2_pairs_R2", "dense_fit_gt2_K7_R3"])
+def test_e_batch_column_read_from_restart_0_fails(name):
+    """(e) in the strided sweeps restart rb reads column block 0: S and GT_prob of restart 0"""
+    p = EC.problem_b(name)
+    g = EC.dense_route(p.spec, p.N, p.M, EC.N_CU)
+    sweep, _ = _sweep_of(p, g.nb_theta)
+    s0 = p.states[0]
+    A0 = p.AD @ s0.ID
+    B0 = (p.DP @ s0.ID) - A0
+
+    def from_restart_0(A, B, GT):
+        late = sweep >= 1
+        A[late], B[late], GT[late] = A0[late], B0[late], s0.GT[late]
+        return A, B, GT
+    _theta_defect_fails(name, p, p.states[p.spec.restarts - 1], from_restart_0)
+
+
+def test_e_cell_rows_read_from_restart_0_fails():
+    """(e) on the cell side: a later sweep of vrx_cell_softmax reads restart 0's logLik_ID columns"""
+    name = "dense_fit_cell2_R3"
+    p = EC.problem_b(name)
+    g = EC.dense_route(p.spec, p.N, p.M, EC.N_CU)
+    sweep, _ = _cell_sweep(p, g)
+    be = EC.OracleBackend(p)
+    L0, L2 = be.loglik(be._st(0)), be.loglik(be._st(2))
+    ex = X.id_from_loglik(X.ld(L2), X.EPS * np.abs(X.ld(L2)), p.pri.ID_prior, p.K)["ID_prob"]
+    bad = np.where((sweep >= 1)[:, None], L0, L2)
+    u, u_orc = X.distance(O.softmax_log(bad - np.log(p.K)), *ex), X.distance(O.softmax_log(L2 - np.log(p.K)), *ex)
+    print("%s ID_prob from restart 0's logLik_ID: %.3g units against %.2f" % (name, u, u_orc))
+    assert not X.held(u, u_orc)
+
+
 # ---------------------------------------------------------------- the restatement against the fixture
 def test_exact_functions_agree_with_the_golden_onestep():
     """c1_onestep holds the real reference's values after each update; the extended-precision

@@ -19,6 +19,12 @@ one's input and never its excuse.  Every case asserts through ``info()`` / ``bui
 the path it names ran, and the cases that switch a fusion of the fit loop count its launches.
 Every case is also held, after its updates have run, to the instances of ``vrx_spmm_lds`` its passes
 launched (``DeviceModel.lds_launches()``): template arguments, column blocks, gather list, slabs.
+The dense cases (``dense_*``) are sized in the grid terms of the device's CU count so that the dense
+kernels run past their grid caps -- second and third sweeps of vrx_theta_partial, vrx_gt_update and
+vrx_cell_softmax, two and three strides of the shared theta's second stage, two and three trips of the
+ELBO's -- and each asserts the route it names from the model's record of its dense launches
+(``DeviceModel.dense_launches()``) against the restated grid arithmetic (``exact_cases.dense_grid``)
+before any number is compared.
 The cases are in tests/exact_cases.py; the same sweep runs on the CPU with the oracle in the
 device's place (tests/test_exact_cpu.py).
 
@@ -40,6 +46,7 @@ pytestmark = pytest.mark.gpu
 PINNED = {}
 
 _ROWS = []
+_ROUTES = {}        # dense case -> (flow, the route its launch record showed)
 
 
 @pytest.fixture(scope="module")
@@ -47,6 +54,7 @@ def va():
     import vireo_amd
     from vireo_amd import _lib
     _lib.require_gpu()          # fail loudly: there is no CPU fallback
+    EC.set_n_cu(_lib.device_info(0)["n_cu"])     # the dense cases' sizes follow the device's grid caps
     yield vireo_amd
     path = os.environ.get("VIREO_EXACT_UNITS_OUT")
     if path:
@@ -69,6 +77,17 @@ def _write_table(path):
                 tight = max(rows, key=lambda r: r[3] / r[5])
                 f.write("%-4s %-14s %10.3f units in %-28s %5.2f of the bound in %s\n"
                         % (flow, out, far[3], far[1], tight[3] / tight[5], tight[1]))
+        f.write("\n# the dense kernels past their grid caps: the route each case's launch record showed (asserted\n"
+                "# before any number was compared), its worst output in units and the largest share of a bound\n")
+        f.write("%-4s %-28s %10s %6s  %s\n" % ("flow", "case", "worst", "share", "route"))
+        for case, (flow, route) in _ROUTES.items():
+            rows = [r for r in _ROWS if r[0] == flow and r[1].split("[")[0] == case]
+            if rows:
+                f.write("%-4s %-28s %10.3f %6.2f  %s\n" % (flow, case, max(r[3] for r in rows),
+                                                          max(r[3] / r[5] for r in rows), route))
+        f.write("# not covered:\n")
+        for what, why in EC.NOT_COVERED:
+            f.write("#   %s -- %s\n" % (what, why))
 
 
 def _kind(p):
@@ -121,6 +140,47 @@ def _assert_instances(p, dm, seen):
             for l in got[o]:
                 assert (l.slab_rows, l.n_slab) == slabs[o], (name, o, l, slabs[o])
                 assert l.slab_rows % 16 == 0 and l.slab_rows >= 64, (name, o, l)
+
+
+def _assert_route(p, dm, flow):
+    """a dense case took the route it declares: the model's record of its dense launches
+    (``DeviceModel.dense_launches()``) against the restated grid arithmetic (``EC.dense_grid``) for this
+    device's CU count, and that arithmetic against the sweeps / strides / trips the case names.  After
+    flow A the last shared-theta update was finalised by vrx_theta_final and the last ELBO came from
+    vrx_elbo_final; after flow B's longest run the finalisation is the fused or the separate one by the
+    count of partials, and every ELBO but the last rode in the next theta launch where the case turns
+    that on."""
+    sp = p.spec
+    if not callable(sp.data):
+        return
+    rec = dm.dense_launches()
+    n_cu = rec["n_cu"]
+    assert n_cu == EC.N_CU == _lib_info()["n_cu"], (sp.name, rec)
+    assert EC.route_misses(sp, n_cu) == [], (sp.name, EC.route_misses(sp, n_cu))
+    g = EC.dense_route(sp, p.N, p.M, n_cu)
+    shared = p.kind == "vireo" and not sp.ase
+    fused_cells = flow == "B" and bool(sp.fused_softmax)
+    want = dict(nb_theta=g.nb_theta, n_cell_part=g.n_cell_part, n_gt_part=g.n_gt_part, n_th_part=g.n_th_part,
+                elbo_carrier="kernel", cell_source="cell_pass" if fused_cells else "softmax")
+    if shared:
+        want.update(theta_parts=g.nb_theta, theta_final="fused" if flow == "B" and g.fuse else "kernel")
+    if p.kind == "vireo":
+        want["nb_gt"] = g.nb_gt
+    if not fused_cells:
+        want.update(nb_cell=g.nb_cell, KP=g.KP)
+    rides = (flow == "B" and sp.iters >= 2 and sp.env.get("VIREO_ELBO_RIDE") == "1"
+             and (shared or p.kind != "vireo"))
+    if rides:
+        want.update(ride_cell_part=g.n_cell_part, ride_gt_part=g.n_gt_part, ride_th_part=g.n_th_part)
+    got = {k: rec[k] for k in want}
+    print("%-28s route %s" % (sp.name, rec))
+    assert got == want, (sp.name, got, want)
+    took = ["%s=%s" % (k, getattr(g, k)) for k in EC.ROUTE_KEYS if k in sp.route]
+    took += ["nb_theta=%d" % g.nb_theta, "nb_gt=%d" % rec["nb_gt"], "nb_cell=%d" % rec["nb_cell"], "KP=%d" % rec["KP"],
+             "parts=%d/%d/%d" % (g.n_cell_part, g.n_gt_part, g.n_th_part)]
+    if rides:
+        took.append("ride+kernel")
+    _ROUTES[sp.name] = (flow, " ".join(took))
 
 
 def _lib_info():
@@ -269,6 +329,7 @@ def test_each_update_against_exact(va, monkeypatch, name):
     be = DeviceBackend(p, counts)
     seen = _assert_path(p, be.dm, counts)
     out = EC.run_a(p, be)
+    _assert_route(p, be.dm, "A")
     _assert_instances(p, be.dm, seen)
     u_dev = EC.distances_a(p, out)
     u_orc = EC.distances_a(p, EC.run_a(p, EC.OracleBackend(p)))
@@ -283,7 +344,10 @@ def test_fit_loop_iterations_against_exact(va, monkeypatch, name):
     seen = _assert_path(p, be.batch or be.dm, counts)
     orc = EC.OracleBackend(p)
     for r in range(p.spec.restarts):
-        u_dev = EC.distances_b(p, EC.run_b(p, be, r), r)
+        snaps = EC.run_b(p, be, r)
+        if r == 0:
+            _assert_route(p, be.batch or be.dm, "B")
+        u_dev = EC.distances_b(p, snaps, r)
         if r == 0:
             _assert_launches(p, be)
             _assert_instances(p, be.batch or be.dm, seen)

@@ -102,6 +102,38 @@ def test_rounds_equal_the_reference(fixture, name):
     dev.close()
 
 
+@pytest.mark.parametrize("K", V.CAPPED_DONORS)
+@pytest.mark.parametrize("n_var", V.CAPPED_SIZES)
+def test_rounds_past_the_grid_cap_of_the_maximum(n_var, K):
+    """more variants than one sweep of vrx_barcode_max's capped grid (1 024 blocks x 256) holds: the second
+    and the third sweep, and vrx_barcode_max2 over all 1 024 partials.  Round 1 has its one maximum in the
+    last variant; round 2 ties on both sides of the cap and the median decides (tests/variant_select_np.py,
+    ``capped_case``; its properties are asserted in tests/test_variant_select_cpu.py).  Entropies, tie set,
+    median filter and picks bit for bit against the NumPy restatement."""
+    from vireo_amd.variant_select import BarcodeRounds
+    GT, vc = V.capped_case(n_var, K)
+    dev = BarcodeRounds(GT, vc)
+    rank = np.zeros(K, dtype=np.int64)
+    for rnd in range(2):
+        want, _ = V.entropies(GT, rank)
+        tied = np.flatnonzero(want == np.max(want))
+        kept = tied[vc[tied] >= np.median(vc[tied])]
+        top, n_tied, n_kept = dev.round()
+        got = dev.entropies()
+        where = (n_var, K, rnd)
+        assert np.array_equal(bits(got), bits(want)), (where, np.flatnonzero(bits(got) != bits(want))[:8])
+        assert bits(top) == bits(np.max(want)) and (n_tied, n_kept) == (len(tied), len(kept)), (where, top, n_tied, n_kept)
+        for r in sorted({0, len(kept) // 2, len(kept) - 1}):
+            idx, e = dev.pick(r)
+            assert idx == kept[r] and bits(e) == bits(want[idx]), (where, r, idx)
+        if rnd == 0:
+            assert kept.tolist() == [n_var - 1]
+            rank = V.dense_rank(rank, GT[-1])
+            dev.choose(GT[-1])
+            assert np.array_equal(dev.rank, rank)
+    dev.close()
+
+
 @pytest.mark.parametrize("counts,n_kept", [
     ([5.0, 1.0, 3.0], 2),                     # odd: the middle one, 3
     ([5.0, 1.0, 3.0, 4.0], 2),                # even: (3 + 4) / 2 = 3.5

@@ -75,6 +75,28 @@ def test_special_cases_are_what_they_claim(fixture):
     assert len(V.fixture_case(fixture, "k1")["chosen"]) == 0
 
 
+@pytest.mark.parametrize("K", V.CAPPED_DONORS)
+@pytest.mark.parametrize("n_var", V.CAPPED_SIZES)
+def test_capped_cases_decide_past_the_grid_cap(n_var, K):
+    """the inputs of test_gpu_variant_select.py's runs past the cap of vrx_barcode_max: round 1 has ONE
+    maximum, in the last variant, which a single sweep of the capped grid never reads; round 2 ties on both
+    sides of the cap (below it only where the chosen variant is the one index past it) and the median
+    keeps some of the tied and drops others"""
+    GT, vc = V.capped_case(n_var, K)
+    assert GT.shape == (n_var, K) and n_var > V.BC_GRID and GT.max() == 2
+    rank = np.zeros(K, dtype=np.int64)
+    ent, _ = V.entropies(GT, rank)
+    assert np.flatnonzero(ent == ent.max()).tolist() == [n_var - 1] and n_var - 1 >= V.BC_GRID
+    ent, _ = V.entropies(GT, V.dense_rank(rank, GT[-1]))
+    tied = np.flatnonzero(ent == ent.max())
+    kept = tied[vc[tied] >= np.median(vc[tied])]
+    assert 0 < len(kept) < len(tied) and tied.min() < V.BC_GRID
+    if K == 2 or n_var > V.BC_GRID + 8:
+        assert tied.max() >= V.BC_GRID and kept.min() < V.BC_GRID <= kept.max()
+    if n_var > V.BC_GRID + 8:
+        assert np.setdiff1d(tied, kept).max() >= V.BC_GRID                  # the median drops one past the cap too
+
+
 def test_sum_rule_is_np_sum():
     rs = np.random.RandomState(0)
     for n in range(1, 129):

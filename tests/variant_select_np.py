@@ -183,6 +183,39 @@ def fixture_case(fixture, name):
     return {key: fixture["%s_%s" % (name, key)] for key in FIXTURE_KEYS}
 
 
+# ---- past the grid cap of the maximum --------------------------------------------------------------
+# vrx_barcode_max launches at most VRX_BC_MAX_BLOCKS blocks of VRX_BC_BLOCK threads (csrc/vrx_barcode.h: 1024
+# x 256) and strides beyond; vrx_barcode_max2 then takes 1 024 partials, four per thread.
+BC_GRID = 1024 * 256
+CAPPED_SIZES = (BC_GRID + 1, 2 * BC_GRID + 3)          # the second and the third sweep
+CAPPED_DONORS = (2, 9)
+
+
+def capped_case(n_var, K):
+    """(GT, var_count) of three categories whose first two rounds decide past the cap.
+    Round 1: the one maximum is the LAST variant, which only a strided sweep reaches (every other variant
+    holds fewer categories, or the same ones less evenly).  Round 2, once that variant is chosen: the tie
+    set has members on both sides of index BC_GRID and the median of var_count decides between them.
+    K = 9: six planted variants whose pattern splits every class of the chosen one; K = 2: the chosen
+    variant tells both donors apart, so every variant ties."""
+    rs = np.random.RandomState(7 * K + n_var % 1000)
+    vc = rs.randint(21, 200, n_var).astype(float)
+    if K == 2:
+        GT = np.repeat(rs.randint(0, 3, (n_var, 1)), 2, axis=1)      # (a, a): entropy 0
+        GT[-1] = [0, 1]
+        vc[-1] = 250.0                                               # (kept by any median of these counts)
+        return GT, vc
+    assert K == 9
+    GT = rs.randint(0, 2, (n_var, K))                                 # two categories: at most 1 bit
+    GT[-1] = [0, 0, 0, 1, 1, 1, 2, 2, 2]                              # log2(3) bits, alone
+    # (at BC_GRID + 1 variants the only index past the cap is the chosen variant's own: the six stay below)
+    past = [BC_GRID, BC_GRID + 6, n_var - 2] if n_var > BC_GRID + 8 else [BC_GRID - 4, BC_GRID - 3, BC_GRID - 2]
+    planted = [5, 100000, BC_GRID - 1] + past
+    GT[planted] = [0, 1, 2, 0, 1, 2, 0, 1, 1]                         # uneven now, eight bins of nine next round
+    vc[planted] = [1.0, 9.0, 2.0, 8.0, 3.0, 7.0]                      # median 5: survivors 100000 and past[0], past[2]
+    return GT, vc
+
+
 # ---- the GTbarcode runs of tests/golden/barcode/<run>/ -------------------------------------------
 BARCODE_VCF = os.path.join(HERE, "golden", "data", "donors.cellSNP.vcf.gz")
 BARCODE_RUNS = {

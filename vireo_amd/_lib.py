@@ -140,6 +140,7 @@ SIGNATURES = {
     "vrx_stop_verdicts": (C.c_int, [C.c_int, C.c_int64, _I32, _D, _I32, _D]),
     "vrx_model_info": (C.c_int, [_P, _I32]),
     "vrx_model_lds_launches": (C.c_int, [_P, C.c_int32, _I32, C.c_int32, _I32]),
+    "vrx_model_dense_launches": (C.c_int, [_P, _I32]),
     "vrx_model_profile": (C.c_int, [_P, C.c_int32]),
     "vrx_model_profile_read": (C.c_int, [_P, _D, _I64]),
     "vrx_model_run_iters": (C.c_int, [_P, C.c_int32, C.c_int32, _D, _D]),

@@ -1925,6 +1925,8 @@ struct vrx_model {
     hipEvent_t t0 = nullptr, t1 = nullptr;
     // the launches of the last LDS-resident pass of each orientation (0 variant, 1 cell): vrx_model_lds_launches
     std::vector<LdsLaunch> lds_log[2];
+    // what the dense kernels' last launches of each kind did: vrx_model_dense_launches
+    int32_t dense_log[VRX_DENSE_FIELDS] = {0, 0, VRX_DENSE_THETA_NONE, 0, 0, 0, 0, -1, 0, 0, 0, 0, 0, 0, VRX_DENSE_ELBO_NONE};
 
     ~vrx_model() {
         if (h_pin) (void)hipHostFree(h_pin);
@@ -2786,11 +2788,20 @@ static int cell_pass_softmax(vrx_model* m) {
     F.ID = m->ID.p;
     F.part = m->part_cell.p;
     m->n_cell_part = (int)(o.n_seg / VRX_WAVES);
+    m->dense_log[VRX_DENSE_CELL_SOURCE] = VRX_DENSE_CELL_FUSED;
     m->l_pending = false;
     return launch_spmm<1>(m, o, m->W.p, m->Kt, m->LID.p, m->PC.p, &F);
 }
 
 static VrxElboIn elbo_inputs(vrx_model* m);
+
+static void log_elbo(vrx_model* m, const VrxElboIn& e, int carrier) {
+    const int at = carrier == VRX_DENSE_ELBO_RIDE ? VRX_DENSE_RIDE_CELL : VRX_DENSE_ELBO_CELL;
+    m->dense_log[at] = e.n_cell_part;
+    m->dense_log[at + 1] = e.n_gt_part;
+    m->dense_log[at + 2] = e.n_th_part;
+    m->dense_log[VRX_DENSE_ELBO_CARRIER] = carrier;
+}
 
 // the ELBO a previous iteration left deferred (with its stop rule), as the extra block of the
 // theta launch that carries it; off when none waits
@@ -2801,6 +2812,7 @@ static VrxElboRide take_ride(vrx_model* m) {
     E.in = elbo_inputs(m);
     E.rule = m->elbo_rule;
     m->elbo_deferred = false;
+    log_elbo(m, E.in, VRX_DENSE_ELBO_RIDE);
     return E;
 }
 
@@ -2823,6 +2835,7 @@ static int theta_step(vrx_model* m, int update, bool defer_final = false) {
         const VrxElboRide E = take_ride(m);
         m->th_cur ^= 1;
         m->n_th_part = (int)nb;
+        m->dense_log[VRX_DENSE_NB_THETA] = (int32_t)nb;
         vrx_bmm_theta<<<dim3(nb + E.on, m->R), VRX_BLOCK, 0, s>>>(
             m->NK, update, c.fix_beta_sum, reinterpret_cast<double2*>(m->S.p), f.npiece,
             reinterpret_cast<const double2*>(m->RV.p), m->prior1.p,
@@ -2831,6 +2844,7 @@ static int theta_step(vrx_model* m, int update, bool defer_final = false) {
         m->w_valid = true;
     } else if (c.ase_mode) {
         if ((rc = take_S(m, nullptr))) return rc;  // (the ASE kernel does not fuse the range sum)
+        m->dense_log[VRX_DENSE_NB_THETA] = m->nb_throws;
         vrx_theta_ase<<<dim3(m->nb_throws, m->R), VRX_BLOCK, 0, s>>>(
             m->N, m->K, m->T, update, c.fix_beta_sum, reinterpret_cast<const double2*>(m->S.p),
             m->GT.p, m->prior1.p, m->prior2.p, (int)m->prior_rows, m->mu.p, m->sm.p, m->psi.p,
@@ -2842,6 +2856,7 @@ static int theta_step(vrx_model* m, int update, bool defer_final = false) {
             if ((rc = take_S(m, &f))) return rc;  // every layout fuses here
             auto* kern = m->T == 3 ? vrx_theta_partial<3> : vrx_theta_partial<VRX_MAXT>;
             const VrxElboRide E = take_ride(m);  // the previous iteration's ELBO + stop rule: one extra block
+            m->dense_log[VRX_DENSE_NB_THETA] = m->nb_theta;
             kern<<<dim3(m->nb_theta + E.on, m->R), VRX_BLOCK, 0, s>>>(
                 m->NK, m->T, reinterpret_cast<double2*>(m->S.p), f.npiece,
                 reinterpret_cast<const double2*>(f.partial), f.n_vrows, f.vptr,
@@ -2855,6 +2870,10 @@ static int theta_step(vrx_model* m, int update, bool defer_final = false) {
         if (update && defer_final && m->nb_theta <= fuse_max) {
             m->theta_pending = true;
         } else {
+            if (update) {
+                m->dense_log[VRX_DENSE_THETA_FINAL] = VRX_DENSE_THETA_KERNEL;
+                m->dense_log[VRX_DENSE_THETA_PARTS] = m->nb_theta;
+            }
             vrx_theta_final<<<m->R, VRX_BLOCK, 0, s>>>(m->nb_theta, m->T, update, c.fix_beta_sum,
                                                      m->part_theta.p, m->prior1.p, m->prior2.p,
                                                      m->mu.p, m->sm.p, m->psi.p, m->part_th.p, m->ctl.p);
@@ -2885,7 +2904,10 @@ static int gt_step(vrx_model* m, int learn) {
         F.psi = m->psi.p;
         F.kl_out = m->part_th.p;
         m->theta_pending = false;
+        m->dense_log[VRX_DENSE_THETA_FINAL] = VRX_DENSE_THETA_FUSED;
+        m->dense_log[VRX_DENSE_THETA_PARTS] = F.n_part;
     }
+    m->dense_log[VRX_DENSE_NB_GT] = m->nb_gt;
     auto* kern = m->T == 3 ? vrx_gt_update<3> : vrx_gt_update<VRX_MAXT>;
     kern<<<dim3(m->nb_gt, m->R), VRX_BLOCK, 0, m->p->stream>>>(
         m->NK, m->K, m->T, learn, m->cfg.ase_mode, m->N, reinterpret_cast<const double2*>(m->S.p),
@@ -2927,6 +2949,9 @@ static int softmax_step(vrx_model* m, int update) {
     int rc = take_LID(m, &f);
     if (rc) return rc;
     m->n_cell_part = m->nb_cell;
+    m->dense_log[VRX_DENSE_NB_CELL] = m->nb_cell;
+    m->dense_log[VRX_DENSE_KP] = m->KP;
+    m->dense_log[VRX_DENSE_CELL_SOURCE] = VRX_DENSE_CELL_SOFTMAX;
 #define VRX_SM_CASE(KPV)                                                                        \
     case KPV:                                                                                   \
         vrx_cell_softmax<KPV><<<dim3(m->nb_cell, m->R), VRX_BLOCK, 0, s>>>(                     \
@@ -2950,7 +2975,9 @@ static int softmax_step(vrx_model* m, int update) {
 // ELBO of iteration rule.it into the trace; evaluates the stop rule when it is active
 static int elbo_step(vrx_model* m, const VrxStopRule& rule) {
     ProfScope ps(m, VRX_KERN_DENSE);
-    vrx_elbo_final<<<m->R, VRX_BLOCK, 0, m->p->stream>>>(elbo_inputs(m), rule, m->ctl.p);
+    const VrxElboIn in = elbo_inputs(m);
+    log_elbo(m, in, VRX_DENSE_ELBO_KERNEL);
+    vrx_elbo_final<<<m->R, VRX_BLOCK, 0, m->p->stream>>>(in, rule, m->ctl.p);
     VRX_HIP(hipGetLastError());
     return VRX_OK;
 }
@@ -3268,6 +3295,13 @@ extern "C" int vrx_model_lds_launches(vrx_model* m, int32_t orient, int32_t* out
     const size_t n = std::min(log.size(), (size_t)cap);
     if (n) memcpy(out, log.data(), n * sizeof(LdsLaunch));
     *n_out = (int32_t)log.size();
+    return VRX_OK;
+}
+
+extern "C" int vrx_model_dense_launches(vrx_model* m, int32_t* out) {
+    VRX_REQUIRE(m && out, "vrx_model_dense_launches: null argument");
+    m->dense_log[VRX_DENSE_N_CU] = m->p->n_cu;
+    memcpy(out, m->dense_log, sizeof(m->dense_log));
     return VRX_OK;
 }
 

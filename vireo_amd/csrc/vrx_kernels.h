@@ -2088,7 +2088,7 @@ __global__ __launch_bounds__(VRX_BLOCK) void vrx_cell_softmax(
     const int stop = ctl[rb * VRX_CTL_WORDS + VRX_CTL_STOP];
     const int kl = threadIdx.x % KP;
     double acc[2] = {0.0, 0.0};
-    // Grid-stride over the cells: the host caps the grid (8 blocks per CU), a block takes the cell
+    // Grid-stride over the cells: the host caps the grid (4 blocks per CU by default), a block takes the cell
     // groups b, b + grid, ... and ends in ONE block sum -- large M paid a prologue (stop word, first
     // load) and a block reduction per 256 threads, three waves of blocks deep at c5.  Every thread
     // runs every sweep (`live` guards the work: the group reductions want whole groups).

@@ -14,6 +14,11 @@ from ._lib import dptr, f64
 # one column-block launch of an LDS-resident pass (include/vireo_hip.h, vrx_model_lds_launches)
 LdsLaunch = collections.namedtuple("LdsLaunch", "mode rw padk split form kb ld perm slab_rows n_slab")
 
+# the dense kernels' launch record (include/vireo_hip.h, vrx_model_dense_launches: VRX_DENSE_*)
+DENSE_FIELDS = 15
+THETA_FINAL = (None, "fused", "kernel")
+ELBO_CARRIER = (None, "kernel", "ride")
+
 
 def _prior_rows(P, full_rows):
     """(array-or-None, rows) for a prior table: 0 = uniform (constant table), 1 = one
@@ -201,6 +206,18 @@ class DeviceModel(_lib.Handle):
             out.append([LdsLaunch(*(int(v) for v in row[:7]), bool(row[7]), int(row[8]), int(row[9]))
                         for row in a])
         return tuple(out)
+
+    def dense_launches(self):
+        """what the dense kernels' last launches of each kind did (vrx_model_dense_launches): grid sizes,
+        how the shared theta was finalised, where the cell partials came from, and the partial counts
+        and carrier of the last ELBO"""
+        a = np.zeros(DENSE_FIELDS, dtype=np.int32)
+        _lib.check(_lib.lib().vrx_model_dense_launches(self._h, a.ctypes.data_as(C.POINTER(C.c_int32))))
+        v = [int(x) for x in a]
+        return dict(n_cu=v[0], nb_theta=v[1], theta_final=THETA_FINAL[v[2]], theta_parts=v[3], nb_gt=v[4],
+                    nb_cell=v[5], KP=v[6], cell_source={-1: None, 0: "softmax", 1: "cell_pass"}[v[7]],
+                    n_cell_part=v[8], n_gt_part=v[9], n_th_part=v[10], ride_cell_part=v[11], ride_gt_part=v[12],
+                    ride_th_part=v[13], elbo_carrier=ELBO_CARRIER[v[14]])
 
     # ---- timing -----------------------------------------------------------------------
     def profile(self, enable=True):
